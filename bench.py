@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the PARQ recurrent decoder path on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--scenes-per-gpu B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--scenes-per-gpu B] [--dump-outputs DIR]
 
 metric  : decoder-iterations/sec = scenes x recurrent iterations / wall time of
           PARQDecoder.forward (prologue incl. the hoisted K/V projection + I iterations)
@@ -505,6 +505,8 @@ def train_bench(args):
         loss = step()
     torch.cuda.synchronize(); parallel.barrier(); torch.cuda.synchronize()
     dt_own = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict([("loss", loss.detach())] + [("param_" + k, p.detach()) for k, p in dec.named_parameters()]))
     dt = parallel.max_over_ranks(dt_own, device=red_dev)
     per_rank_ms = [x / args.steps * 1e3 for x in parallel.gather_over_ranks(dt_own, device=red_dev)]
     final_loss, train_mode = float(loss.detach()), dec._train_mode()
@@ -538,6 +540,29 @@ def train_bench(args):
     if world > 1:
         parallel.barrier()
         torch.distributed.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` as <out_dir>/<name>.npy in float32 (float64 stays float64).  A tensor that would
+    take the total past DUMP_LIMIT_BYTES is replaced by a fixed sample of its flattened elements (seeded, the same in every run),
+    written as <name>.sample.npy beside <name>.sample_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        fname = name.replace("/", "_")
+        if total + a.nbytes > DUMP_LIMIT_BYTES:
+            n = min(a.size, max(0, (DUMP_LIMIT_BYTES - total - 16 * 1024) // (a.itemsize + 8)), 1 << 20)
+            idx = np.sort(np.random.default_rng(1234).choice(a.size, size=n, replace=False)).astype(np.int64)
+            np.save(os.path.join(out_dir, fname + ".sample_index.npy"), idx)
+            a, fname = a.reshape(-1)[idx], fname + ".sample"
+            total += idx.nbytes
+        np.save(os.path.join(out_dir, fname + ".npy"), a)
+        total += a.nbytes
 
 
 def parq_env():
@@ -608,9 +633,15 @@ def main():
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS), help="BASELINE.json configuration: cfg3 (default) is the one the "
                     "metric is quoted on = the headline; cfg2 (bf16) / cfg5 (fp16) are the reduced-precision configurations, emitted as "
                     "the same JSON line with their own roofline and bounded cpu_baseline (NOT the headline number)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32; rank 0): "
+                         "the forward's per-iteration output tensors, or with --train the loss and the updated parameters.  Inputs and "
+                         "weights are seeded, so two builds run with the same arguments can be compared output for output")
     ap.add_argument("--dim", type=int, default=256, help="decoder width; 256 = the BASELINE metric (default).  1024 = the reference's "
                     "shipped DEC_DIM (head dim 256): reported beside the headline, NOT the BASELINE metric")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     conf = CONFIGS[args.config]
     if "dim" in conf:
         args.dim = conf["dim"]
@@ -676,9 +707,12 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     dt_own = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"it%d_%s" % (k, key): v for k, o in enumerate(last) for key, v in o.items()})
+    del last
     dt = parallel.max_over_ranks(dt_own, device=red_dev)
     per_rank_ms = [x / args.steps * 1e3 for x in parallel.gather_over_ranks(dt_own, device=red_dev)]
     per_rank_cpus = parallel.gather_over_ranks(float(len(pinned)), device=red_dev)

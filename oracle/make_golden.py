@@ -45,6 +45,9 @@ Cases:
                  (transformer_parq.py:377-380) scaled by 4, so that rows rest on a handful of keys (row probability sums down to ~1:
                  the regime trained detectors attend in) — consumed teacher-forced at an unrelaxed 1e-4 in whatever
                  tier the peakedness guard of attention mode "split8" selects (the guard has to trip on it)
+  g22_reference_ops the reference's free-running fp32 outputs (all iterations) at the three shapes of
+                 tests/test_oracle_vs_reference.py (weights seed 901, scene seed 902): what the oracle's reference_ops
+                 mode, bench.py's cpu_baseline, is held to without the reference tree
 """
 from __future__ import annotations
 
@@ -445,6 +448,38 @@ def main(only=None):
         make_f1_golden(ref)
     if not only or "g13_lr_schedule" in only:
         make_lr_golden(ref)
+    if not only or "g22_reference_ops" in only:
+        make_reference_ops_golden(ref)
+
+
+REFERENCE_OPS_SHAPES = {"cfg1": dict(V=2, h=60, w=80, Q=64, I=1), "cfg2_shape_fp32": dict(V=5, h=120, w=160, Q=128, I=4),
+                        "cfg3": dict(V=10, h=120, w=160, Q=256, I=8)}
+REFERENCE_OPS_SEEDS = dict(wseed=901, sseed=902)
+
+
+def reference_ops_case_inputs(sh):
+    cfg = synth.decoder_cfg(dim=256, queries=sh["Q"], heads=4, ffn=768, layers=sh["I"])
+    W = synth.make_decoder_weights(cfg, REFERENCE_OPS_SEEDS["wseed"])
+    sc = synth.make_scene(REFERENCE_OPS_SEEDS["sseed"], 1, sh["V"], sh["h"], sh["w"], 256)
+    return cfg, W, sc
+
+
+def make_reference_ops_golden(ref):
+    arrays = {}
+    for name, sh in REFERENCE_OPS_SHAPES.items():
+        cfg, W, sc = reference_ops_case_inputs(sh)
+        dec = RL.build_reference_decoder(ref, cfg, W)
+        t = torch.from_numpy
+        with torch.no_grad():
+            outs = dec(t(sc["tokens"]), ref.Camera(t(sc["camera"])), ref.Pose(t(sc["T_camera_pseudoCam"])),
+                       ref.Pose(t(sc["T_world_pseudoCam"])), ref.Pose(t(sc["T_world_local"])))
+        for k, o in enumerate(outs):
+            for key in KEYS:
+                arrays["%s_it%d_%s" % (name, k, key)] = o[key].detach().numpy().astype(np.float32)
+    meta = dict(shapes=REFERENCE_OPS_SHAPES, **REFERENCE_OPS_SEEDS)
+    arrays["meta"] = np.frombuffer(json.dumps(meta, sort_keys=True).encode(), dtype=np.uint8)
+    np.savez_compressed(os.path.join(OUT_DIR, "g22_reference_ops.npz"), **arrays)
+    print("wrote g22_reference_ops", len(arrays) - 1, "arrays")
 
 
 PARSE_CASE = dict(seed=41, B=2, Q=96, track_scale=[-1.5, 1.5, -2, 1, 0, 2])

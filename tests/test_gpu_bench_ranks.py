@@ -25,6 +25,14 @@ def _run(extra, gpus=2):
     return json.loads(lines[0])
 
 
+def _need_gpus(n):
+    """The eight-rank launcher runs only where every rank has a GPU of its own: on fewer GPUs several rank processes would hold one
+    device at the same time."""
+    have = torch.cuda.device_count()
+    if have < n:
+        pytest.skip("needs %d GPUs (one per rank), found %d" % (n, have))
+
+
 def test_bench_two_ranks_forward_line():
     d = _run(["--steps", "4", "--warmup", "1"])
     want_backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
@@ -50,9 +58,10 @@ def test_bench_two_ranks_training_line():
 
 def test_bench_eight_ranks_launcher_smoke():
     """the self-launcher, the rendezvous port, the per-rank host-core slices and the shutdown at EIGHT local ranks,
-    before the driver's first 8-GPU run (train.py:103-125 is the reference's launcher).  On a 1-GPU lease all eight ranks share cuda:0
-    over gloo — the numbers mean nothing, the rank path is the subject: eight per-rank step times, host-core slices that are
-    pairwise disjoint (where the topology is readable), one JSON line, exit code 0 (clean destroy_process_group)."""
+    before the driver's first 8-GPU run (train.py:103-125 is the reference's launcher).  Needs eight GPUs, one per rank.  The rank path
+    is the subject: eight per-rank step times, host-core slices that are pairwise disjoint (where the topology is readable), one
+    JSON line, exit code 0 (clean destroy_process_group)."""
+    _need_gpus(8)
     d = _run(["--steps", "2", "--warmup", "1"], gpus=8)
     want_backend = "nccl" if torch.cuda.device_count() >= 8 else "gloo"
     assert d["n_gpus"] == 8 and d["collective_backend"] == want_backend
@@ -73,6 +82,7 @@ def test_bench_eight_ranks_launcher_smoke():
 def test_bench_eight_ranks_four_scenes_per_gpu_variant():
     """SURVEY.md section 8(d) names two lines for the scaling runs: B = #GPUs and a B = 4 per GPU variant (BASELINE cfg 4's shard size).
     The same launcher at eight ranks with --scenes-per-gpu 4, so that the driver's first 8-GPU run can take both lines."""
+    _need_gpus(8)
     d = _run(["--steps", "1", "--warmup", "1", "--scenes-per-gpu", "4"], gpus=8)
     assert d["n_gpus"] == 8 and d["config"]["scenes_per_gpu"] == 4 and "dp8" in d["config"]["parallelism"]
     assert len(d["per_rank_ms_per_step"]) == 8 and all(t > 0 for t in d["per_rank_ms_per_step"])
@@ -81,12 +91,13 @@ def test_bench_eight_ranks_four_scenes_per_gpu_variant():
     assert d["guard_policy_cost"] is None if "guard_policy_cost" in d else True     # (single-rank extras stay out of multi-rank lines)
 
 
-def test_bench_single_rank_default_line_contract():
+def test_bench_single_rank_default_line_contract(tmp_path):
     """The driver's N = 1 command (fewer steps, without the CPU baseline and the optional records): ONE JSON line with the contract's
     fields, the roofline object of the dominant kernel, and the sub-records measured beside `value` — the strict fp16 x 3 run and two
     scenes in flight on two HIP streams, whose outputs must be bit for bit those of one-at-a-time forwards."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-b32",
-                        "--no-peaked", "--no-pmc"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--no-peaked", "--no-pmc", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=900,
+                       cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -96,6 +107,14 @@ def test_bench_single_rank_default_line_contract():
         assert key in d, key
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["unit"] == "decoder-iterations/sec" and d["higher_is_better"] is True
     assert abs(d["value"] - 8 * d["steps"] / (d["ms_per_step"] * 1e-3 * d["steps"])) < 1e-6 * d["value"]
+    # --dump-outputs: the six outputs of each of the 8 iterations of the last timed forward, finite float32
+    import numpy as np
+    from parq_amd.decoder import OUTPUT_KEYS
+    dumped = sorted(os.listdir(tmp_path / "out"))
+    assert dumped == sorted("it%d_%s.npy" % (k, key) for k in range(8) for key in OUTPUT_KEYS), dumped
+    for f in dumped:
+        a = np.load(tmp_path / "out" / f)
+        assert a.dtype == np.float32 and a.shape[0] == 1 and np.isfinite(a).all(), f
     rf = d["roofline"]
     assert rf["bound"] == "hbm" and rf["unit"] == "GB/s" and 0.2 < rf["frac"] < 1.0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-9
     two = d["two_scenes_in_flight"]

@@ -1,10 +1,14 @@
-"""DEV-CONTAINER gate of BASELINE.md §3 (skipped when /root/reference is absent, i.e. on the GPU box): the CPU restatement that
-bench.py times as `cpu_baseline` (oracle/parq_oracle.py, reference_ops=True: per-iteration K/V in-projection, materialised
-(H, Q, N) softmax, head-averaged attention weights) against the IMPORTED reference at the BASELINE shapes —
-  * free-running outputs of all iterations within 1e-5 on all six tensors (same ATen ops in the same order: bit-identical in
-    practice), and
-  * wall time not more than ~10 % above the reference's (measured: 0.73-0.85x, i.e. the reported CPU baseline is slightly
-    generous to the CPU and the GPU/CPU ratio conservative)."""
+"""Gate of BASELINE.md §3: the CPU restatement that bench.py times as `cpu_baseline` (oracle/parq_oracle.py, reference_ops=True:
+per-iteration K/V in-projection, materialised (H, Q, N) softmax, head-averaged attention weights) against the reference at the
+BASELINE shapes —
+  * always: the reference's own fp32 outputs of every iteration, stored in tests/golden/g22_reference_ops.npz
+    (oracle/make_golden.py), within 1e-5 on all six tensors, teacher-forced: iteration k is fed the reference points the
+    reference itself used there (its coord_pos), because free-running, the recurrence on white-noise features amplifies the
+    rounding differences of another host's GEMM blocking or thread count far beyond any tolerance, and
+  * where the reference tree is importable (the development container: oracle/reference_loader.py), the reference run in the same
+    process: free-running outputs of all iterations within 1e-5 on all six tensors (same ATen ops in the same order, same host:
+    bit-identical in practice), and wall time not more than ~10 % above the reference's (measured: 0.73-0.85x, i.e. the reported
+    CPU baseline is slightly generous to the CPU and the GPU/CPU ratio conservative)."""
 import time
 
 import numpy as np
@@ -15,20 +19,29 @@ from parq_amd import synth
 from oracle import parq_oracle as O
 from oracle import reference_loader as RL
 
-pytestmark = pytest.mark.skipif(not RL.available(), reason="needs the reference tree (dev container only)")
+import golden_util as G
 
 SHAPES = {"cfg1": dict(V=2, h=60, w=80, Q=64, I=1), "cfg2_shape_fp32": dict(V=5, h=120, w=160, Q=128, I=4),
           "cfg3": dict(V=10, h=120, w=160, Q=256, I=8)}
 
 
+def _worst(ref_outs, port_outs):
+    worst = 0.0
+    for oa, ob in zip(ref_outs, port_outs):
+        for key in ob:
+            x, y = np.asarray(oa[key], dtype=np.float64), ob[key].numpy().astype(np.float64)
+            worst = max(worst, float((np.abs(x - y) / np.maximum(1.0, np.abs(x))).max()))
+    return worst
+
+
 @pytest.mark.parametrize("name", list(SHAPES))
 def test_cpu_port_matches_the_imported_reference_in_outputs_and_wall_time(name):
     sh = SHAPES[name]
-    ref = RL.load()
+    meta, z = G.load("g22_reference_ops")
+    assert meta["shapes"][name] == sh and (meta["wseed"], meta["sseed"]) == (901, 902), meta
     cfg = synth.decoder_cfg(dim=256, queries=sh["Q"], heads=4, ffn=768, layers=sh["I"])
     W = synth.make_decoder_weights(cfg, 901)
     sc = synth.make_scene(902, 1, sh["V"], sh["h"], sh["w"], 256)
-    rdec = RL.build_reference_decoder(ref, cfg, W)
     od = O.OracleDecoder(cfg, W, synth.SCANNET_MEAN_SIZES, reference_ops=True)
     t = torch.from_numpy
 
@@ -37,21 +50,30 @@ def test_cpu_port_matches_the_imported_reference_in_outputs_and_wall_time(name):
             return rdec(t(sc["tokens"]), ref.Camera(t(sc["camera"])), ref.Pose(t(sc["T_camera_pseudoCam"])),
                         ref.Pose(t(sc["T_world_pseudoCam"])), ref.Pose(t(sc["T_world_local"])))
 
-    def run_port():
+    def run_port(forced=None):
         with torch.no_grad():
-            return od.forward(sc["tokens"], sc["camera"], sc["T_camera_pseudoCam"], sc["T_world_pseudoCam"], sc["T_world_local"])
+            return od.forward(sc["tokens"], sc["camera"], sc["T_camera_pseudoCam"], sc["T_world_pseudoCam"], sc["T_world_local"],
+                              forced_refs=forced)
 
+    # the reference's stored outputs: every iteration, all six tensors, teacher-forced with the reference's own reference points
+    stored = [{key: z["%s_it%d_%s" % (name, k, key)] for key in G.KEYS} for k in range(sh["I"])]
+    forced = [O.normalize(t(o["coord_pos"]), cfg.TRANSFORMER.SCALE) for o in stored]
+    port = run_port(forced)
+    assert len(port) == sh["I"]
+    worst_stored = _worst(stored, port)
+    print("\n%s: port vs the reference's stored outputs (teacher-forced) max err %.2e" % (name, worst_stored))
+    assert worst_stored <= 1e-5, worst_stored
+    if not RL.available():               # the live comparison and the wall-time ratio need the reference tree itself
+        return
+
+    ref = RL.load()
+    rdec = RL.build_reference_decoder(ref, cfg, W)
     reps = 2
     t_ref, t_port = [], []
-    run_port()                                           # thread pools, allocator
     for _ in range(reps):
         t0 = time.perf_counter(); a = run_ref(); t_ref.append(time.perf_counter() - t0)
         t0 = time.perf_counter(); b = run_port(); t_port.append(time.perf_counter() - t0)
-    worst = 0.0
-    for oa, ob in zip(a, b):
-        for key in ob:
-            x, y = oa[key].numpy().astype(np.float64), ob[key].numpy().astype(np.float64)
-            worst = max(worst, float((np.abs(x - y) / np.maximum(1.0, np.abs(x))).max()))
+    worst = _worst([{k: v.numpy() for k, v in o.items()} for o in a], b)
     ratio = min(t_port) / min(t_ref)
     print("\n%s: port vs reference max err %.2e; wall %.2f s vs %.2f s (ratio %.2f); %.2f decoder-iterations/s on %d threads"
           % (name, worst, min(t_port), min(t_ref), ratio, sh["I"] / min(t_port), torch.get_num_threads()))
