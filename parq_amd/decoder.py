@@ -216,10 +216,20 @@ class _WsEntry:
 
     def __init__(self, ws, slot, stream):
         self.ws, self.slot, self.stream = ws, slot, stream
-        self.epoch = 0                # epoch of the last forward enqueued here (the device stores it into the slot's progress word)
+        self.epoch = 0                # epoch of the last forward enqueued here (a range check reads its own forward's, _Run.epoch)
         self.graphs = {}              # key -> parq_graph_t (one per (weights, attention settings): the current one; stale ones are retired)
         self.last_key = None          # key of the previous forward in this workspace (a graph is captured when a key repeats)
         self.replays = 0
+
+
+class _Run:
+    """One enqueued inference forward as its range check must see it: the workspace, mirror slot and epoch it ran with and the
+    arithmetic settings (attention mode, head tiers, seam fusion) it was enqueued under.  A deferred check (InFlight) runs after
+    other forwards may have re-used the workspace's fields or switched the module to safer arithmetic: it reads this, not them."""
+    __slots__ = ("entry", "slot", "epoch", "settings")
+
+    def __init__(self, entry, slot, epoch, settings):
+        self.entry, self.slot, self.epoch, self.settings = entry, slot, epoch, settings
 
 
 class _WsCache(dict):
@@ -352,6 +362,7 @@ class PARQDecoder(_Tracked, nn.Module):
         self._arena_streams = {}          # stream id -> stream object of every stream that is ordered behind the current arena
         self._defer = None                # InFlight.submit(): list that receives the settle callable of a forward instead of a host wait
         self._epoch = 0                   # counter of inference forwards (parq_set_progress)
+        self._pending = {}                # mirror slot -> number of forwards in it whose deferred check has not run yet
         self._profiling = False
         # Captured forward (include/parq_hip.h parq_forward_capture): the iterations of the second inference forward of a (shape,
         # stream, weights, attention settings) are recorded into a HIP graph and later forwards replay it behind their directly
@@ -494,7 +505,7 @@ class PARQDecoder(_Tracked, nn.Module):
         return int(_lib.load().parq_mirror_take(C.c_void_p(self._mirror_ptr(slot)))) if self._range_mirror is not None else 0
 
     def _free_slot(self):
-        used = {e.slot for e in self._ws.values()}
+        used = {e.slot for e in self._ws.values()} | set(self._pending)     # (a dropped workspace's forward may still await its check)
         for sl in range(1, self._MIRROR_SLOTS):
             if sl not in used:
                 return sl
@@ -504,12 +515,13 @@ class PARQDecoder(_Tracked, nn.Module):
         """Host loads of the pinned words earlier forwards raise from the device (no synchronisation): bit 0 = an operand left the
         fp16 range (outputs of that forward are NaN), bit 1 = attention mode 'split8' met a row carried by too few keys on the heads of
         bits 8.. (outputs of that forward are NaN from that iteration on unless ``range_check == "off"``), bit 2 = an in-launch hand-off
-        timed out."""
+        timed out.  The word of a forward whose check was deferred (InFlight) belongs to that check: it is left alone."""
         if self._mirror_np is None or not self._mirror_np[:self._MIRROR_SLOTS].any():
             return
         v = 0
         for sl in np.nonzero(self._mirror_np[:self._MIRROR_SLOTS])[0].tolist():
-            v |= self._mirror_take(sl)
+            if sl not in self._pending:
+                v |= self._mirror_take(sl)
         if v == 0 or self.range_check == "off":
             return
         if v & 4:
@@ -519,24 +531,32 @@ class PARQDecoder(_Tracked, nn.Module):
         elif (v & 2) and self.attention_mode == "split8":
             self._peaky_fallback(v >> 8, "detected after an earlier forward, whose outputs are NaN from that iteration on")
 
-    def _range_after_forward(self, entry, sc, dev):
-        """"sync" policy: wait for the forward just enqueued in `entry` and read what it raised; True = re-run it (with the fp32 kernels
-        after a range violation, with the flagged heads on the fp16 x 3 tier after a too-peaked row in mode 'split8', with one launch
-        per stage after a hand-off timeout).  The FIRST inference forward of a module in mode 'split8' (per weight version) is checked
-        this way under every policy but "off" (one synchronisation, once): a model whose attention is too peaked for that mode is peaked
-        from its first call on."""
-        first = self.attention_mode == "split8" and not self._peaky_checked and self.range_check != "off"
-        if not first and (self.range_check != "sync" or self.attention_mode not in ("split", "split8", "fp16")):
+    def _settings(self):
+        """(attention mode, head tiers, seam fusion) as the next forward's _handle() will set them."""
+        return (self.attention_mode, (int(self.safe_heads) if self.num_heads <= 16 else 0, 0 if self.range_check == "off" else 1),
+                bool(self.fuse_seams))
+
+    def _range_after_forward(self, run, sc, dev):
+        """"sync" policy: wait for the forward `run` (a _Run) and read what it raised; True = re-run it (with the fp32 kernels after a
+        range violation, with the flagged heads on the fp16 x 3 tier after a too-peaked row in mode 'split8', with one launch per stage
+        after a hand-off timeout).  The FIRST inference forward of a module in mode 'split8' (per weight version) is checked this way
+        under every policy but "off" (one synchronisation, once): a model whose attention is too peaked for that mode is peaked from its
+        first call on.  What the forward could raise is decided by the settings it was ENQUEUED under: a deferred check (InFlight) may
+        find the module already switched by another forward's check — then the fallback has nothing left to change, and the forward
+        is re-run all the same because it ran under the old settings."""
+        mode, (_, poison), seams = run.settings
+        first = mode == "split8" and not self._peaky_checked and self.range_check != "off"
+        if not first and (self.range_check != "sync" or mode not in ("split", "split8", "fp16")):
             return False
-        want_calm = (self.range_check == "sync" and self.tier_return_after > 0 and self.safe_heads != 0 and self.attention_mode == "split8"
-                     and self.num_heads <= 16)
+        want_calm = (self.range_check == "sync" and self.tier_return_after > 0 and self.safe_heads != 0 and mode == "split8"
+                     and self.attention_mode == "split8" and self.num_heads <= 16)
         if want_calm:
             # also needs every head's smallest row sum of this forward: a device read of the flag words (waits for the stream)
-            flags = self._flag_view(entry.ws, sc.B, sc.V, sc.h, sc.w, 48).tolist()
-            v = self._mirror_take(entry.slot)
+            flags = self._flag_view(run.entry.ws, sc.B, sc.V, sc.h, sc.w, 48).tolist()
+            v = self._mirror_take(run.slot)
         else:
-            self._wait_progress(entry, dev)                   # until this forward can raise no more flags (not: until it has finished)
-            v = self._mirror_take(entry.slot)
+            self._wait_progress(run, dev)                     # until this forward can raise no more flags (not: until it has finished)
+            v = self._mirror_take(run.slot)
             flags = None
         if first:
             self._peaky_checked = True
@@ -544,20 +564,24 @@ class PARQDecoder(_Tracked, nn.Module):
             return False
         if self.range_check == "off":
             return False
-        rerun = False
-        if (v & 4) and self.fuse_seams:                           # a hand-off timed out: re-run with one launch per stage (every policy that looks)
-            self._seam_fallback("re-running this forward")
-            rerun = True
-        if (v & 1) and self.attention_mode in ("split", "split8", "fp16"):
-            if self.range_check == "sync" or first:
+        poisoned = changed = False
+        if (v & 4) and seams:                                     # a hand-off timed out: re-run with one launch per stage (every policy that looks)
+            poisoned = True
+            if self.fuse_seams:
+                self._seam_fallback("re-running this forward")
+                changed = True
+        if (v & 1) and mode in ("split", "split8", "fp16") and (self.range_check == "sync" or first):
+            poisoned = True
+            if self.attention_mode in ("split", "split8", "fp16"):
                 self._range_fallback("re-running this forward")
-                return True
-        if (v & 2) and self.attention_mode == "split8":
-            if self._peaky_fallback(v >> 8, "re-running this forward"):
+                changed = True
+        if (v & 2) and mode == "split8" and poison:
+            poisoned = True
+            if self.attention_mode == "split8" and self._peaky_fallback(v >> 8, "re-running this forward"):
+                changed = True
                 self._peaky_checked = False if first else self._peaky_checked     # the re-run is checked too: other heads may follow
-                return True
-        if rerun:
-            return True
+        if poisoned:
+            return changed or self._settings() != run.settings
         if want_calm:
             # heads on the fp16 x 3 tier whose rows all spread again (flags[32 + h]: the head's smallest row sum of this forward)
             limit = 256.0 * float(self.tier_return_margin)
@@ -573,15 +597,15 @@ class PARQDecoder(_Tracked, nn.Module):
                     self._calm_streak.pop(h)
         return False
 
-    def _wait_progress(self, entry, dev):
+    def _wait_progress(self, run, dev):
         """Spin on the slot's progress word until the device has stored this forward's epoch there (parq_set_progress: the first launch
         behind the last iteration's cross-attention merge does — nothing after it can raise a flag, so the decision "re-run or not" is
         final ~36 us before the outputs are; those stay stream-ordered as always).  A forward that never gets there (or a library
         without the signal) ends the wait through the stream itself."""
-        word, want = self._mirror_np, entry.epoch
-        idx = self._MIRROR_SLOTS + entry.slot
+        word, want = self._mirror_np, run.epoch
+        idx = self._MIRROR_SLOTS + run.slot
         if want:
-            query = entry.stream.query
+            query = run.entry.stream.query
             for spin in range(1 << 30):
                 if word[idx] == want:
                     return
@@ -897,8 +921,9 @@ class PARQDecoder(_Tracked, nn.Module):
         self._order_behind_pack(dev)
         lead = (self.num_layers, sc.B, self.num_queries)
         flat = torch.empty(self.num_layers * sc.B * self.num_queries * self._out_width, dtype=torch.float32, device=dev)
-        entry = self._enqueue_forward(sc, keep, flat, dev)
+        run = self._enqueue_forward(sc, keep, flat, dev)
         self.__dict__["_last_flat"] = flat                     # (InFlight: the one allocation behind the outputs)
+        self.__dict__["_last_settle"] = None
         # (everything below runs while the device works on the forward)
         rows = self.num_layers * sc.B * self.num_queries
         ncls = self.num_semcls + 1
@@ -906,21 +931,48 @@ class PARQDecoder(_Tracked, nn.Module):
         per = [seg.view(*lead, wd).unbind(0) for seg, wd in zip(flat.split([rows * wd for wd in widths]), widths)]
         result = [dict(zip(OUTPUT_KEYS, [p[i] for p in per])) for i in range(self.num_layers)]
 
+        pending = []
+
         def settle():
             """What policy "sync" owes the caller (and every policy owes a module's first forward): wait, look, and re-run — with the
             exact fp32 kernels (range), or with the flagged heads on the fp16 x 3 tier (each re-run can only add heads: at most
-            num_heads of them) — into the SAME output tensors."""
-            e = entry
-            for _attempt in range(self.num_heads + 2):
-                if not self._range_after_forward(e, sc, dev):
-                    break
-                e = self._enqueue_forward(sc, keep, flat, dev)
+            num_heads of them) — into the SAME output tensors.  Runs once; a second call returns at once."""
+            nonlocal run
+            if run is None:
+                return result
+            try:
+                for _attempt in range(self.num_heads + 2):
+                    if not self._range_after_forward(run, sc, dev):
+                        break
+                    run = self._enqueue_forward(sc, keep, flat, dev)
+            finally:
+                run = None
+                for sl in pending:
+                    n = self._pending.get(sl, 0) - 1
+                    if n > 0:
+                        self._pending[sl] = n
+                    else:
+                        self._pending.pop(sl, None)
             return result
 
         if self._defer is not None and self.range_check == "sync" and self.attention_mode in ("split", "split8", "fp16"):
-            self._defer.append(settle)         # InFlight.submit: the wait belongs to Ticket.result(), other forwards keep the device busy
+            # InFlight.submit: the wait belongs to Ticket.result(), other forwards keep the device busy.  Until then this forward's
+            # mirror slot is its own: _range_poll leaves the word alone and no new workspace is given the slot.
+            pending.append(run.slot)
+            self._pending[run.slot] = self._pending.get(run.slot, 0) + 1
+            self._defer.append(settle)
+            self.__dict__["_last_settle"] = settle
             return result
         return settle()
+
+    def settle_deferred(self):
+        """Inside an ``InFlight.submit`` of a module that wraps this decoder: run the range check the decoder's last call handed to the
+        ticket NOW (wait for that forward, re-run it if the device flagged it), before the wrapper reads the outputs on the host — its
+        set loss does.  Returns at once when nothing is deferred."""
+        fn = self.__dict__.get("_last_settle")
+        if fn is not None:
+            self.__dict__["_last_settle"] = None
+            fn()
 
     def _out_pointers(self, base, rows):
         """parq_outputs over one flat allocation at device address `base`: the six tensors back to back, `rows` rows each."""
@@ -934,14 +986,15 @@ class PARQDecoder(_Tracked, nn.Module):
     def _enqueue_forward(self, sc, keep, flat, dev):
         """One inference forward into `flat` (the six output tensors back to back).  From the second forward of a (workspace, weights,
         attention settings) on, the iterations are replayed from a captured graph behind the directly launched prologue and K/V
-        projection (parq_forward_replay); launch by launch otherwise (parq_forward).  Returns the workspace entry."""
+        projection (parq_forward_replay); launch by launch otherwise (parq_forward).  Returns its _Run."""
         lib = _lib.load()
         h = self._handle()
         entry = self._workspace_entry(sc.B, sc.V, sc.h, sc.w, dev, handle=h)
         ws = entry.ws
         self._set_mirror(entry.slot)
         self._epoch = (self._epoch % 0x7ffffff0) + 1
-        entry.epoch = self._epoch
+        entry.epoch = self._epoch                           # (the device stores it into the slot's progress word)
+        run = _Run(entry, entry.slot, self._epoch, (self._mode_set, self._tiers_set, self._seams_set))
         _lib.check(lib.parq_set_progress(h, C.c_void_p(self._progress_ptr(entry.slot)), self._epoch), "parq_set_progress")
         stream = C.c_void_p(entry.stream.cuda_stream)
         po = self._out_pointers(flat.data_ptr(), self.num_layers * sc.B * self.num_queries)
@@ -958,7 +1011,7 @@ class PARQDecoder(_Tracked, nn.Module):
         else:
             _lib.check(lib.parq_forward(h, C.byref(sc), _lib.ptr(ws), ws.numel() * 4, C.byref(po), stream), "parq_forward")
         self._mark_first_forward(dev)
-        return entry
+        return run
 
     def _capture(self, entry, key, sc, stream):
         """Record the iterations of this workspace's forward into a HIP graph (parq_forward_capture); graphs of earlier weights / settings

@@ -62,7 +62,7 @@ class Ticket:
     def done(self):
         return self._ev.query()
 
-    def result(self):
+    def _settle_now(self):
         if self._settle:
             with torch.cuda.stream(self._stream):
                 for fn in self._settle:         # host wait + the pinned word of this forward's workspace; a flagged forward is re-run
@@ -70,6 +70,9 @@ class Ticket:
                 self._settle = []
                 self._ev = torch.cuda.Event()
                 self._ev.record(self._stream)
+
+    def result(self):
+        self._settle_now()
         cur = torch.cuda.current_stream(self._stream.device)
         cur.wait_event(self._ev)
         for t in (self._storages if self._storages is not None else _storages(self._out)):
@@ -102,6 +105,7 @@ class InFlight:
             device = p.device if p is not None and p.is_cuda else torch.device("cuda", torch.cuda.current_device())
         self.module, self.device = module, torch.device(device)
         self._streams = [torch.cuda.Stream(self.device) for _ in range(depth)]
+        self._unsettled = [None] * depth          # per stream: the last ticket submitted there, while its check may still be deferred
         self._next = 0
         self._decs = _decoders(module)
         for dec in self._decs:                   # one workspace per stream stays cached (PARQDecoder)
@@ -113,9 +117,17 @@ class InFlight:
 
     def submit(self, *args, **kwargs):
         """Enqueue ``module(*args, **kwargs)`` on the next stream, behind whatever the caller's current stream has enqueued so far
-        (the producers of the arguments).  Returns a Ticket."""
-        side = self._streams[self._next]
-        self._next = (self._next + 1) % len(self._streams)
+        (the producers of the arguments).  Returns a Ticket.
+
+        A stream's workspace holds at most one forward whose check is still deferred: with more than ``depth`` tickets outstanding,
+        this call first settles the ticket it submitted ``depth`` calls ago (a host wait for that forward, the others keep the device
+        busy).  A caller that takes each result before it submits again never waits here."""
+        i = self._next
+        side = self._streams[i]
+        self._next = (i + 1) % len(self._streams)
+        prev, self._unsettled[i] = self._unsettled[i], None
+        if prev is not None:
+            prev._settle_now()
         cur = torch.cuda.current_stream(self.device)
         side.wait_stream(cur)
         for t in _storages((args, kwargs)):      # the arguments were allocated on the caller's stream and are read on `side`
@@ -134,10 +146,17 @@ class InFlight:
             for d in decs:
                 d.__dict__["_defer"] = None
         # the decoder's 48 output tensors are views of one allocation: hand the ticket that allocation instead of letting it walk them
-        flats = [d.__dict__.get("_last_flat") for d in decs]
-        own = [f for f in flats if f is not None] if (decs and (self.module is decs[0] or getattr(self.module, "box3d_decoder", None) is decs[0])) else None
-        return Ticket(out, ev, side, settle, own or None)
+        # (a wrapper returns more than the decoder's outputs: its ticket walks them all)
+        flat = decs[0].__dict__.get("_last_flat") if decs and self.module is decs[0] else None
+        ticket = Ticket(out, ev, side, settle, [flat] if flat is not None else None)
+        if settle:
+            self._unsettled[i] = ticket
+        return ticket
 
     def drain(self):
+        for i, t in enumerate(self._unsettled):
+            if t is not None:
+                self._unsettled[i] = None
+                t._settle_now()
         for s in self._streams:
             s.synchronize()

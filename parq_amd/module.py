@@ -60,6 +60,7 @@ class PARQ(_Base):
                                      batch["T_world_pseudoCam"], batch["T_world_local"],
                                      feat_hw=tuple(feats.shape[-2:]))
         if "obbs_padded" in batch:
+            self.box3d_decoder.settle_deferred()        # (InFlight) the loss reads the outputs on the host: a flagged forward is re-run first
             losses = self.box3d_decoder.loss(outputs, batch["obbs_padded"], batch["T_world_local"], batch["sym"])
         else:
             losses = {"total_loss": 0}
