@@ -58,7 +58,7 @@ typedef struct parq_config {
 /* Inputs of one PARQDecoder.forward call (model/parq_decoder.py:134). */
 typedef struct parq_scene {
     int32_t B, V, h, w;              /* scenes, views, feature-map height/width           */
-    const float *tokens;             /* (B, V*h*w, C)                                     */
+    const float *tokens;             /* (B, V*h*w, C); fp16 / bf16 elements after parq_set_token_type */
     const float *camera;             /* (B, V, 6)  feature-scale cameras                  */
     const float *T_camera_pseudoCam; /* (B, V, 12)                                        */
     const float *T_world_pseudoCam;  /* (B, V, 12)                                        */
@@ -139,6 +139,18 @@ int parq_pack_weights(parq_handle h, void *arena, size_t arena_bytes, parq_strea
  *      row sum seen as 0x7fffffff - its float bits) — and bits 1 and 8 + h of the range mirror — when a row of head h has a sum
  *      under 256; what happens then is the caller's policy, see parq_set_head_tiers. */
 int parq_set_attention_mode(parq_handle h, int32_t mode);
+
+/* Element type of the memory tokens (call before sizing the workspace): after the call the `tokens` pointer of every parq_scene passed
+ * to this handle — parq_forward, parq_forward_replay, parq_prepare, parq_iterate — is read as (B, V*h*w, C) elements of that type.
+ * A 16-bit token widens to fp32 exactly, and the kernels widen each row in registers as they read it and run the fp32-token arithmetic
+ * from there: the outputs are bit-identical to a call on the fp32 copy of the same tokens, in every attention mode, while the K/V
+ * projection and project + sample read half the bytes and no fp32 copy exists (attention mode 0, and head dims without the split
+ * cache, widen into the workspace instead: it grows by B*N*C floats there).  The range check of modes 1 and 2 sees the same values.
+ * parq_forward_capture records the type; parq_forward_replay refuses (PARQ_ERR_STATE) a graph recorded under another one.
+ * Training (parq_forward_train, parq_backward) and parq_iterate_sharded read fp32 tokens only and return PARQ_ERR_ARG otherwise.
+ * Default PARQ_TOKENS_F32; an unknown type is PARQ_ERR_ARG. */
+enum { PARQ_TOKENS_F32 = 0, PARQ_TOKENS_F16 = 1, PARQ_TOKENS_BF16 = 2 };
+int parq_set_token_type(parq_handle h, int32_t type);
 /* Per-head tiers of attention mode 4 (inference; head dim 64, dim 256, at most 16 heads).  Bit h of `safe_mask` moves head h to the
  * fp16 x 3 arithmetic of mode 1 INSIDE a mode-4 forward: the K/V projection writes that head's cache region in the split layout, the
  * cross-attention of an iteration runs as two launches over complementary head sets (flash_split8_kernel over the others,
@@ -340,7 +352,10 @@ int parq_set_backward_streams(parq_handle h, int32_t n);
  * intermediate).  Requires (3*num_samples) % 64 == 0 and C % 64 == 0 (shipped: 64 samples, C = 1024 or 256). */
 /* PARQ_RAYPE_WEIGHTS_CACHED: the workspace is the one the previous call used (same flags otherwise, same C and num_samples) and
  * w1 / w2 have not changed since: their hi/lo split and fragment-ordered copies inside it are reused (three small launches less). */
-enum { PARQ_RAYPE_NCHW_OUT = 1, PARQ_RAYPE_NO_HIDDEN = 2, PARQ_RAYPE_WEIGHTS_CACHED = 4 };
+/* PARQ_RAYPE_OUT_F16 / PARQ_RAYPE_OUT_BF16 (inference, with PARQ_RAYPE_NO_HIDDEN, channels-last only): tokens_out receives fp16 / bf16
+ * elements, each the fp32 result rounded to nearest even (as torch.Tensor.to: NaN stays NaN) — the tokens parq_set_token_type lets the
+ * decoder read as they are.  Equal to the fp32 output converted afterwards; the workspace is the same. */
+enum { PARQ_RAYPE_NCHW_OUT = 1, PARQ_RAYPE_NO_HIDDEN = 2, PARQ_RAYPE_WEIGHTS_CACHED = 4, PARQ_RAYPE_OUT_F16 = 8, PARQ_RAYPE_OUT_BF16 = 16 };
 size_t parq_ray_pe_workspace_bytes(int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C, int32_t num_samples);   /* flags = 0 */
 size_t parq_ray_pe_workspace_bytes_flags(int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C, int32_t num_samples,
                                          int32_t flags);

@@ -65,6 +65,7 @@ SYMBOLS = {
     "parq_iterate": (C.c_int, [_vp, C.POINTER(ParqScene), _vp, _sz, _i32, _vp, C.POINTER(ParqOutputs), _vp, _vp]),
     "parq_workspace_lookup": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.c_char_p, C.POINTER(_sz), C.POINTER(_sz)]),
     "parq_set_attention_mode": (C.c_int, [_vp, _i32]),
+    "parq_set_token_type": (C.c_int, [_vp, _i32]),
     "parq_set_head_tiers": (C.c_int, [_vp, C.c_uint32, _i32]),
     "parq_set_seam_fusion": (C.c_int, [_vp, _i32]),
     "parq_set_range_mirror": (C.c_int, [_vp, _vp]),
@@ -161,6 +162,13 @@ def ptr(t):
         return None
     assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), \
         "expected a contiguous float32 CUDA tensor, got %s %s contiguous=%s" % (t.device, t.dtype, t.is_contiguous())
+    return C.c_void_p(t.data_ptr())
+
+
+def token_ptr(t):
+    """Device pointer of the tokens of a scene: a contiguous CUDA tensor of float32, float16 or bfloat16 (parq_set_token_type)."""
+    assert t.is_cuda and t.dtype in (torch.float32, torch.float16, torch.bfloat16) and t.is_contiguous(), \
+        "expected contiguous float32 / float16 / bfloat16 CUDA tokens, got %s %s contiguous=%s" % (t.device, t.dtype, t.is_contiguous())
     return C.c_void_p(t.data_ptr())
 
 

@@ -79,6 +79,7 @@ struct Workspace {
     int64_t kvc, flags;               // split-fp16 K/V cache, int flags (overflow)
     int64_t seam_flags, lnp1;         // the norm1 seam inside one launch (chain.hip seam_tile): flags [M / 16][4], fp64 partial row sums of xa ([M][C/64][2])
     int64_t xsplit;                   // fp16 hi/lo copy of the tokens for the large-C K/V projection (kvproj_big.hip), else empty
+    int64_t tok32;                    // attention mode 0 with 16-bit tokens: their exact fp32 widening, read by the fp32 K/V projection; else empty
     int64_t cam, ind;                 // a captured forward: this call's cameras and pointer block (common.hpp CallPtrs), left by its prologue
     int64_t total;
     int self_split, cross_split;
@@ -113,6 +114,7 @@ struct parq_ctx {
     int ref_state = 0;                // 0: none, 1: ws.ref valid
     int attn_mode = 1;                // 0: fp32 MFMA, 1: split fp16x3, 2: fp16, 3: bf16 (1..3: head dims 64 and 256), 4: split with fp8 cross terms
     int kv16_state = 1;               // what the arena's 16-bit W_kv copy currently holds (same numbering)
+    int tok_type = 0;                 // parq_set_token_type: element type of every scene's tokens (kTokF32 / kTokF16 / kTokBF16)
     float drop_p = 0.f;               // training dropout (decoder layer, transformer_parq.py:339-386) and its base seed
     uint32_t drop_seed = 0;
     uint32_t site_seed(int k, int site) const { return rng_stream(drop_seed, (uint32_t)(k * 8 + site)); }
@@ -274,6 +276,7 @@ int carve_workspace(const parq_ctx* c, int B, int V, int h, int w, Workspace* ws
     ws->seam_flags = take((M / 16 + 1) * 4);         // directly behind `flags`: the forward prologue clears both in one go
     ws->lnp1 = take(M * (C / 64) * 4);
     ws->xsplit = take(split_mode && kvproj_big_on() ? (int64_t)kvproj_big_scratch_floats(B, (int)N, C) : 0);
+    ws->tok32 = take(!split_mode && c->tok_type != kTokF32 ? (int64_t)B * N * C : 0);
     const size_t fs = flash_scratch_bytes(B, c->H, c->Q, c->dh, ws->self_split);
     size_t fc = flash_scratch_bytes(B, c->H, c->Q, c->dh, ws->cross_split);
     if (c->attn_mode == 4 && c->dh == 64 && c->H <= 16) {
@@ -430,14 +433,20 @@ int do_prepare(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
             char* cache = reinterpret_cast<char*>(wsp + ws.kvc) + (size_t)li * kvsplit_cache_bytes(B, c->vheads(), (int)N, c->terms());
             if (kvproj_big_on() && kvproj_big_scratch_floats(B, (int)N, C) > 0)
                 HIPCHK(launch_kvproj_big(sc->tokens, A + L.kv_whi, A + L.kv_wlo, A + L.cross_in_b + C, B, (int)N, C, cache,
-                                         reinterpret_cast<int*>(wsp + ws.flags), wsp + ws.xsplit, s, c->terms(), c->kind()));
+                                         reinterpret_cast<int*>(wsp + ws.flags), wsp + ws.xsplit, s, c->terms(), c->kind(), c->tok_type));
             else
                 HIPCHK(launch_kvproj_split(sc->tokens, A + L.kv_whi, A + L.kv_wlo, A + L.cross_in_b + C, B, (int)N, C, c->vheads(),
                                            cache, reinterpret_cast<int*>(wsp + ws.flags), s,
                                            c->mixed_tiers(N, train, train && bwd_reads_cache(c, ws)) ? 11 : c->terms_for(N, train, train && bwd_reads_cache(c, ws)),
-                                           c->kind(), c->safe_heads()));
+                                           c->kind(), c->safe_heads(), c->tok_type));
         } else {
-            LinearArgs a = lin(sc->tokens, C, A + L.cross_in_w + (int64_t)C * C, C, A + L.cross_in_b + C,
+            // 16-bit tokens: the fp32 GEMM reads their exact widening (once per forward, in front of the first layer)
+            const float* X = sc->tokens;
+            if (c->tok_type != kTokF32) {
+                if (li == 0) HIPCHK(launch_widen_tokens(sc->tokens, wsp + ws.tok32, (int64_t)B * N * C, c->tok_type, s));
+                X = wsp + ws.tok32;
+            }
+            LinearArgs a = lin(X, C, A + L.cross_in_w + (int64_t)C * C, C, A + L.cross_in_b + C,
                                wsp + ws.kv + (int64_t)li * B * 2 * N * C, 0, (int)(B * N), 2 * C, C);
             a.rows_per_batch = (int)N; a.y_batch = 2 * N * C; a.y_row = c->dh; a.col_blk = c->dh; a.y_blk = N * c->dh;
             HIPCHK(launch_linear(a, 1, s));
@@ -594,7 +603,8 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
     bool fused = false;
     if (!train && !fuse_off && !c->profiling) {
         const hipError_t e = launch_pe1_sample(pe1, sc->tokens, reinterpret_cast<const double*>(wsp + ws.T_cl), cam_in, ref, c->sb, B, sc->V,
-                                               sc->h, sc->w, C, Q, sample_out, o->coord_pos, gn1, B * 8 * kGnSlots, sample_cnt, s, ind, row0 * 3);
+                                               sc->h, sc->w, C, Q, sample_out, o->coord_pos, gn1, B * 8 * kGnSlots, sample_cnt, s, ind, row0 * 3,
+                                               c->tok_type);
         if (e == hipSuccess) fused = true;
         else if (e != hipErrorNotSupported) return fail(PARQ_ERR_HIP, "launch_pe1_sample failed: %s", hipGetErrorString(e));
     }
@@ -611,7 +621,8 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
     if (!fused) {
         Prof p(c, s, PARQ_PROF_PROJECT_SAMPLE);
         HIPCHK(launch_project_sample_f64(sc->tokens, reinterpret_cast<const double*>(wsp + ws.T_cl), cam_in, ref, c->sb,
-                                         B, sc->V, sc->h, sc->w, C, Q, sample_out, o->coord_pos, gn1, B * 8 * kGnSlots, s, sample_cnt, ind, row0 * 3));
+                                         B, sc->V, sc->h, sc->w, C, Q, sample_out, o->coord_pos, gn1, B * 8 * kGnSlots, s, sample_cnt, ind, row0 * 3,
+                                         c->tok_type));
     }
     // view-sharded: this rank's fp16-range flag travels as the last float of the record (the caller's all-reduce adds the ranks')
     if (sharded) HIPCHK(launch_shard_range_flag(c->cache_mode() && c->kind() == kF16 ? reinterpret_cast<const int*>(wsp + ws.flags) : nullptr,
@@ -1363,6 +1374,7 @@ int parq_iterate_sharded(parq_handle h, const parq_scene* scene, void* workspace
                          int32_t phase, const float* ref_in, const parq_outputs* outs, float* ref_out, const float* xchg_in,
                          float* xchg_out, int32_t nranks, parq_stream stream) {
     if (!h || !workspace) return fail(PARQ_ERR_ARG, "NULL argument");
+    if (h->tok_type != kTokF32) return fail(PARQ_ERR_ARG, "parq_iterate_sharded reads fp32 tokens only: set token type 0");
     if (!h->packed || !h->prepared) return fail(PARQ_ERR_STATE, "parq_prepare must be called first");
     int rc = check_scene(h, scene);
     if (rc) return rc;
@@ -1443,16 +1455,17 @@ int parq_forward(parq_handle h, const parq_scene* scene, void* workspace, size_t
 /* ---- a captured forward (include/parq_hip.h) ---------------------------------------------------------------------------------- */
 // what a graph was recorded with: parq_forward_replay refuses a graph whose recording no longer matches the handle or the call
 struct GraphKey {
-    int B, V, h, w, mode, seam, poison;
+    int B, V, h, w, mode, seam, poison, tok;
     uint32_t safe;
     const void* ws; const void* arena; const void* mirror; const void* progress;
     bool operator==(const GraphKey& o) const {
-        return B == o.B && V == o.V && h == o.h && w == o.w && mode == o.mode && seam == o.seam && poison == o.poison && safe == o.safe &&
+        return B == o.B && V == o.V && h == o.h && w == o.w && mode == o.mode && seam == o.seam && poison == o.poison && tok == o.tok && safe == o.safe &&
                ws == o.ws && arena == o.arena && mirror == o.mirror && progress == o.progress;
     }
 };
 static GraphKey graph_key(const parq_ctx* c, int B, int V, int hh, int ww, const void* wsp) {
-    return GraphKey{B, V, hh, ww, c->attn_mode, c->seam_fusion ? 1 : 0, c->peaky_poison, c->safe_heads(), wsp, c->arena, c->range_mirror, c->progress_word};
+    return GraphKey{B, V, hh, ww, c->attn_mode, c->seam_fusion ? 1 : 0, c->peaky_poison, c->tok_type, c->safe_heads(), wsp, c->arena, c->range_mirror,
+                    c->progress_word};
 }
 struct parq_graph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; size_t nodes = 0; GraphKey key; };
 
@@ -1510,7 +1523,7 @@ int parq_forward_replay(parq_handle h, parq_graph_t g, const parq_scene* scene, 
     if (rc) return rc;
     if (!(g->key == graph_key(h, scene->B, scene->V, scene->h, scene->w, workspace)) || !h->derived_valid)
         return fail(PARQ_ERR_STATE, "parq_forward_replay: the graph was recorded for another shape / workspace / weight arena / range mirror or under "
-                                    "other attention settings (mode, head tiers, seam fusion): capture again");
+                                    "other attention settings (mode, head tiers, seam fusion) or token type: capture again");
     hipStream_t s = (hipStream_t)stream;
     // launched directly with THIS call's pointers: prologue (which also leaves them in the workspace for the recorded part) + K/V projection
     rc = do_prepare(h, scene, (float*)workspace, ws, s, false, outs, true);
@@ -1573,6 +1586,14 @@ int parq_set_attention_mode(parq_handle h, int32_t mode) {
     return PARQ_OK;
 }
 
+int parq_set_token_type(parq_handle h, int32_t type) {
+    if (!h) return fail(PARQ_ERR_ARG, "NULL handle");
+    if (type != kTokF32 && type != kTokF16 && type != kTokBF16) return fail(PARQ_ERR_ARG, "token type must be 0 (fp32), 1 (fp16) or 2 (bf16), not %d", type);
+    if (type != h->tok_type) h->prepared = false;     // a prepared scene's tokens were read as the previous type
+    h->tok_type = type;
+    return PARQ_OK;
+}
+
 int parq_set_head_tiers(parq_handle h, uint32_t safe_mask, int32_t poison_on_peaked) {
     if (!h) return fail(PARQ_ERR_ARG, "NULL handle");
     if (safe_mask != 0 && h->H > 16) return fail(PARQ_ERR_ARG, "per-head tiers need at most 16 heads");
@@ -1623,6 +1644,7 @@ size_t parq_grad_arena_bytes(parq_handle h) { return h ? (size_t)h->ar.rowmajor_
 int parq_forward_train(parq_handle h, const parq_scene* scene, void* workspace, size_t workspace_bytes, const parq_outputs* outs,
                        parq_stream stream) {
     if (!h || !workspace) return fail(PARQ_ERR_ARG, "NULL argument");
+    if (h->tok_type != kTokF32) return fail(PARQ_ERR_ARG, "parq_forward_train reads fp32 tokens only: set token type 0");
     if (!h->packed) return fail(PARQ_ERR_STATE, "parq_pack_weights must be called first");
     if (h->dh % 16 != 0) return fail(PARQ_ERR_ARG, "training needs a head dim that is a multiple of 16");
     int rc = check_scene(h, scene);
@@ -1689,6 +1711,7 @@ int parq_wait_iteration(parq_handle h, int32_t k) {
 int parq_backward(parq_handle h, const parq_scene* scene, void* workspace, size_t workspace_bytes, const parq_outputs* outs,
                   const parq_output_grads* g, float* grad_arena, float* d_tokens, parq_stream stream) {
     if (!h || !workspace || !outs || !g || !grad_arena) return fail(PARQ_ERR_ARG, "NULL argument");
+    if (h->tok_type != kTokF32) return fail(PARQ_ERR_ARG, "parq_backward reads fp32 tokens only: set token type 0");
     if (!h->packed) return fail(PARQ_ERR_STATE, "parq_pack_weights must be called first");
     int rc = check_scene(h, scene);
     if (rc) return rc;
@@ -2118,6 +2141,11 @@ int parq_ray_pe(const float* camera, const float* T_cp, const float* T_wp, const
                 const float* features_nchw, float* tokens_out, int32_t flags, void* workspace, size_t workspace_bytes,
                 parq_stream stream) {
     const int32_t nchw_out = flags & PARQ_RAYPE_NCHW_OUT;
+    // 16-bit token rows (inference: the hidden layer is not kept for a backward; channels-last)
+    const int out16 = (flags & PARQ_RAYPE_OUT_F16) ? kTokF16 : (flags & PARQ_RAYPE_OUT_BF16) ? kTokBF16 : kTokF32;
+    if ((flags & PARQ_RAYPE_OUT_F16) && (flags & PARQ_RAYPE_OUT_BF16)) return fail(PARQ_ERR_ARG, "ray-PE: one 16-bit output type at a time");
+    if (out16 != kTokF32 && (nchw_out || !(flags & PARQ_RAYPE_NO_HIDDEN)))
+        return fail(PARQ_ERR_ARG, "ray-PE: 16-bit tokens are an inference output (no-hidden flag, channels-last)");
     if (!camera || !T_cp || !T_wp || !T_wl || !w1 || !b1 || !w2 || !b2 || !scale6_host || !tokens_out || !workspace)
         return fail(PARQ_ERR_ARG, "NULL argument");
     if (B < 1 || V < 1 || hh < 1 || ww < 1 || num_samples < 1) return fail(PARQ_ERR_ARG, "bad dims");
@@ -2149,13 +2177,13 @@ int parq_ray_pe(const float* camera, const float* T_cp, const float* T_wp, const
         if (two && !Hd) return fail(PARQ_ERR_ARG, "the two-kernel form needs the hidden region (do not pass the no-hidden flag)");
         HIPCHK(launch_raype_fused(camera, T_cp, T_wp, T_wl, scale6_host, min_depth, max_depth, B, V, hh, ww, w1hi, w1lo, b1,
                                   w2hi, w2lo, b2, features_nchw, Hd, tabs, tabs + (int64_t)B * V * 12, tokens_out,
-                                  nchw_out ? 1 : 0, s, W2f, two | (cached ? 2 : 0)));
+                                  nchw_out ? 1 : 0, s, W2f, two | (cached ? 2 : 0), out16));
         return PARQ_OK;
     }
     if (nchw_out) return fail(PARQ_ERR_ARG, "NCHW output needs the fused path (C = 256, 64 samples)");
     HIPCHK(launch_raype_points(camera, T_cp, T_wp, T_wl, scale6_host, min_depth, max_depth, B, V, hh, ww, num_samples, P, s));
     HIPCHK(launch_gemm_split(P, K1, w1hi, w1lo, b1, Hd, C, M, C, K1, 1, nullptr, 1, s));
-    HIPCHK(launch_gemm_split(Hd, C, w2hi, w2lo, b2, tokens_out, C, M, C, C, 0, features_nchw, hh * ww, s));
+    HIPCHK(launch_gemm_split(Hd, C, w2hi, w2lo, b2, tokens_out, C, M, C, C, 0, features_nchw, hh * ww, s, nullptr, 1.f, nullptr, 0, out16));
     return PARQ_OK;
 }
 

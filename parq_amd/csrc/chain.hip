@@ -294,11 +294,11 @@ __global__ __launch_bounds__(NWV * 64) void chain_linear_kernel(LinearArgs a) {
 // workgroups [n_lin, n_lin + B*Q) project and sample one (scene, query) each (sample_body.hpp).  Saves one dependent launch
 // (1.9 us boundary + ramp) per iteration; the two bodies run side by side on different CUs.
 struct SampleArgs {
-    const float* tokens; const double* T_cl; const float* cam; const float* ref; ScaleBox sb; int V, h, w, C, Q;
+    const void* tokens; const double* T_cl; const float* cam; const float* ref; ScaleBox sb; int V, h, w, C, Q;
     float* tgt; float* coord_pos; double* zero_f64; int zero_n; float* raw_count;
     const void* const* ind; int64_t coord_off;     // optional CallPtrs block of a captured forward: tokens = ind[0], coord_pos = ind[6] + coord_off
 };
-template <int NCH>
+template <int NCH, int TT = kTokF32>
 __global__ __launch_bounds__(1024) void pe1_sample_kernel(LinearArgs a, SampleArgs sa, int n_lin) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if ((int)blockIdx.x < n_lin) {
@@ -308,10 +308,10 @@ __global__ __launch_bounds__(1024) void pe1_sample_kernel(LinearArgs a, SampleAr
     } else {
         PARQ_TL_KERNEL(kTlProjectSample);
         if (sa.ind != nullptr) {
-            sa.tokens = reinterpret_cast<const float*>(sa.ind[0]);
+            sa.tokens = sa.ind[0];
             sa.coord_pos = reinterpret_cast<float*>(const_cast<void*>(sa.ind[6])) + sa.coord_off;
         }
-        project_sample_body<NCH, double>(sa.tokens, sa.T_cl, sa.cam, sa.ref, sa.sb, sa.V, sa.h, sa.w, sa.C, sa.Q, sa.tgt, sa.coord_pos,
+        project_sample_body<NCH, double, TT>(sa.tokens, sa.T_cl, sa.cam, sa.ref, sa.sb, sa.V, sa.h, sa.w, sa.C, sa.Q, sa.tgt, sa.coord_pos,
                                          sa.zero_f64, sa.zero_n, sa.raw_count, (int)blockIdx.x - n_lin, (int)gridDim.x - n_lin, smem);
     }
 }
@@ -1682,9 +1682,20 @@ hipError_t launch_fold_pos_weights(const float* Wa, const float* ba, const float
 
 // fused first launch of an iteration: pe1 (args `a`: K = 384, ReLU, bias) + project/sample.  hipErrorNotSupported when the shapes
 // do not fit (the caller then launches the two stages separately).
-hipError_t launch_pe1_sample(const LinearArgs& a_in, const float* tokens, const double* T_cl, const float* cam, const float* ref, ScaleBox sb,
+template <int TT>
+static void launch_pe1_sample_t(int nch, dim3 grid, dim3 block, size_t smem, hipStream_t s, const LinearArgs& a, const SampleArgs& sa, int n_lin) {
+    switch (nch) {
+        case 1: hipLaunchKernelGGL((pe1_sample_kernel<1, TT>), grid, block, smem, s, a, sa, n_lin); break;
+        case 2: hipLaunchKernelGGL((pe1_sample_kernel<2, TT>), grid, block, smem, s, a, sa, n_lin); break;
+        case 3: hipLaunchKernelGGL((pe1_sample_kernel<3, TT>), grid, block, smem, s, a, sa, n_lin); break;
+        default: hipLaunchKernelGGL((pe1_sample_kernel<4, TT>), grid, block, smem, s, a, sa, n_lin); break;
+    }
+}
+
+hipError_t launch_pe1_sample(const LinearArgs& a_in, const void* tokens, const double* T_cl, const float* cam, const float* ref, ScaleBox sb,
                              int B, int V, int h, int w, int C, int Q, float* tgt, float* coord_pos, double* zero_f64, int zero_n,
-                             float* raw_count, hipStream_t s, const void* const* ind, int64_t coord_off) {
+                             float* raw_count, hipStream_t s, const void* const* ind, int64_t coord_off, int tok_type) {
+    if (tok_type != kTokF32 && tok_type != kTokF16 && tok_type != kTokBF16) return hipErrorInvalidValue;
     if (!chain_linear_supported(a_in, 1)) return hipErrorNotSupported;
     const Sig g = sig_of(a_in);
     if (!(g.K == 384 && g.pro == kProNone && g.add2 == 0 && g.bias && g.relu && g.res == kResNone && !g.gnout)) return hipErrorNotSupported;
@@ -1698,12 +1709,10 @@ hipError_t launch_pe1_sample(const LinearArgs& a_in, const float* tokens, const 
     const size_t smem = (size_t)nwv * C * sizeof(float) + (size_t)nwv * sizeof(int) + (size_t)V * 32 + 16;
     SampleArgs sa{tokens, T_cl, cam, ref, sb, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, raw_count, ind, coord_off};
     const dim3 grid((unsigned)(n_lin + B * Q)), block(nwv * 64);
-    switch ((C / 4 + 63) / 64) {
-        case 1: hipLaunchKernelGGL((pe1_sample_kernel<1>), grid, block, smem, s, a, sa, n_lin); break;
-        case 2: hipLaunchKernelGGL((pe1_sample_kernel<2>), grid, block, smem, s, a, sa, n_lin); break;
-        case 3: hipLaunchKernelGGL((pe1_sample_kernel<3>), grid, block, smem, s, a, sa, n_lin); break;
-        default: hipLaunchKernelGGL((pe1_sample_kernel<4>), grid, block, smem, s, a, sa, n_lin); break;
-    }
+    const int nch = (C / 4 + 63) / 64;
+    if (tok_type == kTokF16) launch_pe1_sample_t<kTokF16>(nch, grid, block, smem, s, a, sa, n_lin);
+    else if (tok_type == kTokBF16) launch_pe1_sample_t<kTokBF16>(nch, grid, block, smem, s, a, sa, n_lin);
+    else launch_pe1_sample_t<kTokF32>(nch, grid, block, smem, s, a, sa, n_lin);
     return hipGetLastError();
 }
 

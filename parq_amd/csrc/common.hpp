@@ -285,6 +285,69 @@ __device__ __forceinline__ half8 cvt8_rn(const float* x) {
     }
 }
 
+// ---- element type of the memory tokens (parq_set_token_type): fp32, or 16-bit rows widened to fp32 in registers.  Both 16-bit
+// formats are subsets of fp32, so the widening is exact (NaN and infinities included) and everything after it is the fp32-token
+// kernel's arithmetic unchanged.
+enum : int { kTokF32 = 0, kTokF16 = 1, kTokBF16 = 2 };
+template <int TT> struct TokElem { typedef float type; };
+template <> struct TokElem<kTokF16> { typedef _Float16 type; };
+template <> struct TokElem<kTokBF16> { typedef unsigned short type; };       // raw bf16 bits
+template <int TT> constexpr int tok_bytes() { return TT == kTokF32 ? 4 : 2; }
+
+__device__ __forceinline__ float bf16_bits_to_f32(unsigned int b) { return __builtin_bit_cast(float, b << 16); }
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+// two fp32 -> two 16-bit tokens of type TT (kTokF16 / kTokBF16) packed low | high, each rounded to nearest even as torch.Tensor.to
+// does, NaN stays NaN: the packed conversions v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32.  fp16 goes through inline asm because a lone
+// (_Float16) cast compiles to v_cvt_f16_f32, which on gfx950 rounds some exact ties the other way (see split_pair above).
+template <int TT>
+__device__ __forceinline__ unsigned int round2_tok16(float y0, float y1) {
+    static_assert(TT != kTokF32, "16-bit token types only");
+    if constexpr (TT == kTokF16) {
+        unsigned int r;
+        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(y0), "v"(y1));
+        return r;
+    } else {
+        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+        const bf16x2 v = {(__bf16)y0, (__bf16)y1};
+        return __builtin_bit_cast(unsigned int, v);
+    }
+}
+// 8 consecutive 16-bit tokens (one 16-byte piece) -> fp32
+template <int TT>
+__device__ __forceinline__ void widen8(u32x4 raw, float* x) {
+    static_assert(TT != kTokF32, "16-bit token types only");
+    const unsigned int w[4] = {raw[0], raw[1], raw[2], raw[3]};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if constexpr (TT == kTokF16) {
+            const half2v h = __builtin_bit_cast(half2v, w[i]);
+            x[2 * i] = (float)h[0];
+            x[2 * i + 1] = (float)h[1];
+        } else {
+            x[2 * i] = bf16_bits_to_f32(w[i] & 0xffffu);
+            x[2 * i + 1] = bf16_bits_to_f32(w[i] >> 16);
+        }
+    }
+}
+
+// 4 consecutive tokens at element offset 4 * c4 of `row` -> fp32 (one 16-byte or 8-byte load)
+template <int TT>
+__device__ __forceinline__ f32x4 load_tok4(const void* row, int c4) {
+    if constexpr (TT == kTokF32) {
+        return reinterpret_cast<const f32x4*>(row)[c4];
+    } else {
+        const uint2 r = reinterpret_cast<const uint2*>(row)[c4];
+        if constexpr (TT == kTokF16) {
+            const half2v a = __builtin_bit_cast(half2v, r.x), b = __builtin_bit_cast(half2v, r.y);
+            return f32x4{(float)a[0], (float)a[1], (float)b[0], (float)b[1]};
+        } else {
+            return f32x4{bf16_bits_to_f32(r.x & 0xffffu), bf16_bits_to_f32(r.x >> 16), bf16_bits_to_f32(r.y & 0xffffu),
+                         bf16_bits_to_f32(r.y >> 16)};
+        }
+    }
+}
+
 template <int KIND>
 __device__ __forceinline__ f32x16 mfma16(half8 a, half8 b, f32x16 c) {
     if constexpr (KIND == kF16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
@@ -453,8 +516,9 @@ size_t kvsplit_cache_bytes(int B, int H, int N, int terms = 3);
 int flash_split_pick_splits(int B, int H, int Lq, int Lk, int num_cus);
 // kvproj_big.hip: the K/V projection for C > 256 (pre-split tokens, LDS-DMA operands); scratch = kvproj_big_scratch_floats floats
 size_t kvproj_big_scratch_floats(int B, int N, int C);
-hipError_t launch_kvproj_big(const float* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N, int C,
-                             void* cache, int* overflow, float* scratch, hipStream_t s, int terms = 3, int kind = kF16);
+hipError_t launch_kvproj_big(const void* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N, int C,
+                             void* cache, int* overflow, float* scratch, hipStream_t s, int terms = 3, int kind = kF16,
+                             int tok_type = kTokF32);      // tok_type: element type of `tokens` (kTokF32 / kTokF16 / kTokBF16)
 // flash_split256.hip: the same for head dim 256 (a head = 4 virtual heads of 64 in the cache; wave pairs split the head dim)
 int flash_split256_pick_splits(int B, int H, int Lq, int Lk, int num_cus);
 hipError_t launch_flash_split256(const FlashArgs& a, const void* cache, hipStream_t s, int terms = 3, int kind = kF16);
@@ -490,10 +554,15 @@ hipError_t launch_set_loss(const float* logits, const float* center, const float
                            int32_t* cls, hipStream_t s);
 // terms = 11: attention mode 4 with per-head tiers — head h as mode-4 stages, or in the split layout where bit h of safe_mask is set;
 // every (scene, head) region of the cache then spans ceil(N / 32) * 16 KB (the split layout's size)
-hipError_t launch_kvproj_split(const float* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N,
-                               int C, int H, void* cache, int* overflow, hipStream_t s, int terms = 3, int kind = kF16, unsigned safe_mask = 0);
+hipError_t launch_kvproj_split(const void* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N,
+                               int C, int H, void* cache, int* overflow, hipStream_t s, int terms = 3, int kind = kF16, unsigned safe_mask = 0,
+                               int tok_type = kTokF32);
 // fp32 -> 16-bit (round to nearest) weights of the single-term modes
 hipError_t launch_cvt16(const float* src, void* dst, int64_t n, int kind, hipStream_t s);
+// 16-bit tokens (tok_type kTokF16 / kTokBF16) -> fp32, exact: the fp32 K/V projection of attention mode 0 reads the widened copy
+hipError_t launch_widen_tokens(const void* src, float* dst, int64_t n, int tok_type, hipStream_t s);
+// 16-bit tokens -> `kind` (kF16 / kBF16) rounded to nearest from their exact fp32 value: what launch_cvt16 makes of the widened tokens
+hipError_t launch_cvt16_tokens(const void* src, void* dst, int64_t n, int kind, int tok_type, hipStream_t s);
 
 // raype.hip: ray-point positional encoding + tokenisation
 hipError_t launch_raype_points(const float* cam, const float* T_cp, const float* T_wp, const float* T_wl,
@@ -503,7 +572,8 @@ hipError_t launch_raype_fused(const float* cam, const float* T_cp, const float* 
                               float min_depth, float max_depth, int B, int V, int h, int w, const void* W1hi, const void* W1lo,
                               const float* b1, const void* W2hi, const void* W2lo, const float* b2, const float* feat,
                               float* hidden, double* Tl, double* depth, float* out, int nchw_out, hipStream_t s,
-                              void* W2f = nullptr, int two_kernels = 0);
+                              void* W2f = nullptr, int two_kernels = 0,
+                              int out16 = kTokF32);      // out16: kTokF16 / kTokBF16 token rows (one-pass kernel, no hidden, channels-last)
 // GroupNorm(1, C) statistics from the float64 moments (sum, sum of squares) of a group, all in float64 (the variance is a difference
 // of two nearly equal numbers) with one reciprocal of the element count.  Used by the forward consumers and by the backward that
 // re-normalises from the same moments.  (An fp32 reciprocal square root was measured: the consumers' times did not move — the
@@ -583,7 +653,8 @@ hipError_t launch_parse_pred(const float* center, const float* size, const float
 hipError_t launch_gemm_split(const float* X, int64_t ldx, const void* Whi, const void* Wlo, const float* bias, float* Y,
                              int64_t ldy, int M, int N, int K, int relu, const float* feat, int hw, hipStream_t s,
                              const float* scale_dev = nullptr, float scale_mul = 1.f, const float* xscale_dev = nullptr,
-                             int accumulate = 0);   // Y (+)= ((x * *xscale_dev) W^T) * scale_mul / *scale_dev + bias
+                             int accumulate = 0,    // Y (+)= ((x * *xscale_dev) W^T) * scale_mul / *scale_dev + bias
+                             int out16 = kTokF32);  // Y as kTokF16 / kTokBF16 elements (rounded to nearest; not with accumulate)
 
 // ------------------------------------------------------------------ elementwise / gather kernels
 hipError_t launch_camera_local(const float* T_cp, const float* T_wp, const float* T_wl, int B, int V,
@@ -607,13 +678,14 @@ hipError_t launch_project_sample(const float* tokens, const float* T_cl, const f
                                  float* coord_pos, hipStream_t s);
 // zero_f64/zero_n: accumulators (GroupNorm moments) this kernel clears for later kernels of the iteration
 // ind / coord_off: tokens = ind[0] and coord_pos = (float*)ind[6] + coord_off instead of the two pointer arguments (CallPtrs)
-hipError_t launch_project_sample_f64(const float* tokens, const double* T_cl, const float* cam, const float* ref,
+// tok_type: element type of the token rows (kTokF32 / kTokF16 / kTokBF16), widened to fp32 as they are read
+hipError_t launch_project_sample_f64(const void* tokens, const double* T_cl, const float* cam, const float* ref,
                                      ScaleBox sb, int B, int V, int h, int w, int C, int Q, float* tgt,
                                      float* coord_pos, double* zero_f64, int zero_n, hipStream_t s, float* raw_count = nullptr,
-                                     const void* const* ind = nullptr, int64_t coord_off = 0);
-hipError_t launch_pe1_sample(const LinearArgs& pe1, const float* tokens, const double* T_cl, const float* cam, const float* ref, ScaleBox sb,
+                                     const void* const* ind = nullptr, int64_t coord_off = 0, int tok_type = kTokF32);
+hipError_t launch_pe1_sample(const LinearArgs& pe1, const void* tokens, const double* T_cl, const float* cam, const float* ref, ScaleBox sb,
                              int B, int V, int h, int w, int C, int Q, float* tgt, float* coord_pos, double* zero_f64, int zero_n,
-                             float* raw_count, hipStream_t s, const void* const* ind = nullptr, int64_t coord_off = 0);
+                             float* raw_count, hipStream_t s, const void* const* ind = nullptr, int64_t coord_off = 0, int tok_type = kTokF32);
 hipError_t launch_sample_finalize(const float* sums, const float* counts, int64_t M, int C, float* tgt, hipStream_t s,
                                   const float* range_sum = nullptr, int* range_flag = nullptr);
 hipError_t launch_shard_range_flag(const int* range_flag, float* out, hipStream_t s);

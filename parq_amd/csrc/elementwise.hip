@@ -147,19 +147,19 @@ __global__ void forward_prologue_kernel(const float* T_cp, const float* T_wp, co
 // is a single fully coalesced wave load.  Views are reduced through LDS in a fixed order.
 constexpr int kMaxChunks = 4;   // C <= 1024
 
-template <int NCH, typename TPose>
+template <int NCH, typename TPose, int TT = kTokF32>
 __global__ __launch_bounds__(1024) void project_sample_kernel(
-    const float* __restrict__ tokens, const TPose* __restrict__ T_cl, const float* __restrict__ cam,
+    const void* __restrict__ tokens, const TPose* __restrict__ T_cl, const float* __restrict__ cam,
     const float* __restrict__ ref, ScaleBox sb, int V, int h, int w, int C, int Q, float* __restrict__ tgt,
     float* __restrict__ coord_pos, double* __restrict__ zero_f64, int zero_n, float* __restrict__ raw_count,
     const void* const* __restrict__ ind, int64_t coord_off) {
     PARQ_TL_KERNEL(kTlProjectSample);
     extern __shared__ __attribute__((aligned(16))) float smem[];   // [nwv][C] + [nwv] counts + footprints
     if (ind != nullptr) {                                           // a captured forward: this call's pointers (CallPtrs; wave-uniform loads)
-        tokens = reinterpret_cast<const float*>(ind[0]);
+        tokens = ind[0];
         coord_pos = reinterpret_cast<float*>(const_cast<void*>(ind[6])) + coord_off;
     }
-    project_sample_body<NCH, TPose>(tokens, T_cl, cam, ref, sb, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, raw_count,
+    project_sample_body<NCH, TPose, TT>(tokens, T_cl, cam, ref, sb, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, raw_count,
                                     (int)blockIdx.x, (int)gridDim.x, smem);
 }
 
@@ -619,8 +619,8 @@ hipError_t launch_posemb(const float* ref, const float* dim_t, int M, float* emb
     return hipGetLastError();
 }
 
-template <typename TPose>
-static hipError_t launch_project_sample_t(const float* tokens, const TPose* T_cl, const float* cam, const float* ref,
+template <typename TPose, int TT = kTokF32>
+static hipError_t launch_project_sample_t(const void* tokens, const TPose* T_cl, const float* cam, const float* ref,
                                           ScaleBox sb, int B, int V, int h, int w, int C, int Q, float* tgt,
                                           float* coord_pos, double* zero_f64, int zero_n, hipStream_t s, float* raw_count = nullptr,
                                           const void* const* ind = nullptr, int64_t coord_off = 0) {
@@ -630,10 +630,10 @@ static hipError_t launch_project_sample_t(const float* tokens, const TPose* T_cl
     const int nch = ceil_div(C / 4, 64);
     dim3 grid(B * Q), block(nwv * 64);
     switch (nch) {
-        case 1: hipLaunchKernelGGL((project_sample_kernel<1, TPose>), grid, block, smem, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, raw_count, ind, coord_off); break;
-        case 2: hipLaunchKernelGGL((project_sample_kernel<2, TPose>), grid, block, smem, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, raw_count, ind, coord_off); break;
-        case 3: hipLaunchKernelGGL((project_sample_kernel<3, TPose>), grid, block, smem, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, raw_count, ind, coord_off); break;
-        default: hipLaunchKernelGGL((project_sample_kernel<4, TPose>), grid, block, smem, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, raw_count, ind, coord_off); break;
+        case 1: hipLaunchKernelGGL((project_sample_kernel<1, TPose, TT>), grid, block, smem, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, raw_count, ind, coord_off); break;
+        case 2: hipLaunchKernelGGL((project_sample_kernel<2, TPose, TT>), grid, block, smem, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, raw_count, ind, coord_off); break;
+        case 3: hipLaunchKernelGGL((project_sample_kernel<3, TPose, TT>), grid, block, smem, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, raw_count, ind, coord_off); break;
+        default: hipLaunchKernelGGL((project_sample_kernel<4, TPose, TT>), grid, block, smem, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, raw_count, ind, coord_off); break;
     }
     return hipGetLastError();
 }
@@ -644,10 +644,16 @@ hipError_t launch_project_sample(const float* tokens, const float* T_cl, const f
     return launch_project_sample_t<float>(tokens, T_cl, cam, ref, sb, B, V, h, w, C, Q, tgt, coord_pos, nullptr, 0, s);
 }
 
-hipError_t launch_project_sample_f64(const float* tokens, const double* T_cl, const float* cam, const float* ref,
+hipError_t launch_project_sample_f64(const void* tokens, const double* T_cl, const float* cam, const float* ref,
                                      ScaleBox sb, int B, int V, int h, int w, int C, int Q, float* tgt,
                                      float* coord_pos, double* zero_f64, int zero_n, hipStream_t s, float* raw_count,
-                                     const void* const* ind, int64_t coord_off) {
+                                     const void* const* ind, int64_t coord_off, int tok_type) {
+    // 16-bit token rows: the inference forward only (the view-sharded and training forwards keep fp32 tokens)
+    if (tok_type == kTokF16)
+        return launch_project_sample_t<double, kTokF16>(tokens, T_cl, cam, ref, sb, B, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, s, raw_count, ind, coord_off);
+    if (tok_type == kTokBF16)
+        return launch_project_sample_t<double, kTokBF16>(tokens, T_cl, cam, ref, sb, B, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, s, raw_count, ind, coord_off);
+    if (tok_type != kTokF32) return hipErrorInvalidValue;
     return launch_project_sample_t<double>(tokens, T_cl, cam, ref, sb, B, V, h, w, C, Q, tgt, coord_pos, zero_f64, zero_n, s, raw_count, ind, coord_off);
 }
 

@@ -34,13 +34,19 @@ struct BigArgs {
     int N, C, VH;                                   // VH = C / 64 virtual heads
 };
 
-// 8 fp32 -> hi/lo fp16, streaming (the pre-pass)
-__global__ __launch_bounds__(256) void split_tokens_kernel(const float* __restrict__ x, _Float16* __restrict__ hi, _Float16* __restrict__ lo,
+// 8 tokens -> hi/lo fp16, streaming (the pre-pass); TT: element type of the tokens, 16-bit ones widened to fp32 first (exact)
+template <int TT>
+__global__ __launch_bounds__(256) void split_tokens_kernel(const void* __restrict__ x, _Float16* __restrict__ hi, _Float16* __restrict__ lo,
                                                            int64_t n8, int* __restrict__ overflow) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n8) return;
-    const float4 a = reinterpret_cast<const float4*>(x)[2 * i], b = reinterpret_cast<const float4*>(x)[2 * i + 1];
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    float v[8];
+    if constexpr (TT == kTokF32) {
+        const float4 a = reinterpret_cast<const float4*>(x)[2 * i], b = reinterpret_cast<const float4*>(x)[2 * i + 1];
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+        widen8<TT>(reinterpret_cast<const u32x4*>(x)[i], v);
+    }
     bool ovf = false;
 #pragma unroll
     for (int e = 0; e < 8; ++e) ovf |= !(fabsf(v[e]) < 60000.f);
@@ -269,9 +275,10 @@ static hipError_t launch_big_t(const BigArgs& a, int B, hipStream_t s) {
 }
 
 // terms = 3: Whi / Wlo are the hi / lo planes of W_kv; terms = 1: Whi holds W_kv rounded to `kind`, Wlo is unused
-hipError_t launch_kvproj_big(const float* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N, int C,
-                             void* cache, int* overflow, float* scratch, hipStream_t s, int terms, int kind) {
+hipError_t launch_kvproj_big(const void* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N, int C,
+                             void* cache, int* overflow, float* scratch, hipStream_t s, int terms, int kind, int tok_type) {
     if (!kvproj_big_scratch_floats(B, N, C) || !scratch || B > 65535) return hipErrorInvalidValue;
+    if (tok_type != kTokF32 && tok_type != kTokF16 && tok_type != kTokBF16) return hipErrorInvalidValue;
     const int64_t n = (int64_t)B * N * C;
     _Float16* xhi = reinterpret_cast<_Float16*>(scratch);
     _Float16* xlo = xhi + n;
@@ -279,10 +286,16 @@ hipError_t launch_kvproj_big(const float* tokens, const void* Whi, const void* W
     a.Xhi = xhi; a.Xlo = xlo; a.Whi = reinterpret_cast<const _Float16*>(Whi); a.Wlo = reinterpret_cast<const _Float16*>(Wlo);
     a.bias = bias; a.cache = reinterpret_cast<_Float16*>(cache); a.overflow = overflow; a.N = N; a.C = C; a.VH = C / 64;
     if (terms == 3) {
-        hipLaunchKernelGGL(split_tokens_kernel, dim3((unsigned)ceil_div64(n / 8, 256)), dim3(256), 0, s, tokens, xhi, xlo, n / 8, overflow);
+        const dim3 grid((unsigned)ceil_div64(n / 8, 256));
+        if (tok_type == kTokF16) hipLaunchKernelGGL(split_tokens_kernel<kTokF16>, grid, dim3(256), 0, s, tokens, xhi, xlo, n / 8, overflow);
+        else if (tok_type == kTokBF16) hipLaunchKernelGGL(split_tokens_kernel<kTokBF16>, grid, dim3(256), 0, s, tokens, xhi, xlo, n / 8, overflow);
+        else hipLaunchKernelGGL(split_tokens_kernel<kTokF32>, grid, dim3(256), 0, s, tokens, xhi, xlo, n / 8, overflow);
         return launch_big_t<3, kF16>(a, B, s);
     }
-    if (hipError_t e = launch_cvt16(tokens, xhi, n, kind, s); e != hipSuccess) return e;      // (token range: checked on the K / V values in the epilogue)
+    if (hipError_t e = tok_type == kTokF32 ? launch_cvt16(reinterpret_cast<const float*>(tokens), xhi, n, kind, s)
+                                           : launch_cvt16_tokens(tokens, xhi, n, kind, tok_type, s);
+        e != hipSuccess)
+        return e;      // (token range: checked on the K / V values in the epilogue)
     return kind == kF16 ? launch_big_t<1, kF16>(a, B, s) : launch_big_t<1, kBF16>(a, B, s);
 }
 

@@ -27,7 +27,7 @@ constexpr int kThreads = 256;
 constexpr int kBlkHalfs = 8192;                 // one 32-key cache block (16 KB)
 
 struct KvProjArgs {
-    const float* X;            // tokens [B][N][C]
+    const void* X;             // tokens [B][N][C]: fp32, or 16-bit of the kernel's token type TT
     const _Float16* Whi;       // [2C][C]
     const _Float16* Wlo;
     const float* bias;         // [2C]
@@ -39,6 +39,7 @@ struct KvProjArgs {
     unsigned safe_mask; int64_t head_bytes;
 };
 
+template <int TT>
 __global__ __launch_bounds__(kThreads) void kvproj_split_kernel(KvProjArgs a) {
     extern __shared__ __attribute__((aligned(16))) _Float16 lds[];      // A_hi | A_lo | W_hi | W_lo, each [128][64]
     _Float16* Ahi = lds;
@@ -74,9 +75,12 @@ __global__ __launch_bounds__(kThreads) void kvproj_split_kernel(KvProjArgs a) {
 
     bool ovf = false;            // fp16 operand range (tokens and K / V values)
     // ---- staging assignment: 1024 A chunks (row, c) and 2048 W chunks per stage
-    float4 areg[8];
+    constexpr bool T16 = TT != kTokF32;          // 16-bit tokens: one 16-byte piece per 8 k, widened to fp32 at the LDS write
+    float4 areg[T16 ? 1 : 8];
+    u32x4 areg16[T16 ? 4 : 1];
     uint4 wreg[8];
-    const float* Xb = a.X + ((int64_t)b * a.N) * C;
+    typedef typename TokElem<TT>::type TE;
+    const TE* Xb = reinterpret_cast<const TE*>(a.X) + ((int64_t)b * a.N) * C;
     auto gload = [&](int ks) {
         const int k0 = ks * kBK;
 #pragma unroll
@@ -84,7 +88,9 @@ __global__ __launch_bounds__(kThreads) void kvproj_split_kernel(KvProjArgs a) {
             const int id = tid + i * kThreads;      // 0..1023
             const int row = id >> 3, c = id & 7;
             const int tok = m0 + row;
-            if (tok < a.N) {
+            if constexpr (T16) {
+                areg16[i] = tok < a.N ? *reinterpret_cast<const u32x4*>(Xb + (int64_t)tok * C + k0 + c * 8) : u32x4{0u, 0u, 0u, 0u};
+            } else if (tok < a.N) {
                 const float4* p = reinterpret_cast<const float4*>(Xb + (int64_t)tok * C + k0 + c * 8);
                 areg[2 * i] = p[0];
                 areg[2 * i + 1] = p[1];
@@ -111,8 +117,13 @@ __global__ __launch_bounds__(kThreads) void kvproj_split_kernel(KvProjArgs a) {
             const int id = tid + i * kThreads;
             const int row = id >> 3, c = id & 7;
             const int pos = c ^ ((row >> 1) & 7);
-            float x[8] = {areg[2 * i].x, areg[2 * i].y, areg[2 * i].z, areg[2 * i].w,
-                          areg[2 * i + 1].x, areg[2 * i + 1].y, areg[2 * i + 1].z, areg[2 * i + 1].w};
+            float x[8];
+            if constexpr (T16) {
+                widen8<TT>(areg16[i], x);
+            } else {
+                x[0] = areg[2 * i].x; x[1] = areg[2 * i].y; x[2] = areg[2 * i].z; x[3] = areg[2 * i].w;
+                x[4] = areg[2 * i + 1].x; x[5] = areg[2 * i + 1].y; x[6] = areg[2 * i + 1].z; x[7] = areg[2 * i + 1].w;
+            }
 #pragma unroll
             for (int e = 0; e < 8; ++e) ovf |= !(fabsf(x[e]) < 60000.f);          // the token operand is carried in fp16 too
             half8 hi, lo;
@@ -297,7 +308,10 @@ constexpr int kKvStampSteps = 96, kKvStampPts = 8, kKvStampBytes = 2 * kKvStampS
 #define PARQ_KV_STAMP(pt) do { } while (0)
 #endif
 
-template <int TM, int TERMS, int KIND, int NK, int D, int PROBE = 0>
+// TT (token type): 16-bit tokens fill the ring at half the bytes per k-step — one DMA instruction = 8 rows x 128 B = 1 KB of LDS, so
+// every request is still a whole kilobyte and every row piece a whole 128-byte line — and are widened to fp32 (exactly) at the
+// conversion; from there on the arithmetic is the fp32-token kernel's.
+template <int TM, int TERMS, int KIND, int NK, int D, int PROBE = 0, int TT = kTokF32>
 __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int total_rt, int nrt, int P) {
     PARQ_TL_KERNEL(kTlKvProj);
     constexpr int NWV = 8;
@@ -310,7 +324,8 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
     constexpr int kCols = NWV * 32;
     constexpr int RT = TM / 32;                  // 32-row blocks per tile (accumulators per wave)
     constexpr int C = NK * kBK;
-    constexpr int kRawBytes = TM * kBK * 4;      // one k-step of fp32 tokens
+    constexpr int kTB = tok_bytes<TT>();
+    constexpr int kRawBytes = TM * kBK * kTB;    // one k-step of tokens
     constexpr int NDMA = kRawBytes / (kThr * 16);            // DMA instructions per thread and k-step
     constexpr int NST_K = RT * 2 * (SPLIT ? 2 : 1);     // store instructions per thread and tile (mode 4: K waves 2 + 1 + 1 per block,
                                                         // V waves 2: the stage cache holds V as one fp16 plane — NST_V inside run())
@@ -318,7 +333,6 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
     static_assert(D >= 3 && D - 2 <= NK && NDMA >= 1 && NI >= 1, "wait counts below assume at most one epilogue inside the prefetch window");
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
     typedef __attribute__((address_space(3))) unsigned char lds_byte;
-    float* raw = reinterpret_cast<float*>(ldsb);
     _Float16* hl = reinterpret_cast<_Float16*>(ldsb + D * kRawBytes);
     _Float16* stg = hl + 2 * 2 * TM * kBK;       // epilogue strips: 2 KB per wave
 #if defined(PARQ_DEV_PROBES) && defined(PARQ_KV_STAMPS)
@@ -360,14 +374,16 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
         const int qq = q < last_step ? q : last_step;
         const int tile = p + (qq / NK) * P, ks = qq % NK;
         const int b = tile / nrt, m0 = (tile - b * nrt) * TM;
-        const float* Xb = a.X + ((int64_t)b * a.N) * C + ks * kBK;
+        const char* Xb = reinterpret_cast<const char*>(a.X) + (((int64_t)b * a.N) * C + ks * kBK) * kTB;
         lds_byte* dst = (lds_byte*)(ldsb) + (q % D) * kRawBytes;
         if constexpr (PROBE & 8) return;
+        constexpr int kRowB = kBK * kTB;                                      // bytes of one row of the k-step: 256 (fp32), 128 (16-bit)
+        constexpr int kRowsPer = 1024 / kRowB;                                // rows per 1 KB instruction
 #pragma unroll
         for (int j = 0; j < NDMA; ++j) {
-            const int row = (wave * NDMA + j) * 4 + (lane >> 4);              // one instruction = 4 rows x 256 B = 1 KB of LDS
+            const int row = (wave * NDMA + j) * kRowsPer + lane / (kRowB / 16);
             const int tok = m0 + row < a.N ? m0 + row : a.N - 1;
-            const char* src = reinterpret_cast<const char*>(Xb + (int64_t)tok * C) + (lane & 15) * 16;
+            const char* src = Xb + (int64_t)tok * C * kTB + (lane % (kRowB / 16)) * 16;
             __builtin_amdgcn_global_load_lds(src, dst + (wave * NDMA + j) * 1024, 16, 0, 0);
         }
     };
@@ -375,7 +391,7 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
     // conversion of k-step q (tile origin m0): raw[q % D] -> hl[q & 1]
     auto convert = [&](int q, int m0) {
         if constexpr (PROBE & 4) return;
-        float* src = raw + (q % D) * (TM * kBK);
+        const unsigned char* src = ldsb + (q % D) * kRawBytes;
         _Float16* Ahi = hl + (q & 1) * (2 * TM * kBK);
         _Float16* Alo = Ahi + TM * kBK;
 #pragma unroll
@@ -386,18 +402,28 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
             const bool ok = m0 + row < a.N;         // rows past the scene: zeros
             // read through inline asm: a C++ read of the DMA ring makes hipcc wait for EVERY outstanding global_load_lds first
             // (s_waitcnt vmcnt(0): it cannot tell the ring slots apart), which is exactly the prefetch distance this kernel is about
+            float x[8];
+            if constexpr (kTB == 2) {
+                // a thread's piece is ONE 16-byte chunk of a 128-byte row: consecutive lanes read consecutive chunks
+                u32x4 v;
+                const unsigned addr = (unsigned)(size_t)(lds_byte*)(src + (row * kBK + c * 8) * 2);
+                asm volatile("ds_read_b128 %0, %1" : "=&v"(v) : "v"(addr) : "memory");
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v)::"memory");
+                widen8<TT>(v, x);
+            } else {
             typedef float f32x4v __attribute__((ext_vector_type(4)));
             f32x4v v0, v1;
             // a thread's piece is two 16-byte chunks of one 256-byte row; odd rows fetch theirs in the opposite order, so that the
             // 16 lanes an LDS cycle serves ({0-3, 12-15, 20-27}: rows r, r+1, r+2, r+3) hit 16 different chunk positions instead of
             // 8 positions twice (rows are exactly one bank period apart: 3.1e6 conflict cycles per launch before)
             const unsigned odd = (unsigned)(row & 1) * 16u;
-            const unsigned addr = (unsigned)(size_t)(lds_byte*)(src + row * kBK + c * 8);
+            const unsigned addr = (unsigned)(size_t)(lds_byte*)(src + (row * kBK + c * 8) * 4);
             const unsigned addrA = addr + odd, addrB = addr + 16u - odd;
             asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3" : "=&v"(v0), "=&v"(v1) : "v"(addrA), "v"(addrB) : "memory");
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v0), "+v"(v1)::"memory");
             const f32x4v lo4 = odd ? v1 : v0, hi4 = odd ? v0 : v1;
-            float x[8] = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+            x[0] = lo4[0]; x[1] = lo4[1]; x[2] = lo4[2]; x[3] = lo4[3]; x[4] = hi4[0]; x[5] = hi4[1]; x[6] = hi4[2]; x[7] = hi4[3];
+            }
 #pragma unroll
             for (int e = 0; e < 8; ++e) x[e] = ok ? x[e] : 0.f;
             if constexpr (KIND == kF16) {
@@ -663,32 +689,92 @@ __global__ void cvt16_kernel(const float* __restrict__ src, _Float16* __restrict
     }
 }
 
-template <int TM, int TERMS, int KIND, int NK, int D, int PROBE = 0>
+template <int TM, int TERMS, int KIND, int NK, int D, int PROBE = 0, int TT = kTokF32>
 static hipError_t launch_dma_nk(const KvProjArgs& a, int B, hipStream_t s) {
     static DynLdsOnce once;
 #if defined(PARQ_DEV_PROBES) && defined(PARQ_KV_STAMPS)
-    const size_t lds = (size_t)D * TM * kBK * 4 + (size_t)2 * 2 * TM * kBK * sizeof(_Float16) + 8 * 2048 + kKvStampBytes;
+    const size_t lds = (size_t)D * TM * kBK * tok_bytes<TT>() + (size_t)2 * 2 * TM * kBK * sizeof(_Float16) + 8 * 2048 + kKvStampBytes;
 #else
-    const size_t lds = (size_t)D * TM * kBK * 4 + (size_t)2 * 2 * TM * kBK * sizeof(_Float16) + 8 * 2048;
+    const size_t lds = (size_t)D * TM * kBK * tok_bytes<TT>() + (size_t)2 * 2 * TM * kBK * sizeof(_Float16) + 8 * 2048;
 #endif
-    if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&kvproj_dma_kernel<TM, TERMS, KIND, NK, D, PROBE>), lds); e != hipSuccess) return e;
+    if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&kvproj_dma_kernel<TM, TERMS, KIND, NK, D, PROBE, TT>), lds); e != hipSuccess) return e;
     const int nslice = 2 * a.C / 256, nrt = ceil_div(a.N, TM);
     const int total_rt = B * nrt;
     int P = device_num_cus() / nslice;
     if (P < 1) P = 1;
     if (P > total_rt) P = total_rt;
     dim3 grid(ceil_div(P, 8) * 8 * nslice, 1, 1);
-    hipLaunchKernelGGL((kvproj_dma_kernel<TM, TERMS, KIND, NK, D, PROBE>), grid, dim3(512), lds, s, a, total_rt, nrt, P);
+    hipLaunchKernelGGL((kvproj_dma_kernel<TM, TERMS, KIND, NK, D, PROBE, TT>), grid, dim3(512), lds, s, a, total_rt, nrt, P);
     return hipGetLastError();
 }
 
-template <int TERMS, int KIND, int D>
+template <int TERMS, int KIND, int D, int TT = kTokF32>
 static hipError_t launch_dma(const KvProjArgs& a, int B, hipStream_t s) {
-    if (a.C == 4 * kBK) return launch_dma_nk<64, TERMS, KIND, 4, D>(a, B, s);
+    if (a.C == 4 * kBK) return launch_dma_nk<64, TERMS, KIND, 4, D, 0, TT>(a, B, s);
     if constexpr (D <= 4) {
-        if (a.C == 2 * kBK) return launch_dma_nk<64, TERMS, KIND, 2, D>(a, B, s);
+        if (a.C == 2 * kBK) return launch_dma_nk<64, TERMS, KIND, 2, D, 0, TT>(a, B, s);
     }
     return hipErrorInvalidValue;
+}
+
+// (the tiled kernel — head dim 64 at dims the persistent and the large-C kernels do not take — spills 144 bytes per lane in every
+// token type: its fp32 form always has, and the 16-bit forms keep that footprint with fewer VGPRs; every other 16-bit instantiation
+// of the K/V projection has no scratch)
+template <int TT>
+static hipError_t launch_tiled(const KvProjArgs& a, dim3 grid, size_t ldsb, hipStream_t s) {
+    static DynLdsOnce once;
+    if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&kvproj_split_kernel<TT>), ldsb); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kvproj_split_kernel<TT>, grid, dim3(kThreads), ldsb, s, a);
+    return hipGetLastError();
+}
+
+// the persistent kernel's product-build dispatch for 16-bit tokens (the same (terms, kind) cases as fp32 tokens, ring depth 4)
+template <int TT>
+static hipError_t launch_dma_tok16(const KvProjArgs& a, int B, int N, int C, int terms, int kind, hipStream_t s) {
+    if (terms == 8) return (N % 64 == 0 && C == 256) ? launch_dma_nk<64, 8, kF16, 4, 4, 0, TT>(a, B, s) : hipErrorInvalidValue;
+    if (terms == 11) return (N % 64 == 0 && C == 256) ? launch_dma_nk<64, 11, kF16, 4, 4, 0, TT>(a, B, s) : hipErrorInvalidValue;
+    if (terms != 3) return kind == kF16 ? launch_dma<1, kF16, 4, TT>(a, B, s) : launch_dma<1, kBF16, 4, TT>(a, B, s);
+    return launch_dma<3, kF16, 4, TT>(a, B, s);
+}
+
+template <int TT>
+__global__ void widen_tokens_kernel(const void* __restrict__ src, float* __restrict__ dst, int64_t n8) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n8) return;
+    float x[8];
+    widen8<TT>(reinterpret_cast<const u32x4*>(src)[i], x);
+    reinterpret_cast<float4*>(dst)[2 * i] = float4{x[0], x[1], x[2], x[3]};
+    reinterpret_cast<float4*>(dst)[2 * i + 1] = float4{x[4], x[5], x[6], x[7]};
+}
+
+template <int TT, int KIND>
+__global__ void cvt16_tokens_kernel(const void* __restrict__ src, _Float16* __restrict__ dst, int64_t n8) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n8) return;
+    float x[8];
+    widen8<TT>(reinterpret_cast<const u32x4*>(src)[i], x);
+    reinterpret_cast<half8*>(dst)[i] = cvt8_rn<KIND>(x);
+}
+
+hipError_t launch_widen_tokens(const void* src, float* dst, int64_t n, int tok_type, hipStream_t s) {
+    if (n % 8 != 0) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)ceil_div64(n / 8, 256));
+    if (tok_type == kTokF16) hipLaunchKernelGGL(widen_tokens_kernel<kTokF16>, grid, dim3(256), 0, s, src, dst, n / 8);
+    else if (tok_type == kTokBF16) hipLaunchKernelGGL(widen_tokens_kernel<kTokBF16>, grid, dim3(256), 0, s, src, dst, n / 8);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_cvt16_tokens(const void* src, void* dst, int64_t n, int kind, int tok_type, hipStream_t s) {
+    if (n % 8 != 0) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)ceil_div64(n / 8, 256));
+    _Float16* d = reinterpret_cast<_Float16*>(dst);
+    if (tok_type == kTokF16 && kind == kF16) hipLaunchKernelGGL((cvt16_tokens_kernel<kTokF16, kF16>), grid, dim3(256), 0, s, src, d, n / 8);
+    else if (tok_type == kTokF16) hipLaunchKernelGGL((cvt16_tokens_kernel<kTokF16, kBF16>), grid, dim3(256), 0, s, src, d, n / 8);
+    else if (tok_type == kTokBF16 && kind == kF16) hipLaunchKernelGGL((cvt16_tokens_kernel<kTokBF16, kF16>), grid, dim3(256), 0, s, src, d, n / 8);
+    else if (tok_type == kTokBF16) hipLaunchKernelGGL((cvt16_tokens_kernel<kTokBF16, kBF16>), grid, dim3(256), 0, s, src, d, n / 8);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
 }
 
 hipError_t launch_cvt16(const float* src, void* dst, int64_t n, int kind, hipStream_t s) {
@@ -707,12 +793,11 @@ hipError_t launch_split_f32(const float* src, void* hi, void* lo, int64_t n, hip
 }
 
 // tokens [B][N][C] -> split cache; Whi/Wlo [2C][C] fp16, bias [2C] fp32.  Needs C % 64 == 0, head dim 64.
-hipError_t launch_kvproj_split(const float* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N,
-                               int C, int H, void* cache, int* overflow, hipStream_t s, int terms, int kind, unsigned safe_mask) {
+hipError_t launch_kvproj_split(const void* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N,
+                               int C, int H, void* cache, int* overflow, hipStream_t s, int terms, int kind, unsigned safe_mask, int tok_type) {
     if (C % kBK != 0 || C != H * 64 || (2 * C) % kBN != 0) return hipErrorInvalidValue;
-    static DynLdsOnce once;
+    if (tok_type != kTokF32 && tok_type != kTokF16 && tok_type != kTokBF16) return hipErrorInvalidValue;
     const size_t ldsb = (size_t)(2 * kBM * kBK + 2 * kBN * kBK) * sizeof(_Float16);      // 64 KB
-    if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&kvproj_split_kernel), ldsb); e != hipSuccess) return e;
     KvProjArgs a;
     a.X = tokens; a.Whi = reinterpret_cast<const _Float16*>(Whi); a.Wlo = reinterpret_cast<const _Float16*>(Wlo);
     a.bias = bias; a.cache = reinterpret_cast<_Float16*>(cache); a.overflow = overflow; a.N = N; a.C = C; a.H = H;
@@ -720,6 +805,8 @@ hipError_t launch_kvproj_split(const float* tokens, const void* Whi, const void*
     const int nct = 2 * C / kBN, nrt = ceil_div(N, kBM);
     if (C <= 4 * kBK && C % (2 * kBK) == 0) {
         // W-stationary persistent kernel: one workgroup per CU, the column slices of one slot on one XCD
+        if (tok_type == kTokF16) return launch_dma_tok16<kTokF16>(a, B, N, C, terms, kind, s);
+        if (tok_type == kTokBF16) return launch_dma_tok16<kTokBF16>(a, B, N, C, terms, kind, s);
 #ifdef PARQ_DEV_PROBES
         if (terms == 8 && N % 64 == 0 && C == 256) {          // development: the mode-4 epilogue with one kind of store removed (results wrong)
             static const int probe8 = [] { const char* e = dev_env("PARQ_KVPROJ_PROBE8"); return e ? atoi(e) : 0; }();
@@ -765,8 +852,9 @@ hipError_t launch_kvproj_split(const float* tokens, const void* Whi, const void*
     if (terms != 3) return hipErrorInvalidValue;            // the single-term modes exist on the persistent kernel only
     dim3 grid(ceil_div(nrt, 8) * 8 * nct, B, 1);
     if (grid.y > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kvproj_split_kernel, grid, dim3(kThreads), ldsb, s, a);
-    return hipGetLastError();
+    if (tok_type == kTokF16) return launch_tiled<kTokF16>(a, grid, ldsb, s);
+    if (tok_type == kTokBF16) return launch_tiled<kTokBF16>(a, grid, ldsb, s);
+    return launch_tiled<kTokF32>(a, grid, ldsb, s);
 }
 
 PARQ_TL_DEFINE_SETTER(tl_set_kvproj_split)

@@ -121,6 +121,8 @@ struct GemmArgs {
     const float* feat; int hw;
 };
 
+// OUT: element type of Y (kTokF32, or kTokF16 / kTokBF16 rounded to nearest at the store: parq_ray_pe's 16-bit tokens)
+template <int OUT = kTokF32>
 __global__ __launch_bounds__(kThreads) void gemm_split_kernel(GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) _Float16 lds[];      // A_hi | A_lo | W_hi | W_lo, each [128][64]
     _Float16* Ahi = lds;
@@ -276,8 +278,12 @@ __global__ __launch_bounds__(kThreads) void gemm_split_kernel(GemmArgs a) {
         if (ncol < a.N) {
             float y = ot[r * 65 + lane] * osc + bv;
             if (a.relu) y = y > 0.f ? y : 0.f;
-            if (a.accumulate) y += a.Y[(int64_t)m * a.ldy + ncol];
-            a.Y[(int64_t)m * a.ldy + ncol] = y;
+            if constexpr (OUT == kTokF32) {
+                if (a.accumulate) y += a.Y[(int64_t)m * a.ldy + ncol];
+                a.Y[(int64_t)m * a.ldy + ncol] = y;
+            } else {
+                reinterpret_cast<unsigned short*>(a.Y)[(int64_t)m * a.ldy + ncol] = (unsigned short)(round2_tok16<OUT>(y, 0.f) & 0xffffu);
+            }
         }
     }
 }
@@ -649,8 +655,10 @@ __global__ void raype_pack_w2_kernel(const _Float16* __restrict__ hi, const _Flo
 // tile, 2 operand image generated once, 4 no feature loads, 8 no token stores.  Results right: 16 s_memrealtime stamps per phase (printed
 // by the launcher), 32 feature tile requested one tile ahead instead of at the tile top, 64 all row stores before the generator,
 // 128 pose through per-lane loads, 256 W2 ring of three (tools/r05_raype_variants.sh, profiles/r05_raype.txt)
-template <bool KEEP, int PROBE = 0, bool NCHW = false>
+// OUT: element type of the channels-last token rows (kTokF32, or kTokF16 / kTokBF16 rounded to nearest at the row store: 512-byte rows)
+template <bool KEEP, int PROBE = 0, bool NCHW = false, int OUT = kTokF32>
 __global__ __launch_bounds__(kFThreads, 1) void raype_onepass_kernel(RayFusedArgs a, int ntiles, int P) {
+    static_assert(OUT == kTokF32 || (!KEEP && !NCHW), "16-bit tokens: channels-last inference output only");
     extern __shared__ __attribute__((aligned(16))) _Float16 lds[];
     __shared__ double dtab[64];
     constexpr int kStep = 2 * kFTM * 64;                                // halfs per k-step (hi + lo)
@@ -931,8 +939,16 @@ __global__ __launch_bounds__(kFThreads, 1) void raype_onepass_kernel(RayFusedArg
 #pragma unroll
             for (int rr = r0; rr < r1; ++rr) {
                 const int m = tile * kFTM + wave * 8 + rr;
-                if (m < a.M && (PROBE & 8) == 0)
-                    *reinterpret_cast<float4*>(a.out + (int64_t)m * kFC + 4 * lane) = *reinterpret_cast<const float4*>(otw + rr * kOtLd);
+                if constexpr (OUT == kTokF32) {
+                    if (m < a.M && (PROBE & 8) == 0)
+                        *reinterpret_cast<float4*>(a.out + (int64_t)m * kFC + 4 * lane) = *reinterpret_cast<const float4*>(otw + rr * kOtLd);
+                } else if (m < a.M) {
+                    const float4 y = *reinterpret_cast<const float4*>(otw + rr * kOtLd);
+                    {
+                        const unsigned int lo = round2_tok16<OUT>(y.x, y.y), hi = round2_tok16<OUT>(y.z, y.w);
+                        *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(a.out) + (int64_t)m * kFC + 4 * lane) = uint2{lo, hi};
+                    }
+                }
             }
         };
         PARQ_RP_STAMP(5);
@@ -981,7 +997,9 @@ hipError_t launch_raype_fused(const float* cam, const float* T_cp, const float* 
                               float min_depth, float max_depth, int B, int V, int h, int w, const void* W1hi, const void* W1lo,
                               const float* b1, const void* W2hi, const void* W2lo, const float* b2, const float* feat,
                               float* hidden, double* Tl, double* depth, float* out, int nchw_out, hipStream_t s, void* W2f,
-                              int two_kernels) {
+                              int two_kernels, int out16) {
+    if (out16 != kTokF32 && (out16 != kTokF16 && out16 != kTokBF16)) return hipErrorInvalidValue;
+    if (out16 != kTokF32 && (hidden || nchw_out || (two_kernels & 1) || !W2f)) return hipErrorInvalidValue;   // one-pass inference rows only
     const int S = 64;
     const int64_t M64 = (int64_t)B * V * h * w;
     if (M64 > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -1027,6 +1045,14 @@ hipError_t launch_raype_fused(const float* cam, const float* T_cp, const float* 
             static DynLdsOnce once_nn;
             if (hipError_t e = once_nn.ensure(reinterpret_cast<const void*>(&raype_onepass_kernel<false, 0, true>), lds_f); e != hipSuccess) return e;
             hipLaunchKernelGGL((raype_onepass_kernel<false, 0, true>), dim3(P), dim3(kFThreads), lds_f, s, a, ntiles, P);
+        } else if (out16 == kTokF16) {
+            static DynLdsOnce once_h;
+            if (hipError_t e = once_h.ensure(reinterpret_cast<const void*>(&raype_onepass_kernel<false, 0, false, kTokF16>), lds_f); e != hipSuccess) return e;
+            hipLaunchKernelGGL((raype_onepass_kernel<false, 0, false, kTokF16>), dim3(P), dim3(kFThreads), lds_f, s, a, ntiles, P);
+        } else if (out16 == kTokBF16) {
+            static DynLdsOnce once_b16;
+            if (hipError_t e = once_b16.ensure(reinterpret_cast<const void*>(&raype_onepass_kernel<false, 0, false, kTokBF16>), lds_f); e != hipSuccess) return e;
+            hipLaunchKernelGGL((raype_onepass_kernel<false, 0, false, kTokBF16>), dim3(P), dim3(kFThreads), lds_f, s, a, ntiles, P);
         } else {
 #ifdef PARQ_DEV_PROBES
             static const int probe = [] { const char* e = dev_env("PARQ_RAYPE_PROBE"); return e ? atoi(e) : 0; }();
@@ -1087,11 +1113,10 @@ hipError_t launch_raype_fused(const float* cam, const float* T_cp, const float* 
 // Y[M][N] = act(X[M][K] @ W^T + bias) (+ NCHW features); W given as fp16 hi/lo [N][K]; K % 64 == 0
 hipError_t launch_gemm_split(const float* X, int64_t ldx, const void* Whi, const void* Wlo, const float* bias, float* Y,
                              int64_t ldy, int M, int N, int K, int relu, const float* feat, int hw, hipStream_t s,
-                             const float* scale_dev, float scale_mul, const float* xscale_dev, int accumulate) {
+                             const float* scale_dev, float scale_mul, const float* xscale_dev, int accumulate, int out16) {
     if (K % kBK != 0 || M < 1 || N < 1 || (relu && feat)) return hipErrorInvalidValue;
-    static DynLdsOnce once;
+    if (out16 != kTokF32 && ((out16 != kTokF16 && out16 != kTokBF16) || accumulate)) return hipErrorInvalidValue;
     const size_t ldsb = 4 * 64 * 65 * sizeof(float);                    // 66560 B >= the 64 KB of operand staging
-    if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&gemm_split_kernel), ldsb); e != hipSuccess) return e;
     GemmArgs a;
     a.X = X; a.ldx = ldx; a.Whi = reinterpret_cast<const _Float16*>(Whi); a.Wlo = reinterpret_cast<const _Float16*>(Wlo);
     a.bias = bias; a.Y = Y; a.ldy = ldy; a.M = M; a.N = N; a.K = K; a.relu = relu; a.feat = feat; a.hw = hw;
@@ -1099,8 +1124,15 @@ hipError_t launch_gemm_split(const float* X, int64_t ldx, const void* Whi, const
     const int nct = ceil_div(N, kBN), nrt = ceil_div(M, kBM);
     const int64_t wgs = (int64_t)ceil_div(nrt, 8) * 8 * nct;
     if (wgs > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(gemm_split_kernel, dim3((unsigned)wgs), dim3(kThreads), ldsb, s, a);
-    return hipGetLastError();
+    auto launch = [&](auto kern, DynLdsOnce& once) {
+        if (hipError_t e = once.ensure(reinterpret_cast<const void*>(kern), ldsb); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(kThreads), ldsb, s, a);
+        return hipGetLastError();
+    };
+    static DynLdsOnce once, once_h, once_b;
+    if (out16 == kTokF16) return launch(gemm_split_kernel<kTokF16>, once_h);
+    if (out16 == kTokBF16) return launch(gemm_split_kernel<kTokBF16>, once_b);
+    return launch(gemm_split_kernel<kTokF32>, once);
 }
 
 }  // namespace parq

@@ -7,9 +7,11 @@ namespace parq {
 
 // bq: (scene, query) index of this workgroup; nbq: number of such workgroups in the launch (the zeroing of `zero_f64` is spread over
 // them); smem: [nwv][C] partial sums + [nwv] counts + V footprints of 32 bytes (launch_project_sample_t sizes it)
-template <int NCH, typename TPose>
+// TT: element type of the token rows (kTokF32 / kTokF16 / kTokBF16); a lane reads 4 consecutive channels of a row (16 or 8 bytes), so
+// a row is one coalesced wave request in every type, and the arithmetic after the widening is the same
+template <int NCH, typename TPose, int TT = kTokF32>
 __device__ __forceinline__ void project_sample_body(
-    const float* __restrict__ tokens, const TPose* __restrict__ T_cl, const float* __restrict__ cam,
+    const void* __restrict__ tokens_v, const TPose* __restrict__ T_cl, const float* __restrict__ cam,
     const float* __restrict__ ref, ScaleBox sb, int V, int h, int w, int C, int Q, float* __restrict__ tgt,
     float* __restrict__ coord_pos, double* __restrict__ zero_f64, int zero_n, float* __restrict__ raw_count, int bq, int nbq,
     float* smem) {
@@ -87,20 +89,21 @@ __device__ __forceinline__ void project_sample_body(
         const int x0 = f.x0, y0 = f.y0;
         const bool x0ok = x0 >= 0, x1ok = x0 + 1 <= w - 1;
         const bool y0ok = y0 >= 0, y1ok = y0 + 1 <= h - 1;
-        const float* base = tokens + (((int64_t)b * V + v) * h) * (int64_t)w * C;
-        const float* r00 = base + ((int64_t)(y0ok ? y0 : 0) * w + (x0ok ? x0 : 0)) * C;
-        const float* r01 = base + ((int64_t)(y0ok ? y0 : 0) * w + (x1ok ? x0 + 1 : 0)) * C;
-        const float* r10 = base + ((int64_t)(y1ok ? y0 + 1 : 0) * w + (x0ok ? x0 : 0)) * C;
-        const float* r11 = base + ((int64_t)(y1ok ? y0 + 1 : 0) * w + (x1ok ? x0 + 1 : 0)) * C;
+        typedef typename TokElem<TT>::type TE;
+        const TE* base = reinterpret_cast<const TE*>(tokens_v) + (((int64_t)b * V + v) * h) * (int64_t)w * C;
+        const TE* r00 = base + ((int64_t)(y0ok ? y0 : 0) * w + (x0ok ? x0 : 0)) * C;
+        const TE* r01 = base + ((int64_t)(y0ok ? y0 : 0) * w + (x1ok ? x0 + 1 : 0)) * C;
+        const TE* r10 = base + ((int64_t)(y1ok ? y0 + 1 : 0) * w + (x0ok ? x0 : 0)) * C;
+        const TE* r11 = base + ((int64_t)(y1ok ? y0 + 1 : 0) * w + (x1ok ? x0 + 1 : 0)) * C;
         const float w00 = f.w00, w01 = f.w01, w10 = f.w10, w11 = f.w11;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             const int c4 = lane + c * 64;
             if (c4 < C4) {
-                const f32x4 a00 = reinterpret_cast<const f32x4*>(r00)[c4];
-                const f32x4 a01 = reinterpret_cast<const f32x4*>(r01)[c4];
-                const f32x4 a10 = reinterpret_cast<const f32x4*>(r10)[c4];
-                const f32x4 a11 = reinterpret_cast<const f32x4*>(r11)[c4];
+                const f32x4 a00 = load_tok4<TT>(r00, c4);
+                const f32x4 a01 = load_tok4<TT>(r01, c4);
+                const f32x4 a10 = load_tok4<TT>(r10, c4);
+                const f32x4 a11 = load_tok4<TT>(r11, c4);
                 acc[c] += a00 * w00 + a01 * w01 + a10 * w10 + a11 * w11;
             }
         }

@@ -195,6 +195,9 @@ class _TransformerParams(_Tracked, nn.Module):
 # (fp32-class accuracy, default at head dims 64 and 256), "fp32" = exact fp32 MFMA, "fp16" / "bf16" = single reduced-precision
 # products (BASELINE configs 2 and 5; head dim 64 with dim 128 / 256, head dim 256 with dim a multiple of 128)
 ATTENTION_MODES = {"fp32": 0, "split": 1, "fp16": 2, "bf16": 3, "split8": 4}
+# element types the inference entry points take tokens in as they are (include/parq_hip.h parq_set_token_type); anything else is
+# converted to fp32 first
+TOKEN_TYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
 class _Stash:
@@ -624,6 +627,7 @@ class PARQDecoder(_Tracked, nn.Module):
             _lib.check(lib.parq_create(C.byref(cfg), C.byref(h)), "parq_create")
             self._h = h
             self._mode_set = None
+            self._tok_set = 0                # the handle's default token type (fp32)
             self._tiers_set = None
             self._seams_set = None
             self._bwd_batched_set = None
@@ -675,10 +679,25 @@ class PARQDecoder(_Tracked, nn.Module):
             return "split8"
         return "split" if dh in (64, 256) and self.attention_mode != "fp32" else "fp32"
 
+    def _token_type(self, h, tt):
+        """Switch the handle to token type `tt` (TOKEN_TYPES value) for the calls that follow."""
+        if self._tok_set != tt:
+            _lib.check(_lib.load().parq_set_token_type(h, tt), "parq_set_token_type")
+            self._tok_set = tt
+
+    def _ws_token_key(self, tt):
+        """Whether the token type changes a workspace's carving: only where the fp32 K/V projection reads a widened copy of 16-bit
+        tokens (attention mode "fp32", or a head dim without the split cache) — the same copy for fp16 and bf16, so the two share it
+        (their graphs are keyed apart in _enqueue_forward)."""
+        cache = self.attention_mode != "fp32" and self.dim_in // self.num_heads in (64, 256)
+        return 0 if cache or tt == 0 else 1
+
     def _handle_in_mode(self, mode):
         """The handle switched to `mode` without touching the user-facing ``attention_mode`` (the training entry points need
-        the exact-fp32 attention kernels: their backward reads the fp32 K/V cache); the next inference call switches back."""
+        the exact-fp32 attention kernels: their backward reads the fp32 K/V cache); the next inference call switches back.
+        Its token type is fp32: the training and view-sharded entry points read fp32 tokens only."""
         h = self._handle(apply_mode=False)
+        self._token_type(h, 0)
         if self._mode_set != mode:
             _lib.check(_lib.load().parq_set_attention_mode(h, ATTENTION_MODES[mode]), "parq_set_attention_mode")
             self._mode_set = mode
@@ -793,7 +812,7 @@ class PARQDecoder(_Tracked, nn.Module):
             ev.record(torch.cuda.current_stream(device))
             self._arena_event = ev
 
-    def _workspace_entry(self, B, V, h, w, device, handle=None):
+    def _workspace_entry(self, B, V, h, w, device, handle=None, tok=0):
         """Workspace (K/V cache + activations) of a batch shape.  The ``max_workspaces`` most recently used shapes stay alive, so
         a driver that alternates two shapes (e.g. train / validation snippets) does not reallocate a K/V cache per call; each holds
         a K/V cache (393 MB per scene at BASELINE cfg 3), so ``max_workspaces = 1`` halves the module's footprint for single-shape
@@ -803,7 +822,7 @@ class PARQDecoder(_Tracked, nn.Module):
         # keyed by the launch stream too: forwards enqueued on different streams (two scenes in flight: the small-op chain of one
         # leaves most of the chip to the K/V projection and cross-attention of the other, +18 % throughput at BASELINE cfg 3,
         # profiles/r05_two_in_flight.txt) each own a workspace; a workspace is allocated, used and freed in the order of ONE stream
-        k = (B, V, h, w, device.index, _raw_stream(device))
+        k = (B, V, h, w, device.index, _raw_stream(device)) + ((tok,) if tok else ())     # tok: _ws_token_key
         entry = self._ws.take(k)
         if entry is None:
             st = torch.cuda.current_stream(device)
@@ -820,7 +839,9 @@ class PARQDecoder(_Tracked, nn.Module):
         return self._workspace_entry(B, V, h, w, device, handle).ws
 
     # ------------------------------------------------------------------ argument packing
-    def _scene(self, tokens, camera, T_cp, T_wp, T_wl, feat_hw):
+    def _scene(self, tokens, camera, T_cp, T_wp, T_wl, feat_hw, native16=False):
+        """ctypes scene of one call and the tensors it points at.  native16: fp16 / bf16 tokens stay 16-bit (a contiguous copy if
+        they are not contiguous); otherwise every tensor is fp32."""
         tokens = raw(tokens)
         cam, T_cp, T_wp, T_wl = raw(camera), raw(T_cp), raw(T_wp), raw(T_wl)
         if not tokens.is_cuda:
@@ -833,7 +854,12 @@ class PARQDecoder(_Tracked, nn.Module):
                 t = t.to(device=dev, dtype=torch.float32)
             assert t.shape[-1] == last, (tuple(t.shape), last)
             return t if t.is_contiguous() else t.contiguous()
-        tokens = prep(tokens, self.dim_in)
+        if native16 and tokens.dtype in (torch.float16, torch.bfloat16):
+            tokens = tokens if tokens.device == dev else tokens.to(dev)
+            assert tokens.shape[-1] == self.dim_in, (tuple(tokens.shape), self.dim_in)
+            tokens = tokens if tokens.is_contiguous() and tokens.data_ptr() % 16 == 0 else tokens.clone(memory_format=torch.contiguous_format)
+        else:
+            tokens = prep(tokens, self.dim_in)
         cam, T_cp, T_wp, T_wl = prep(cam, 6), prep(T_cp, 12), prep(T_wp, 12), prep(T_wl, 12)
         B, N, _ = tokens.shape
         assert cam.dim() == 3 and cam.shape[0] == B, "camera must be (B,V,6)"
@@ -848,7 +874,7 @@ class PARQDecoder(_Tracked, nn.Module):
             feat_hw = (int(hf), int(wf))
         h, w = int(feat_hw[0]), int(feat_hw[1])
         assert V * h * w == N, "tokens (N=%d) do not match V*h*w = %d*%d*%d" % (N, V, h, w)
-        sc = _lib.ParqScene(B, V, h, w, _lib.ptr(tokens), _lib.ptr(cam), _lib.ptr(T_cp), _lib.ptr(T_wp), _lib.ptr(T_wl))
+        sc = _lib.ParqScene(B, V, h, w, _lib.token_ptr(tokens), _lib.ptr(cam), _lib.ptr(T_cp), _lib.ptr(T_wp), _lib.ptr(T_wl))
         return sc, (tokens, cam, T_cp, T_wp, T_wl), dev
 
     def _alloc_outputs(self, lead, device):
@@ -885,7 +911,9 @@ class PARQDecoder(_Tracked, nn.Module):
         parameter or the tokens require grad) the result carries a graph — in ``train()`` mode with the decoder layer's dropout,
         in ``eval()`` mode without it (the reference differentiates in eval mode too, model/parq_decoder.py:134-163).  Under
         ``torch.no_grad()`` (eval.py:46, Lightning's validation loop), or with nothing that requires grad, the inference chain
-        runs: no saved activations, the folded position MLP, one K/V workspace."""
+        runs: no saved activations, the folded position MLP, one K/V workspace.  Tokens: the inference chain takes float16 / bfloat16
+        tokens as they are (bit-identical to the call on ``tokens.float()``, without that fp32 copy; include/parq_hip.h
+        parq_set_token_type); the autograd path and ``forward_view_sharded`` convert them to float32 as before, like any other dtype."""
         if torch.is_grad_enabled() and (self.training or self._needs_graph(intput_tokens)):
             if not self.training and not getattr(self, "_warned_eval_autograd", False):
                 import warnings
@@ -916,7 +944,7 @@ class PARQDecoder(_Tracked, nn.Module):
     def _forward_inference(self, intput_tokens, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, feat_hw=None):
         self._check_mode()
         self._range_poll()
-        sc, keep, dev = self._scene(intput_tokens, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, feat_hw)
+        sc, keep, dev = self._scene(intput_tokens, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, feat_hw, native16=True)
         self._ensure_packed(dev)
         self._order_behind_pack(dev)
         lead = (self.num_layers, sc.B, self.num_queries)
@@ -989,7 +1017,9 @@ class PARQDecoder(_Tracked, nn.Module):
         projection (parq_forward_replay); launch by launch otherwise (parq_forward).  Returns its _Run."""
         lib = _lib.load()
         h = self._handle()
-        entry = self._workspace_entry(sc.B, sc.V, sc.h, sc.w, dev, handle=h)
+        tt = TOKEN_TYPES[keep[0].dtype]
+        self._token_type(h, tt)                             # (before the workspace is sized: mode "fp32" carves a widened copy)
+        entry = self._workspace_entry(sc.B, sc.V, sc.h, sc.w, dev, handle=h, tok=self._ws_token_key(tt))
         ws = entry.ws
         self._set_mirror(entry.slot)
         self._epoch = (self._epoch % 0x7ffffff0) + 1
@@ -1000,7 +1030,7 @@ class PARQDecoder(_Tracked, nn.Module):
         po = self._out_pointers(flat.data_ptr(), self.num_layers * sc.B * self.num_queries)
         graph = None
         if self.use_graph and not self._profiling:
-            key = (self._arena_gen, self._mode_set, self._tiers_set, self._seams_set)
+            key = (self._arena_gen, self._mode_set, self._tiers_set, self._seams_set, tt)
             graph = entry.graphs.get(key)
             if graph is None and entry.last_key == key:
                 graph = self._capture(entry, key, sc, stream)
@@ -1175,10 +1205,13 @@ class PARQDecoder(_Tracked, nn.Module):
     @torch.no_grad()
     def prepare(self, intput_tokens, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, feat_hw=None):
         self._check_mode()
-        sc, keep, dev = self._scene(intput_tokens, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, feat_hw)
+        sc, keep, dev = self._scene(intput_tokens, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, feat_hw, native16=True)
         self._ensure_packed(dev)
         self._order_behind_pack(dev)
-        entry = self._workspace_entry(sc.B, sc.V, sc.h, sc.w, dev)
+        h = self._handle()
+        tt = TOKEN_TYPES[keep[0].dtype]
+        self._token_type(h, tt)
+        entry = self._workspace_entry(sc.B, sc.V, sc.h, sc.w, dev, handle=h, tok=self._ws_token_key(tt))
         ws = entry.ws
         self._set_mirror(entry.slot)
         _lib.check(_lib.load().parq_prepare(self._handle(), C.byref(sc), _lib.ptr(ws), ws.numel() * 4, _lib.stream_ptr()),
@@ -1196,7 +1229,9 @@ class PARQDecoder(_Tracked, nn.Module):
         if ref_in is not None:
             ref_in = ref_in.to(device=dev, dtype=torch.float32).contiguous()
             assert ref_in.shape == (sc.B, self.num_queries, 3)
-        _lib.check(_lib.load().parq_iterate(self._handle(), C.byref(sc), _lib.ptr(ws), ws.numel() * 4, int(layer_num),
+        h = self._handle()
+        self._token_type(h, TOKEN_TYPES[keep[0].dtype])
+        _lib.check(_lib.load().parq_iterate(h, C.byref(sc), _lib.ptr(ws), ws.numel() * 4, int(layer_num),
                                             _lib.ptr(ref_in), C.byref(po), _lib.ptr(nxt), _lib.stream_ptr()),
                    "parq_iterate")
         return dict(zip(OUTPUT_KEYS, outs)), nxt
@@ -1230,6 +1265,7 @@ class PARQDecoder(_Tracked, nn.Module):
         for _attempt in range(2):
             # mode "split8" runs as "split" here: its peakedness guard looks at whole rows, a rank sees only its shard of the keys
             h = self._handle_in_mode("split") if self.attention_mode == "split8" else self._handle()
+            self._token_type(h, 0)                                              # (fp32 tokens: _scene upcast them)
             ws = self._workspace(sc.B, sc.V, sc.h, sc.w, dev, handle=h)       # (not through _handle(): it would re-apply "split8")
             _lib.check(lib.parq_prepare(h, C.byref(sc), _lib.ptr(ws), ws.numel() * 4, _lib.stream_ptr()), "parq_prepare")
             na, nb = lib.parq_shard_exchange_floats(h, sc.B, 0), lib.parq_shard_exchange_floats(h, sc.B, 1)
@@ -1274,7 +1310,7 @@ class PARQDecoder(_Tracked, nn.Module):
 
     def _last_ws(self):
         k, entry = list(self._ws.items())[-1]
-        return k, entry.ws
+        return k[:6], entry.ws                       # (B, V, h, w, device, stream) — without the token key of _workspace_entry
 
     def fp16_range_exceeded(self):
         """True if the last prepare() / forward() / forward_train() saw a token, K or V element outside the fp16 range while

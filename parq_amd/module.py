@@ -38,6 +38,10 @@ class PARQ(_Base):
                                    _get(tk, "MIN_DEPTH"), _get(tk, "MAX_DEPTH"))
         self.box3d_decoder = PARQDecoder(_get(cfg, "MODEL.DECODER"))
         self.for_vis = _get(cfg, "MODEL.DECODER.FOR_VIS")
+        # None: float32 tokens (the reference).  torch.float16 / torch.bfloat16: the inference chain hands the decoder 16-bit tokens
+        # written by the ray-PE kernel, which the decoder reads as they are (bit-identical to decoding their float32 upcast); with a
+        # graph the ray-PE node stays float32 and its output is converted, and the decoder's autograd path upcasts again
+        self.token_dtype = None
         self.synced_metrics = {}          # validation metrics averaged over the ranks (what the reference logs with sync_dist=True)
 
     def set_data_parallel(self, on=True):
@@ -55,7 +59,7 @@ class PARQ(_Base):
         feats = batch["all_features"]
         # encoding + `images_feat = features + encoding` + both einops rearranges, fused (parq_lightning.py:72-85)
         input_tokens = self.add_ray_pe.tokens(feats, batch["camera_feature"], batch["T_camera_pseudoCam"],
-                                              batch["T_world_pseudoCam"], batch["T_world_local"])
+                                              batch["T_world_pseudoCam"], batch["T_world_local"], dtype=self.token_dtype)
         outputs = self.box3d_decoder(input_tokens, batch["camera_feature"], batch["T_camera_pseudoCam"],
                                      batch["T_world_pseudoCam"], batch["T_world_local"],
                                      feat_hw=tuple(feats.shape[-2:]))

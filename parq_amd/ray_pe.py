@@ -93,7 +93,7 @@ class AddRayPE(nn.Module):
         self._ws_owner = None             # weak reference to the _WsHold of the autograd node that owns ``_ws`` (if any)
         self.dp_all_reduce = False        # True: the backward all-reduces (mean) the encoder gradients over the default process group
 
-    def _run(self, camera, T_cp, T_wp, T_wl, feat_hw, features, nchw=False, own_workspace=False):
+    def _run(self, camera, T_cp, T_wp, T_wl, feat_hw, features, nchw=False, own_workspace=False, out_dtype=torch.float32):
         cam, T_cp, T_wp, T_wl = (raw(x) for x in (camera, T_cp, T_wp, T_wl))
         if not cam.is_cuda:
             raise RuntimeError("parq_amd.AddRayPE runs on the GPU only (there is no CPU fallback)")
@@ -123,6 +123,10 @@ class AddRayPE(nn.Module):
         fused = Cd == 256 and self.num_samples == 64          # the library's one-pass path can write (B, V, C, h, w) directly
         nchw = bool(nchw and fused)
         flags = (1 if nchw else 0) | (0 if own_workspace else 2)
+        # 8 / 16: fp16 / bf16 token rows, rounded to nearest in the kernel (inference, channels-last)
+        out16 = {torch.float32: 0, torch.float16: 8, torch.bfloat16: 16}[out_dtype]
+        assert not (out16 and (nchw or own_workspace)), "16-bit tokens: channels-last inference output only"
+        flags |= out16
         nbytes = lib.parq_ray_pe_workspace_bytes_flags(B, V, h, w, Cd, self.num_samples, flags)
         owner = self._ws_owner() if self._ws_owner is not None else None
         if owner is not None and not owner.consumed and owner.ws is self._ws:
@@ -138,13 +142,13 @@ class AddRayPE(nn.Module):
         if key == self._ws_key:
             flags |= 4
         self._ws_key = key
-        out = torch.empty((B, V, Cd, h, w) if nchw else (B, V * h * w, Cd), dtype=torch.float32, device=dev)
+        out = torch.empty((B, V, Cd, h, w) if nchw else (B, V * h * w, Cd), dtype=out_dtype, device=dev)
         p = [prep(t.detach()) for t in (self.encoder[0].weight, self.encoder[0].bias, self.encoder[2].weight,
                                         self.encoder[2].bias)]
         _lib.check(lib.parq_ray_pe(_lib.ptr(cam), _lib.ptr(T_cp), _lib.ptr(T_wp), _lib.ptr(T_wl), _lib.ptr(p[0]),
                                    _lib.ptr(p[1]), _lib.ptr(p[2]), _lib.ptr(p[3]), (C.c_float * 6)(*self.ray_points_scale),
                                    self.min_depth, self.max_depth, self.num_samples, B, V, h, w, Cd, _lib.ptr(features),
-                                   _lib.ptr(out), flags, _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr()),
+                                   _lib.token_ptr(out), flags, _lib.ptr(self._ws), self._ws.numel() * 4, _lib.stream_ptr()),
                    "parq_ray_pe")
         self._ws._parq_gen = self._gen
         return out, (B, V, h, w), nchw
@@ -171,15 +175,22 @@ class AddRayPE(nn.Module):
             enc, (B, V, h, w), nchw = self._run(camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, hw, None, nchw=True)
             return enc if nchw else enc.view(B, V, h, w, self.dim_out).permute(0, 1, 4, 2, 3)
 
-    def tokens(self, images_feat, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local):
+    def tokens(self, images_feat, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, dtype=None):
         """features + encoding, tokenised channels-last (B, T*H*W, C) in one pass.  With gradients enabled and anything to
         differentiate (train mode, an encoder parameter or the feature maps requiring grad — eval mode included, like the
-        reference) the call is an autograd node that owns the workspace holding the hidden layer for its backward."""
+        reference) the call is an autograd node that owns the workspace holding the hidden layer for its backward.
+        ``dtype`` (None = float32): torch.float16 / torch.bfloat16 tokens — written as such by the kernel on the inference path
+        (each element the float32 result rounded to nearest, i.e. equal to ``tokens(...).to(dtype)``), the float32 autograd node
+        followed by ``.to(dtype)`` with a graph."""
+        if dtype is not None and dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError("AddRayPE.tokens: dtype must be None, torch.float32, torch.float16 or torch.bfloat16")
         if self._needs_graph(images_feat):
             e0, e2 = self.encoder[0], self.encoder[2]
-            return _RayPeFn.apply(self, images_feat, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local,
-                                  e0.weight, e0.bias, e2.weight, e2.bias)
+            out = _RayPeFn.apply(self, images_feat, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local,
+                                 e0.weight, e0.bias, e2.weight, e2.bias)
+            return out if dtype in (None, torch.float32) else out.to(dtype)
         with torch.no_grad():
             hw = tuple(images_feat.shape[-2:])
-            out, _, _ = self._run(camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, hw, images_feat)
+            out, _, _ = self._run(camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, hw, images_feat,
+                                  out_dtype=dtype or torch.float32)
             return out
