@@ -334,8 +334,22 @@ int parq_grad_bucket(parq_handle h, int32_t bucket, int64_t *offset, int64_t *co
 int parq_backward_wait_bucket(parq_handle h, int32_t bucket, parq_stream stream);
 /* Iterations of the chain backward in flight at once (default 8: up to eight streams, weight gradients met in the arena through
  * float atomics — the last bits of the gradients then vary from run to run).  1 = in turn on the caller's stream with plain
- * accumulation (reproducible chain gradients).  Changes the training workspace size: call before parq_train_workspace_bytes. */
+ * accumulation of the chain's weight gradients (other reductions still add with atomics: parq_set_deterministic below makes the
+ * whole backward reproducible).  Changes the training workspace size: call before parq_train_workspace_bytes. */
 int parq_set_backward_streams(parq_handle h, int32_t n);
+/* Deterministic mode (the promise of torch.use_deterministic_algorithms): with `on` = 1, every reduction of parq_forward_train and
+ * parq_backward runs in a fixed order that does not depend on timing, so that two calls on the same inputs give the same bits.
+ *   - forward: the GroupNorm moments of the heads (added by the producing GEMM with float64 atomics into shared slots) are
+ *     recomputed from the stored activations in a fixed order before they are read;
+ *   - backward: row-split weight, bias and norm-parameter gradients, the K/V-projection weight gradient of the split-precision
+ *     kernel (and the head-dim-256 dQ slices it also forms) write one fp32 partial per row range, and a second launch sums them in
+ *     index order; GroupNorm backward sums likewise (float64); the token gradient of project + sample is gathered per token in
+ *     query order instead of scattered with atomics; the short-key attention backward keeps per-workgroup dQ partials summed in
+ *     key-block order (the long-key and batched kernels do so already); everything runs on the caller's stream (one backward stream).
+ * The training workspace grows by the partials (≈ 67 MB on a 256-CU device): call before parq_train_workspace_bytes.  Gradients
+ * agree with the default mode to fp32 summation order.  Head dim 32 has no fixed-order attention backward: parq_backward returns
+ * PARQ_ERR_ARG there.  `on` other than 0 / 1 is PARQ_ERR_ARG.  Default 0. */
+int parq_set_deterministic(parq_handle h, int32_t on);
 
 /* ---- AddRayPE.forward + tokenisation (model/ray_positional_encoding.py:61-139,
  *      model/parq_lightning.py:72-85), once per forward -------------------------------------
@@ -374,6 +388,18 @@ int parq_ray_pe_backward(const float *camera, const float *T_camera_pseudoCam, c
                          float max_depth, int32_t num_samples, int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C,
                          const float *d_tokens, const void *fwd_workspace, void *bwd_workspace, size_t bwd_workspace_bytes,
                          float *dw1, float *db1, float *dw2, float *db2, float *d_features_nchw, parq_stream stream);
+/* PARQ_RAYPE_BWD_DETERMINISTIC: the column sums and weight products of the backward sum their row-range partials in index order
+ * (bit-identical results from run to run) instead of adding them with float atomics; the workspace is larger by the partials
+ * (parq_ray_pe_backward_workspace_bytes_flags with the same flags).  Unknown flag bits: PARQ_ERR_ARG (size 0). */
+enum { PARQ_RAYPE_BWD_DETERMINISTIC = 1 };
+size_t parq_ray_pe_backward_workspace_bytes_flags(int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C, int32_t num_samples,
+                                                  int32_t flags);
+int parq_ray_pe_backward_flags(const float *camera, const float *T_camera_pseudoCam, const float *T_world_pseudoCam,
+                               const float *T_world_local, const float *w2, const float *scale6_host, float min_depth,
+                               float max_depth, int32_t num_samples, int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C,
+                               const float *d_tokens, const void *fwd_workspace, void *bwd_workspace, size_t bwd_workspace_bytes,
+                               float *dw1, float *db1, float *dw2, float *db2, float *d_features_nchw, int32_t flags,
+                               parq_stream stream);
 
 /* ---- eval post-processing (model/parq_decoder.py:372-424 parse_pred + utils/nms.py), one workgroup per scene ----------
  * From the LAST iteration's outputs: obbs_out (B,Q,19) = [-s/2, s/2 per axis | R(ortho6d) centre | arg-max class],
@@ -400,6 +426,16 @@ int parq_set_loss(const float *pred_logits, const float *center_unnormalized, co
                   const int32_t *t_label, const int32_t *t_sym, int32_t nmax, const int32_t *pairs, const float *pair_coef, int32_t P,
                   const float *row_weight, const float *class_weight, const float *loss_weight4_host, float *terms, float *g_logits,
                   float *g_center, float *g_size, float *g_ortho6d, int32_t *class_scratch, parq_stream stream);
+/* PARQ_SETLOSS_DETERMINISTIC: the four terms are summed from per-workgroup partials in workgroup order (bit-identical from run to run)
+ * instead of with float atomics.  class_scratch must then hold parq_set_loss_scratch_bytes(I, B, Q, P, flags) bytes (the partials
+ * follow the I*B*Q class targets).  Unknown flag bits: PARQ_ERR_ARG (size 0). */
+enum { PARQ_SETLOSS_DETERMINISTIC = 1 };
+size_t parq_set_loss_scratch_bytes(int32_t I, int32_t B, int32_t Q, int32_t P, int32_t flags);
+int parq_set_loss_flags(const float *pred_logits, const float *center_unnormalized, const float *size_unnormalized, const float *ortho6d,
+                        int32_t I, int32_t B, int32_t Q, int32_t num_classes, const float *t_center, const float *t_size, const float *t_rot,
+                        const int32_t *t_label, const int32_t *t_sym, int32_t nmax, const int32_t *pairs, const float *pair_coef, int32_t P,
+                        const float *row_weight, const float *class_weight, const float *loss_weight4_host, float *terms, float *g_logits,
+                        float *g_center, float *g_size, float *g_ortho6d, int32_t *class_scratch, int32_t flags, parq_stream stream);
 
 /* ---- single kernels (parity tests, roofline measurements) --------------------------- */
 

@@ -87,6 +87,7 @@ SYMBOLS = {
     "parq_grad_bucket": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
     "parq_backward_wait_bucket": (C.c_int, [_vp, _i32, _vp]),
     "parq_set_backward_streams": (C.c_int, [_vp, _i32]),
+    "parq_set_deterministic": (C.c_int, [_vp, _i32]),
     "parq_ray_pe_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "parq_ray_pe_workspace_bytes_flags": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "parq_ray_pe": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _f, _f, _i32, _i32, _i32, _i32, _i32, _i32,
@@ -94,9 +95,15 @@ SYMBOLS = {
     "parq_ray_pe_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "parq_ray_pe_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                        _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "parq_ray_pe_backward_workspace_bytes_flags": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "parq_ray_pe_backward_flags": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
+                                             _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "parq_parse_pred": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(_f), _i32, _i32, _vp, _vp, _vp]),
     "parq_set_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp,
                                 C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "parq_set_loss_scratch_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "parq_set_loss_flags": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp,
+                                      C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "parq_k_project_sample": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_f), _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "parq_k_camera_local": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "parq_k_linear": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),

@@ -89,6 +89,7 @@ struct Workspace {
     int64_t iter_begin, iter_end, stash;
     // backward scratch (training workspace only)
     int64_t g_a, g_b, g_c, g_pos, g_tmp, g_ffh, g_h1, g_h2, g_z, g_act, g_h3, g_qkv, g_emb, g_ref, g_D, g_bs, wT, g_kv, g_dqp, g_drop, kv_train, g_do, g_res, g_dq, g_Dall, g_kvmax, g_pack, g_mat;
+    int64_t g_det, g_det_floats;      // deterministic mode: scratch of the fixed-order reductions (common.hpp DetScratch), else empty
     int64_t g_set_stride;             // floats between two copies of the per-iteration backward scratch [g_a, g_drop]
     int g_sets;                       // copies of it: iterations of the batched backward run on that many streams at once
     bool bwd_batched;                 // cross-attention backward of all iterations in one launch (shared layer weights, split cache)
@@ -147,6 +148,7 @@ struct parq_ctx {
     bool seam_fusion = false;         // parq_set_seam_fusion: in-launch hand-offs of the chain (off by default since round 6: every dependent stage its own launch)
     bool bwd_batched_env = true;      // parq_set_backward_batched (the parity test compares the two settings)
     int bwd_streams = 8;              // parq_set_backward_streams: iterations of the chain backward in flight at once (1 = in turn)
+    bool deterministic = false;       // parq_set_deterministic: fixed-order reductions in parq_forward_train / parq_backward
     float dim_t_host[128];            // 10000^(2*(i//2)/128): uploaded by parq_pack_weights from this persistent buffer (no stream sync)
     hipStream_t cap_stream = nullptr;       // parq_forward_capture records on a stream of the handle's own
     hipStream_t aux_stream[7] = {nullptr};  // batched backward: iterations 1 .. g_sets-1 (mod g_sets) of a phase run here, 0 on the caller's stream
@@ -306,7 +308,8 @@ int carve_workspace(const parq_ctx* c, int B, int V, int h, int w, Workspace* ws
     // with its own copy of the scratch above (weight gradients meet in the arena through atomics).  Only where every dW product
     // takes the row-split kernel (its plain read-modify-write form and the 64 x 64-tile kernel are not safe for that).
     ws->g_set_stride = off - g_set_begin;
-    ws->g_sets = (bwd_batched_ok(c, N) && c->dh == 64 && (int64_t)F * C < (1 << 19) && (int64_t)3 * C * C < (1 << 19) && true)
+    // (deterministic mode: one stream — the fixed-order forms share one scratch and accumulate in place)
+    ws->g_sets = (!c->deterministic && bwd_batched_ok(c, N) && c->dh == 64 && (int64_t)F * C < (1 << 19) && (int64_t)3 * C * C < (1 << 19) && true)
                      ? (bwd_sets(c->I) < c->bwd_streams ? bwd_sets(c->I) : c->bwd_streams) : 1;
     take((ws->g_sets - 1) * ws->g_set_stride);
     // transposed weight copies of one layer: heads1 [C][NH1], heads2 2x[C][C], lin1^T [C][F], lin2^T [F][C],
@@ -337,6 +340,24 @@ int carve_workspace(const parq_ctx* c, int B, int V, int h, int w, Workspace* ws
         ws->g_mat = take(mat);
     }
     ws->g_kvmax = take(4);                            // [0] bits of max |dK|, |dV| (batched backward), [1] the derived scale
+    // deterministic mode: one scratch shared by the fixed-order forms (each consumes its partials before the next launch writes them):
+    // row-split slabs, the gather records of project + sample, dQ partials of the short-key attention backward, GroupNorm block sums
+    ws->g_det_floats = 0;
+    if (c->deterministic) {
+        int64_t dq = c->dh == 64 ? det_attn_dq_floats(B, c->H, (int)Q, (int)Q) : 0;
+        if (c->dh == 64 && N < 2048) {
+            const int64_t dqc = det_attn_dq_floats(B, c->H, (int)Q, (int)N);
+            dq = dqc > dq ? dqc : dq;
+        }
+        int64_t other = (int64_t)B * 2 * ceil_div64(Q * C, 1024) * 4;              // GroupNorm backward block sums
+        if (dq > other) other = dq;
+        if (ws->bwd_batched || (c->cache_mode() && C % 256 == 0)) {                // row ranges of the split-precision dW_kv / dQ slices
+            const int64_t kv = det_kvbwd_floats();
+            if (kv > other) other = kv;
+        }
+        ws->g_det_floats = det_scratch_floats(M * V, other);
+    }
+    ws->g_det = take(ws->g_det_floats);
     ws->train_total = off;
     return PARQ_OK;
 }
@@ -814,12 +835,15 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
         if (NH1 % 16 == 0) { a.Wp = TP ? TP + ar.heads1_w : nullptr; halfw(a, ar.heads1_w, c->nl == 1 ? 1 : 0); }
         a.gn_out_sums = gn1; a.gn_out_ncols = 2 * C; a.gn_out_group_cols = C; a.gn_out_rows_per_scene = Q; a.gn_out_ngroups = 2;
         HIPCHK(launch_linear(a, 1, s));
+        // deterministic training: the moments the GEMM added with float64 atomics, recomputed in a fixed order (parq_set_deterministic)
+        if (train && c->deterministic) HIPCHK(launch_gn_moments_det(wi + ws.h1, NH1, C, 2, Q, B, gn1, s));
         a = lin(wi + ws.h1, NH1, A + ar.heads2_w, C, nullptr, wi + ws.h2, 2 * C, M, C, C);
         a.gn_sums = gn1; a.gn_gamma = A + ar.gn1_g; a.gn_beta = A + ar.gn1_b; a.norm_eps = eps;
         a.gn_rows_per_scene = Q; a.gn_ngroups = 2;
         a.gX = C; a.gW = (int64_t)C * C; a.gY = C; a.gGamma = C; a.Wp = TP ? TP + ar.heads2_w : nullptr; halfw(a, ar.heads2_w);
         a.gn_out_sums = gn2; a.gn_out_ncols = C; a.gn_out_group_cols = C; a.gn_out_rows_per_scene = Q; a.gn_out_ngroups = 2;
         HIPCHK(launch_linear(a, 2, s));
+        if (train && c->deterministic) HIPCHK(launch_gn_moments_det(wi + ws.h2, 2 * C, C, 2, Q, B, gn2, s));
     }
     // K10: last head layers + box decode + reference point update + next sine embedding
     // (transformer_parq.py:242-279, 331-332)
@@ -1207,6 +1231,15 @@ int parq_set_backward_batched(parq_handle h, int32_t on) {
 int parq_set_backward_streams(parq_handle h, int32_t n) {
     if (!h || n < 1 || n > 8) return fail(PARQ_ERR_ARG, "parq_set_backward_streams: 1 <= n <= 8");
     h->bwd_streams = n;
+    return PARQ_OK;
+}
+
+/* Fixed-order reductions in parq_forward_train / parq_backward (include/parq_hip.h).  Changes the training workspace size and runs
+ * the backward on the caller's stream only (carve_workspace): call before parq_train_workspace_bytes. */
+int parq_set_deterministic(parq_handle h, int32_t on) {
+    if (!h) return fail(PARQ_ERR_ARG, "NULL handle");
+    if (on != 0 && on != 1) return fail(PARQ_ERR_ARG, "parq_set_deterministic: on must be 0 or 1");
+    h->deterministic = on != 0;
     return PARQ_OK;
 }
 
@@ -1722,6 +1755,9 @@ int parq_backward(parq_handle h, const parq_scene* scene, void* workspace, size_
     hipStream_t s = (hipStream_t)stream;
     const int64_t M = (int64_t)scene->B * h->Q;
     const int64_t N = (int64_t)scene->V * scene->h * scene->w;
+    if (h->deterministic && h->dh == 32) return fail(PARQ_ERR_ARG, "deterministic mode: no fixed-order attention backward at head dim 32");
+    // deterministic mode: every reduction below runs in its fixed-order form (common.hpp DetScratch), on the caller's stream only
+    DetScope det(h->deterministic ? wsp + ws.g_det : nullptr, ws.g_det_floats);
     HIPCHK(hipMemsetAsync(grad_arena, 0, (size_t)h->ar.rowmajor_total * sizeof(float), s));
     if (!ws.bwd_batched) HIPCHK(hipMemsetAsync(wsp + ws.g_kv, 0, (size_t)h->nl * scene->B * 2 * N * h->C * sizeof(float), s));
     if (d_tokens) HIPCHK(hipMemsetAsync(d_tokens, 0, (size_t)scene->B * N * h->C * sizeof(float), s));
@@ -2187,11 +2223,16 @@ int parq_ray_pe(const float* camera, const float* T_cp, const float* T_wp, const
     return PARQ_OK;
 }
 
-size_t parq_ray_pe_backward_workspace_bytes(int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C, int32_t num_samples) {
-    if (B < 1 || V < 1 || hh < 1 || ww < 1 || C < 1 || num_samples < 1) return 0;
+size_t parq_ray_pe_backward_workspace_bytes_flags(int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C, int32_t num_samples,
+                                                  int32_t flags) {
+    if (B < 1 || V < 1 || hh < 1 || ww < 1 || C < 1 || num_samples < 1 || (flags & ~PARQ_RAYPE_BWD_DETERMINISTIC)) return 0;
     const int64_t M = (int64_t)B * V * hh * ww, K1 = 3 * (int64_t)num_samples;
-    // points [M][K1] | d hidden [M][C] | W2^T [C][C]
-    return (size_t)(raype_align(M * K1) + raype_align(M * C) + raype_align((int64_t)C * C)) * sizeof(float);
+    // points [M][K1] | d hidden [M][C] | W2^T [C][C] | deterministic mode: the row-split slabs
+    const int64_t det = (flags & PARQ_RAYPE_BWD_DETERMINISTIC) ? raype_align(det_scratch_floats(0, 0)) : 0;
+    return (size_t)(raype_align(M * K1) + raype_align(M * C) + raype_align((int64_t)C * C) + det) * sizeof(float);
+}
+size_t parq_ray_pe_backward_workspace_bytes(int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C, int32_t num_samples) {
+    return parq_ray_pe_backward_workspace_bytes_flags(B, V, hh, ww, C, num_samples, 0);
 }
 
 int parq_ray_pe_backward(const float* camera, const float* T_cp, const float* T_wp, const float* T_wl, const float* w2,
@@ -2199,11 +2240,23 @@ int parq_ray_pe_backward(const float* camera, const float* T_cp, const float* T_
                          int32_t hh, int32_t ww, int32_t C, const float* d_tokens, const void* fwd_workspace, void* bwd_workspace,
                          size_t bwd_workspace_bytes, float* dw1, float* db1, float* dw2, float* db2, float* d_features_nchw,
                          parq_stream stream) {
+    return parq_ray_pe_backward_flags(camera, T_cp, T_wp, T_wl, w2, scale6_host, min_depth, max_depth, num_samples, B, V, hh, ww, C,
+                                      d_tokens, fwd_workspace, bwd_workspace, bwd_workspace_bytes, dw1, db1, dw2, db2, d_features_nchw, 0,
+                                      stream);
+}
+
+int parq_ray_pe_backward_flags(const float* camera, const float* T_cp, const float* T_wp, const float* T_wl, const float* w2,
+                               const float* scale6_host, float min_depth, float max_depth, int32_t num_samples, int32_t B, int32_t V,
+                               int32_t hh, int32_t ww, int32_t C, const float* d_tokens, const void* fwd_workspace, void* bwd_workspace,
+                               size_t bwd_workspace_bytes, float* dw1, float* db1, float* dw2, float* db2, float* d_features_nchw,
+                               int32_t flags, parq_stream stream) {
+    if (flags & ~PARQ_RAYPE_BWD_DETERMINISTIC) return fail(PARQ_ERR_ARG, "unknown ray-PE backward flags 0x%x", (unsigned)flags);
     if (!camera || !T_cp || !T_wp || !T_wl || !w2 || !scale6_host || !d_tokens || !fwd_workspace || !bwd_workspace || !dw1 || !db1 ||
         !dw2 || !db2)
         return fail(PARQ_ERR_ARG, "NULL argument");
     if (B < 1 || V < 1 || hh < 1 || ww < 1 || num_samples < 1 || (3 * num_samples) % 64 != 0 || C % 64 != 0) return fail(PARQ_ERR_ARG, "bad dims");
-    if (bwd_workspace_bytes < parq_ray_pe_backward_workspace_bytes(B, V, hh, ww, C, num_samples)) return fail(PARQ_ERR_WORKSPACE, "ray-PE backward workspace too small");
+    if (bwd_workspace_bytes < parq_ray_pe_backward_workspace_bytes_flags(B, V, hh, ww, C, num_samples, flags))
+        return fail(PARQ_ERR_WORKSPACE, "ray-PE backward workspace too small");
     const int64_t M64 = (int64_t)B * V * hh * ww;
     if (M64 > INT32_MAX) return fail(PARQ_ERR_ARG, "too many tokens");
     const int M = (int)M64, K1 = 3 * num_samples;
@@ -2212,6 +2265,9 @@ int parq_ray_pe_backward(const float* camera, const float* T_cp, const float* T_
     float* P = (float*)bwd_workspace;
     float* gHd = P + raype_align((int64_t)M * K1);
     float* W2T = gHd + raype_align((int64_t)M * C);
+    // PARQ_RAYPE_BWD_DETERMINISTIC: the column sums and weight products below take their fixed-order forms (common.hpp DetScratch)
+    const bool det_on = (flags & PARQ_RAYPE_BWD_DETERMINISTIC) != 0;
+    DetScope det(det_on ? W2T + raype_align((int64_t)C * C) : nullptr, det_on ? det_scratch_floats(0, 0) : 0);
     // tokens = features + relu(p W1^T + b1) W2^T + b2   (ray_positional_encoding.py:128-136, parq_lightning.py:75)
     HIPCHK(hipMemsetAsync(db2, 0, (size_t)C * sizeof(float), s));
     HIPCHK(hipMemsetAsync(db1, 0, (size_t)C * sizeof(float), s));
@@ -2251,13 +2307,32 @@ int parq_set_loss(const float* pred_logits, const float* center_unnormalized, co
                   const int32_t* t_label, const int32_t* t_sym, int32_t nmax, const int32_t* pairs, const float* pair_coef, int32_t P,
                   const float* row_weight, const float* class_weight, const float* loss_weight4_host, float* terms, float* g_logits,
                   float* g_center, float* g_size, float* g_ortho6d, int32_t* class_scratch, parq_stream stream) {
+    return parq_set_loss_flags(pred_logits, center_unnormalized, size_unnormalized, ortho6d, I, B, Q, num_classes, t_center, t_size, t_rot,
+                               t_label, t_sym, nmax, pairs, pair_coef, P, row_weight, class_weight, loss_weight4_host, terms, g_logits,
+                               g_center, g_size, g_ortho6d, class_scratch, 0, stream);
+}
+
+size_t parq_set_loss_scratch_bytes(int32_t I, int32_t B, int32_t Q, int32_t P, int32_t flags) {
+    if (I < 1 || B < 1 || Q < 1 || P < 0 || (flags & ~PARQ_SETLOSS_DETERMINISTIC)) return 0;
+    const int64_t rows = (int64_t)I * B * Q;
+    return (size_t)(rows + ((flags & PARQ_SETLOSS_DETERMINISTIC) ? setloss_part_floats(P, rows) : 0)) * 4;
+}
+
+int parq_set_loss_flags(const float* pred_logits, const float* center_unnormalized, const float* size_unnormalized, const float* ortho6d,
+                        int32_t I, int32_t B, int32_t Q, int32_t num_classes, const float* t_center, const float* t_size, const float* t_rot,
+                        const int32_t* t_label, const int32_t* t_sym, int32_t nmax, const int32_t* pairs, const float* pair_coef, int32_t P,
+                        const float* row_weight, const float* class_weight, const float* loss_weight4_host, float* terms, float* g_logits,
+                        float* g_center, float* g_size, float* g_ortho6d, int32_t* class_scratch, int32_t flags, parq_stream stream) {
+    if (flags & ~PARQ_SETLOSS_DETERMINISTIC) return fail(PARQ_ERR_ARG, "unknown set-loss flags 0x%x", (unsigned)flags);
     if (!pred_logits || !center_unnormalized || !size_unnormalized || !ortho6d || !t_center || !t_size || !t_rot || !t_label || !row_weight ||
         !class_weight || !loss_weight4_host || !terms || !g_logits || !g_center || !g_size || !g_ortho6d || !class_scratch)
         return fail(PARQ_ERR_ARG, "NULL argument");
     if (I < 1 || B < 1 || Q < 1 || num_classes < 2 || nmax < 1 || P < 0 || (P > 0 && (!pairs || !pair_coef))) return fail(PARQ_ERR_ARG, "bad dims");
+    // deterministic: the term partials live behind the I*B*Q class targets (parq_set_loss_scratch_bytes)
+    float* det_part = (flags & PARQ_SETLOSS_DETERMINISTIC) ? reinterpret_cast<float*>(class_scratch + (int64_t)I * B * Q) : nullptr;
     HIPCHK(launch_set_loss(pred_logits, center_unnormalized, size_unnormalized, ortho6d, I, B, Q, num_classes, t_center, t_size, t_rot,
                            t_label, t_sym, nmax, pairs, pair_coef, P, row_weight, class_weight, loss_weight4_host, num_classes - 1, terms,
-                           g_logits, g_center, g_size, g_ortho6d, class_scratch, (hipStream_t)stream));
+                           g_logits, g_center, g_size, g_ortho6d, class_scratch, (hipStream_t)stream, det_part));
     return PARQ_OK;
 }
 

@@ -1242,11 +1242,15 @@ hipError_t launch_attn_bwd(const float* q, int64_t q_batch, int64_t q_head, int6
     memset(a.lse_off, 0, sizeof(a.lse_off));
     for (int t = 0; t < kMaxBwdIters; ++t) a.seeds[t] = drop_seed;
     if (dh != 64 && dh != 32) return attn_bwd_materialised(a, dh, mat_scratch, s);
+    const DetScratch* det = det_scratch();
+    if (det && dh != 64) return hipErrorNotSupported;            // deterministic mode: dQ of the head-dim-32 kernel is float atomics
     dim3 grid(ceil_div(Lk, 256), B * H);
     static const int force = [] {
         const char* e = dev_env("PARQ_ATTN_BWD");            // "naive" / "mfma" (exact fp32 MFMA): debugging overrides of the split kernel
         return e ? (e[0] == 'n' ? 1 : 2) : 0;
     }();
+    if (det && force == 1) return hipErrorNotSupported;
+    if (det && Lk >= 2048 && !gq_part) return hipErrorInvalidValue;
     if (dh == 64 && force == 0 && Lk >= 2048 && absmax) {
         // split-precision kernel: dO scaled by a power of two so that max |dO| sits near 2^10 (keeps the low halves of the small
         // gradient values out of the fp16 subnormals); the scale is computed and consumed on the device (absmax[0] bits, absmax[1] scale)
@@ -1280,6 +1284,11 @@ hipError_t launch_attn_bwd(const float* q, int64_t q_batch, int64_t q_head, int6
             e != hipSuccess) return e;
         dim3 g2(ceil_div(Lk, KW), B * H);
         a.gq_part = big ? gq_part : nullptr;
+        if (!big && det) {            // deterministic mode: per-workgroup dQ partials summed in key-block order, as the long-key form does
+            if (det_attn_dq_floats(B, H, Lq, Lk) > det->floats) return hipErrorInvalidValue;
+            gq_part = det->base;      // (the reduce launch below reads the partials through this argument)
+            a.gq_part = gq_part;
+        }
         if (big) hipLaunchKernelGGL(attn_bwd_mfma_kernel<8>, g2, dim3(512), lds, s, a);
         else hipLaunchKernelGGL(attn_bwd_mfma_kernel<2>, g2, dim3(128), lds, s, a);
         if (a.gq_part) {
@@ -1555,6 +1564,11 @@ hipError_t launch_attn_bwd_batched(const float* q, const int64_t* q_off, int64_t
 }
 
 // scratch floats for the packed Q / dO tile images of launch_attn_bwd_batched
+// dQ partials of the short-key (Lk < 2048) head-dim-64 kernel in deterministic mode: one [pad32(Lq)][64] slot per key block of 64
+int64_t det_attn_dq_floats(int B, int H, int Lq, int Lk) {
+    return (int64_t)B * H * ceil_div(Lk, 64) * ((Lq + 31) & ~31) * 64;
+}
+
 size_t attn_bwd_pack_floats(int B, int H, int Lq, int n_it) {
     return (size_t)n_it * B * H * (((Lq + 31) & ~31) / 32) * kImgHalfs / 2;
 }

@@ -49,6 +49,8 @@ struct TnArgs {
     int accumulate;     // 0 overwrite, 1 add (the launch owns out), 2 add with atomics (launches on other streams add to out too)
     float* bias;        // optional: bias[n] (+)= sum_m A[m][n] for n >= bias_from (the bias gradient of the same layer), by the
     int bias_from;      // workgroups of the first k-tile from the A values they hold anyway (gemm_tn_kernel only)
+    float* part;        // deterministic form (row-split launch): [splits][N][K] tile partials, then [splits][N] bias partials, plain
+                        // stores summed in split order by slab_reduce_kernel; null = the atomics above
 };
 
 // The same contraction for LARGE outputs with FEW rows (the C = 1024 layers of the reference's shipped size: out 1024 x 1024 ..
@@ -228,7 +230,8 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs a) {
         const int n = n0 + tid;
         if (n < a.N && n >= a.bias_from) {
             const float v = (cred[0][tid] + cred[1][tid]) + (cred[2][tid] + cred[3][tid]);
-            if (gridDim.y > 1 || a.accumulate == 2) atomicAdd(a.bias + n, v);
+            if (a.part) a.part[(int64_t)gridDim.y * a.N * a.K + (int64_t)blockIdx.y * a.N + n] = v;
+            else if (gridDim.y > 1 || a.accumulate == 2) atomicAdd(a.bias + n, v);
             else a.bias[n] = a.accumulate ? a.bias[n] + v : v;
         }
     }
@@ -250,7 +253,8 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs a) {
             const int k = k0 + c4 + e;
             if (k < a.K) {
                 float* o = a.out + (int64_t)n * a.ldo + k;
-                if (gridDim.y > 1 || a.accumulate == 2) atomicAdd(o, sum[e]);   // row-split launch, or other streams add to the same out
+                if (a.part) a.part[((int64_t)blockIdx.y * a.N + n) * a.K + k] = sum[e];
+                else if (gridDim.y > 1 || a.accumulate == 2) atomicAdd(o, sum[e]);   // row-split launch, or other streams add to the same out
                 else *o = a.accumulate ? *o + sum[e] : sum[e];
             }
         }
@@ -276,6 +280,34 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X
         if (gridDim.y > 1) atomicAdd(out + n, t);
         else out[n] = accumulate ? out[n] + t : t;
     }
+}
+
+// deterministic form of colsum_kernel's row-split launch: part[blockIdx.y][n] = the same per-workgroup sum, plain stores
+__global__ __launch_bounds__(256) void colsum_part_kernel(const float* __restrict__ X, int64_t ldx, int M, int N, float* __restrict__ part) {
+    __shared__ float p[4][64];
+    const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int w = threadIdx.x >> 6;
+    const int chunk = (M + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int m_begin = (int)blockIdx.y * chunk;
+    const int m_end = m_begin + chunk < M ? m_begin + chunk : M;
+    float s = 0.f;
+    if (n < N)
+        for (int m = m_begin + w; m < m_end; m += 4) s += X[(int64_t)m * ldx + n];
+    p[w][threadIdx.x & 63] = s;
+    __syncthreads();
+    if (w == 0 && n < N) part[(int64_t)blockIdx.y * N + n] = p[0][threadIdx.x] + p[1][threadIdx.x] + p[2][threadIdx.x] + p[3][threadIdx.x];
+}
+
+// out[r][c] (+)= sum_{s = 0 .. S-1} part[s * stride + r * cols + c], the slabs added in index order (deterministic mode)
+__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ part, int S, int64_t stride, int R, int cols,
+                                                          float* __restrict__ out, int64_t ldo, int accumulate) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)R * cols) return;
+    const int r = (int)(i / cols), c = (int)(i - (int64_t)r * cols);
+    float t = 0.f;
+    for (int sl = 0; sl < S; ++sl) t += part[sl * stride + i];
+    float* o = out + (int64_t)r * ldo + c;
+    *o = accumulate ? *o + t : t;
 }
 
 // ------------------------------------------------------------------ y = a + b
@@ -368,6 +400,31 @@ __global__ __launch_bounds__(256) void ln_param_grad_kernel(const float* __restr
         atomicAdd(dbeta + c, p2[0][threadIdx.x] + p2[1][threadIdx.x] + p2[2][threadIdx.x] + p2[3][threadIdx.x]);
     }
 }
+// deterministic form: the same per-workgroup sums as plain stores, part[blockIdx.y][0 = gamma, 1 = beta][C]
+__global__ __launch_bounds__(256) void ln_param_part_kernel(const float* __restrict__ gy, const float* __restrict__ x,
+                                                            const float* __restrict__ stats, int M, int C, float* __restrict__ part) {
+    __shared__ float p1[4][64], p2[4][64];
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int w = threadIdx.x >> 6;
+    const int chunk = (M + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int m_begin = (int)blockIdx.y * chunk, m_end = m_begin + chunk < M ? m_begin + chunk : M;
+    float sg = 0.f, sb = 0.f;
+    if (c < C)
+        for (int m = m_begin + w; m < m_end; m += 4) {
+            const float g = gy[(int64_t)m * C + c];
+            const float xh = (x[(int64_t)m * C + c] - stats[(int64_t)m * 2]) * stats[(int64_t)m * 2 + 1];
+            sg += g * xh;
+            sb += g;
+        }
+    p1[w][threadIdx.x & 63] = sg;
+    p2[w][threadIdx.x & 63] = sb;
+    __syncthreads();
+    if (w == 0 && c < C) {
+        float* p = part + (int64_t)blockIdx.y * 2 * C;
+        p[c] = p1[0][threadIdx.x] + p1[1][threadIdx.x] + p1[2][threadIdx.x] + p1[3][threadIdx.x];
+        p[C + c] = p2[0][threadIdx.x] + p2[1][threadIdx.x] + p2[2][threadIdx.x] + p2[3][threadIdx.x];
+    }
+}
 
 // ------------------------------------------------------------------ GroupNorm(1, C) + ReLU over (rows_per_scene x C) blocks
 // forward moments come from the forward's slot accumulators: sums[(scene * ngroups + g) * kGnSlots + slot][2] (float64)
@@ -395,6 +452,9 @@ struct GnArgs {
     double* bsums;                     // [B][ngroups][2] backward sums (zeroed by the caller)
     float* gx; int64_t ldgx;           // gradient w.r.t. x
     float* dgamma; float* dbeta;       // accumulated
+    // deterministic form (null = atomics): bpart [B][ngroups][gridDim.x][2] per-workgroup backward sums, ppart [splits][2][ngroups*C]
+    // per-row-range dgamma | dbeta partials; both reduced in index order by the next launch
+    double* bpart; float* ppart;
 };
 
 // grid (ceil(rows_per_scene*C / 1024), ngroups, B)
@@ -446,9 +506,27 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(GnArgs a) {
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicAdd(a.bsums + ((int64_t)b * a.ngroups + g) * 2, red[0][0] + red[0][1] + red[0][2] + red[0][3]);
-        atomicAdd(a.bsums + ((int64_t)b * a.ngroups + g) * 2 + 1, red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+        if (a.bpart) {
+            double* p = a.bpart + (((int64_t)b * a.ngroups + g) * gridDim.x + blockIdx.x) * 2;
+            p[0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+            p[1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        } else {
+            atomicAdd(a.bsums + ((int64_t)b * a.ngroups + g) * 2, red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+            atomicAdd(a.bsums + ((int64_t)b * a.ngroups + g) * 2 + 1, red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+        }
     }
+}
+// deterministic form: bsums[b][g] = the workgroup sums of gn_bwd_reduce_kernel in workgroup order; one thread per (scene, group)
+__global__ void gn_bsums_reduce_kernel(const double* __restrict__ bpart, int nparts, int n, double* __restrict__ bsums) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s1 = 0.0, s2 = 0.0;
+    for (int j = 0; j < nparts; ++j) {
+        s1 += bpart[((int64_t)i * nparts + j) * 2];
+        s2 += bpart[((int64_t)i * nparts + j) * 2 + 1];
+    }
+    bsums[(int64_t)i * 2] = s1;
+    bsums[(int64_t)i * 2 + 1] = s2;
 }
 // pass 2: gx = rstd (gz gamma - S1/n - xhat S2/n)
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(GnArgs a) {
@@ -498,8 +576,16 @@ __global__ __launch_bounds__(256) void gn_param_grad_kernel(GnArgs a) {
     p2[w][threadIdx.x & 63] = sb;
     __syncthreads();
     if (w == 0 && c < a.C) {
-        atomicAdd(a.dgamma + g * a.C + c, p1[0][threadIdx.x] + p1[1][threadIdx.x] + p1[2][threadIdx.x] + p1[3][threadIdx.x]);
-        atomicAdd(a.dbeta + g * a.C + c, p2[0][threadIdx.x] + p2[1][threadIdx.x] + p2[2][threadIdx.x] + p2[3][threadIdx.x]);
+        const float vg = p1[0][threadIdx.x] + p1[1][threadIdx.x] + p1[2][threadIdx.x] + p1[3][threadIdx.x];
+        const float vb = p2[0][threadIdx.x] + p2[1][threadIdx.x] + p2[2][threadIdx.x] + p2[3][threadIdx.x];
+        if (a.ppart) {
+            float* p = a.ppart + (int64_t)blockIdx.z * 2 * a.ngroups * a.C;
+            p[g * a.C + c] = vg;
+            p[(int64_t)a.ngroups * a.C + g * a.C + c] = vb;
+        } else {
+            atomicAdd(a.dgamma + g * a.C + c, vg);
+            atomicAdd(a.dbeta + g * a.C + c, vb);
+        }
     }
 }
 
@@ -704,7 +790,186 @@ __global__ __launch_bounds__(1024) void sample_bwd_kernel(const float* __restric
     }
 }
 
+// deterministic mode, training forward: the GroupNorm moments of every (scene, group) block recomputed from the stored pre-norm
+// activations in a fixed order, replacing what the producing GEMM added into the kGnSlots slots with float64 atomics (order-dependent
+// wherever several tiles share a slot).  Slot sl of a block holds the rows sl, sl + kGnSlots, ... (thread-strided float64 sums over
+// the columns, fixed reduction tree); the readers add the slots in slot order.  grid (kGnSlots, ngroups, B)
+__global__ __launch_bounds__(256) void gn_moments_det_kernel(const float* __restrict__ x, int64_t ldx, int C, int ngroups,
+                                                             int rows_per_scene, double* __restrict__ sums) {
+    __shared__ double red[2][256];
+    const int sl = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
+    double s1 = 0.0, s2 = 0.0;
+    for (int r = sl; r < rows_per_scene; r += kGnSlots) {
+        const float* row = x + ((int64_t)b * rows_per_scene + r) * ldx + (int64_t)g * C;
+        for (int c = threadIdx.x; c < C; c += 256) {
+            const double v = (double)row[c];
+            s1 += v;
+            s2 += v * v;
+        }
+    }
+    red[0][threadIdx.x] = s1;
+    red[1][threadIdx.x] = s2;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + o];
+            red[1][threadIdx.x] += red[1][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double* dst = sums + (((int64_t)b * ngroups + g) * kGnSlots + sl) * 2;
+        dst[0] = red[0][0];
+        dst[1] = red[1][0];
+    }
+}
+
+// ------------------------------------------------------------------ project + sample backward, deterministic form (token gradient)
+// The scatter above adds every (scene, query, view) sample into 4 token rows with float atomics: the order in which several queries
+// meet in one token depends on timing.  Here the same contributions are GATHERED per destination token in query order:
+//   pass 1 (one thread per (scene, query)): the bilinear record of every view — the forward's geometry, bit for bit as above —
+//           rec[(bq * V + v) * 8] = {x0, y0 (int bits; x0 = INT_MIN: no sample), 1 / #valid views, -, wx0, wx1, wy0, wy1};
+//   pass 2 (one workgroup per 8 x 8 pixel tile of one view of one scene): the queries whose corners fall in the tile are compacted
+//           in query order into LDS (ballot prefix sums; chunks of kDetList queries added chunk after chunk), then every token of
+//           the tile adds its contributions in that order.  A workgroup owns its tokens: plain read-modify-write.
+constexpr int kDetTile = 8, kDetList = 1024;
+__global__ void sample_det_records_kernel(const double* __restrict__ T_cl, const float* __restrict__ cam, const float* __restrict__ ref,
+                                          ScaleBox sb, int BQ, int Q, int V, int h, int w, float* __restrict__ rec) {
+    const int bq = blockIdx.x * blockDim.x + threadIdx.x;
+    if (bq >= BQ) return;
+    const int b = bq / Q;
+    double P[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) P[i] = (double)ref[(int64_t)bq * 3 + i] * ((double)sb.hi[i] - (double)sb.lo[i]) + (double)sb.lo[i];
+    int total = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        const float inv_denom = 1.f / (float)(total > 0 ? total : 1);
+        for (int v = 0; v < V; ++v) {
+            const double* T = T_cl + ((int64_t)b * V + v) * 12;
+            const float* cm = cam + ((int64_t)b * V + v) * 6;
+            const double x = P[0] * T[0] + P[1] * T[1] + P[2] * T[2] + T[9];
+            const double y = P[0] * T[3] + P[1] * T[4] + P[2] * T[5] + T[10];
+            const double z = P[0] * T[6] + P[1] * T[7] + P[2] * T[8] + T[11];
+            const double eps = (double)1e-3f;
+            const double zc = z > eps ? z : eps;
+            const double u = (x / zc) * (double)cm[2] + (double)cm[4];
+            const double vv = (y / zc) * (double)cm[3] + (double)cm[5];
+            if (pass == 0) {
+                total += (z > eps && u >= 0.0 && u <= (double)cm[0] - 1.0 && vv >= 0.0 && vv <= (double)cm[1] - 1.0) ? 1 : 0;
+                continue;
+            }
+            float* r = rec + ((int64_t)bq * V + v) * 8;
+            const double fx0 = floor(u), fy0 = floor(vv);
+            if (!(fx0 >= -1.0 && fx0 <= (double)(w - 1) && fy0 >= -1.0 && fy0 <= (double)(h - 1))) {
+                r[0] = __int_as_float(INT32_MIN);
+                continue;
+            }
+            r[0] = __int_as_float((int)fx0);
+            r[1] = __int_as_float((int)fy0);
+            r[2] = inv_denom;
+            r[3] = 0.f;
+            r[4] = (float)(1.0 - (u - fx0));
+            r[5] = (float)(u - fx0);
+            r[6] = (float)(1.0 - (vv - fy0));
+            r[7] = (float)(vv - fy0);
+        }
+    }
+}
+// grid (tiles of the view, V, B), 256 threads
+__global__ __launch_bounds__(256) void sample_det_gather_kernel(const float* __restrict__ rec, const float* __restrict__ g_tgt, int Q, int V,
+                                                                int h, int w, int C, float* __restrict__ g_tokens) {
+    __shared__ float lrec[kDetList][8];
+    __shared__ int lq[kDetList];
+    __shared__ int wcnt[4];
+    const int v = blockIdx.y, b = blockIdx.z;
+    const int tx = ceil_div(w, kDetTile);
+    const int px0 = (int)(blockIdx.x % tx) * kDetTile, py0 = (int)(blockIdx.x / tx) * kDetTile;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t tok_base = (((int64_t)b * V + v) * h) * (int64_t)w;
+    for (int q0 = 0; q0 < Q; q0 += kDetList) {
+        int n = 0;                                        // entries of this chunk's list so far (workgroup-uniform)
+        for (int r0 = q0; r0 < q0 + kDetList && r0 < Q; r0 += 256) {
+            const int q = r0 + tid;
+            bool hit = false;
+            float rv[8];
+            if (q < Q) {
+                const float* r = rec + (((int64_t)b * Q + q) * V + v) * 8;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) rv[e] = r[e];
+                const int x0 = __float_as_int(rv[0]), y0 = __float_as_int(rv[1]);
+                // corners x0 .. x0 + 1, y0 .. y0 + 1 against the tile [px0, px0 + 8) x [py0, py0 + 8)
+                hit = x0 != INT32_MIN && x0 + 1 >= px0 && x0 < px0 + kDetTile && y0 + 1 >= py0 && y0 < py0 + kDetTile;
+            }
+            const unsigned long long m = __ballot(hit);
+            if (lane == 0) wcnt[wave] = __popcll(m);
+            __syncthreads();
+            int off = n;
+            for (int i = 0; i < wave; ++i) off += wcnt[i];
+            const int total = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+            if (hit) {
+                const int slot = off + __popcll(m & ((1ull << lane) - 1ull));
+#pragma unroll
+                for (int e = 0; e < 8; ++e) lrec[slot][e] = rv[e];
+                lq[slot] = q;
+            }
+            n += total;
+            __syncthreads();                              // wcnt is rewritten by the next round
+        }
+        for (int p = 0; p < kDetTile * kDetTile; ++p) {
+            const int px = px0 + (p & (kDetTile - 1)), py = py0 + p / kDetTile;
+            if (px >= w || py >= h) continue;
+            float* gt = g_tokens + (tok_base + (int64_t)py * w + px) * C;
+            for (int c = tid; c < C; c += 256) {
+                float acc = 0.f;
+                bool any = false;
+                for (int i = 0; i < n; ++i) {
+                    const int dx = px - __float_as_int(lrec[i][0]), dy = py - __float_as_int(lrec[i][1]);
+                    if ((unsigned)dx > 1u || (unsigned)dy > 1u) continue;
+                    const float gc = g_tgt[((int64_t)b * Q + lq[i]) * C + c] * lrec[i][2];
+                    acc += gc * lrec[i][6 + dy] * lrec[i][4 + dx];
+                    any = true;
+                }
+                if (any) gt[c] += acc;
+            }
+        }
+        __syncthreads();                                  // the list is rebuilt for the next chunk
+    }
+}
+
 }  // namespace
+
+// =============================================================================== deterministic-mode scratch
+namespace {
+thread_local DetScratch t_det;
+constexpr int64_t kDetSlabFloats = (int64_t)4 << 20;        // 16 MB: the row-split partials of any one launch (splits are capped to fit)
+// row ranges of a deterministic row-split launch: `want` capped so that `splits * per_split` floats fit the scratch
+int det_splits(int want, int64_t per_split) {
+    const int64_t fit = t_det.floats / (per_split > 0 ? per_split : 1);
+    return (int)(want < fit ? want : fit);
+}
+}  // namespace
+hipError_t launch_slab_reduce(const float* part, int S, int64_t stride, int R, int cols, float* out, int64_t ldo, int accumulate,
+                              hipStream_t s) {
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div64((int64_t)R * cols, 256)), dim3(256), 0, s, part, S, stride, R, cols,
+                       out, ldo, accumulate);
+    return hipGetLastError();
+}
+hipError_t launch_gn_moments_det(const float* x, int64_t ldx, int C, int ngroups, int rows_per_scene, int B, double* sums, hipStream_t s) {
+    hipLaunchKernelGGL(gn_moments_det_kernel, dim3(kGnSlots, ngroups, B), dim3(256), 0, s, x, ldx, C, ngroups, rows_per_scene, sums);
+    return hipGetLastError();
+}
+const DetScratch* det_scratch() { return t_det.base ? &t_det : nullptr; }
+DetScope::DetScope(float* base, int64_t floats) : saved(t_det) {
+    t_det.base = base;
+    t_det.floats = floats;
+}
+DetScope::~DetScope() { t_det = saved; }
+int64_t det_scratch_floats(int64_t sample_rows, int64_t dq_floats) {
+    int64_t n = kDetSlabFloats;
+    if (sample_rows * 8 > n) n = sample_rows * 8;
+    if (dq_floats > n) n = dq_floats;
+    return n;
+}
 
 // =============================================================================== launchers
 hipError_t launch_transpose(const float* src, int64_t ld_src, float* dst, int64_t ld_dst, int R, int Cc, hipStream_t s) {
@@ -715,7 +980,7 @@ hipError_t launch_gemm_tn(const float* A, int64_t lda, const float* B, int64_t l
                           int accumulate, hipStream_t s, float* bias, int bias_from) {
     TnArgs a;
     a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.out = out; a.ldo = ldo; a.M = M; a.N = N; a.K = K; a.accumulate = accumulate;
-    a.bias = bias; a.bias_from = bias_from;
+    a.bias = bias; a.bias_from = bias_from; a.part = nullptr;
     // large outputs from few rows (C = 1024 layers): 64 x 64 tiles with LDS-staged rows
     if ((int64_t)N * K >= (1 << 19) && M <= 4096) {
         hipLaunchKernelGGL(gemm_tn_tile64_kernel, dim3(ceil_div(N, 64) * ceil_div(K, 64)), dim3(256), 0, s, a);
@@ -737,6 +1002,17 @@ hipError_t launch_gemm_tn(const float* A, int64_t lda, const float* B, int64_t l
         if (splits > cap) splits = cap;
         if (splits < 1) splits = 1;
     }
+    if (t_det.base && splits > 1 && (int64_t)N * K + N > t_det.floats) splits = 1;     // no room for one partial: the plain form
+    if (t_det.base && splits > 1) {
+        // deterministic form: one [N][K] (+ bias [N]) partial per row range, summed in range order
+        splits = det_splits(splits, (int64_t)N * K + N);
+        a.part = t_det.base;
+        hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles, splits), dim3(256), 0, s, a);
+        hipError_t e = launch_slab_reduce(a.part, splits, (int64_t)N * K, N, K, out, ldo, accumulate ? 1 : 0, s);
+        if (e != hipSuccess || !bias || bias_from >= N) return e;
+        return launch_slab_reduce(a.part + (int64_t)splits * N * K + bias_from, splits, N, 1, N - bias_from, bias + bias_from, 0,
+                                  accumulate ? 1 : 0, s);
+    }
     hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles, splits), dim3(256), 0, s, a);
     return hipGetLastError();
 }
@@ -745,6 +1021,12 @@ hipError_t launch_colsum(const float* X, int64_t ldx, int M, int N, float* out, 
     if (accumulate && M >= 512) {                 // few columns, many rows: spread the rows over workgroups (float atomics)
         splits = M >= 8192 ? M / 1024 : M / 128;
         if (splits > 1024) splits = 1024;
+    }
+    if (t_det.base && splits > 1 && N > t_det.floats) splits = 1;
+    if (t_det.base && splits > 1) {
+        splits = det_splits(splits, N);
+        hipLaunchKernelGGL(colsum_part_kernel, dim3(ceil_div(N, 64), splits), dim3(256), 0, s, X, ldx, M, N, t_det.base);
+        return launch_slab_reduce(t_det.base, splits, N, 1, N, out, 0, accumulate, s);
     }
     hipLaunchKernelGGL(colsum_kernel, dim3(ceil_div(N, 64), splits), dim3(256), 0, s, X, ldx, M, N, out, accumulate);
     return hipGetLastError();
@@ -769,6 +1051,14 @@ hipError_t launch_ln_bwd(const float* gy, const float* x, const float* stats, co
     if (dgamma) {
         int splits = M / 64;
         splits = splits < 1 ? 1 : (splits > 64 ? 64 : splits);
+        if (t_det.base) {             // per-row-range partials, summed in range order into dgamma / dbeta
+            splits = det_splits(splits, 2 * (int64_t)C);
+            if (splits < 1) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(ln_param_part_kernel, dim3(ceil_div(C, 64), splits), dim3(256), 0, s, gy, x, stats, M, C, t_det.base);
+            hipError_t e = launch_slab_reduce(t_det.base, splits, 2 * (int64_t)C, 1, C, dgamma, 0, 1, s);
+            if (e != hipSuccess) return e;
+            return launch_slab_reduce(t_det.base + C, splits, 2 * (int64_t)C, 1, C, dbeta, 0, 1, s);
+        }
         hipLaunchKernelGGL(ln_param_grad_kernel, dim3(ceil_div(C, 64), splits), dim3(256), 0, s, gy, x, stats, M, C, dgamma, dbeta);
     }
     return hipGetLastError();
@@ -794,9 +1084,29 @@ hipError_t launch_gn_bwd(const float* x, int64_t ldx, const double* sums, const 
     a.rows_per_scene = rows_per_scene; a.eps = eps; a.gy = gy; a.ldgy = ldgy; a.gz = gz; a.ldgz = (int64_t)ngroups * C;
     a.bsums = bsums; a.gx = gx; a.ldgx = ldgx; a.dgamma = dgamma; a.dbeta = dbeta;
     const int B = ceil_div(M, rows_per_scene);
+    dim3 grid((unsigned)ceil_div64((int64_t)rows_per_scene * C, 1024), ngroups, B);
+    if (t_det.base) {
+        // deterministic form: per-workgroup sums (float64) and per-row-range dgamma / dbeta partials, each reduced in index order
+        if ((int64_t)B * ngroups * grid.x * 4 > t_det.floats) return hipErrorInvalidValue;
+        a.bpart = reinterpret_cast<double*>(t_det.base);
+        hipLaunchKernelGGL(gn_bwd_reduce_kernel, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(gn_bsums_reduce_kernel, dim3(ceil_div(B * ngroups, 64)), dim3(64), 0, s, a.bpart, (int)grid.x, B * ngroups, bsums);
+        hipLaunchKernelGGL(gn_bwd_apply_kernel, grid, dim3(256), 0, s, a);
+        if (!dgamma) return hipGetLastError();
+        int splits = M / 64;
+        splits = splits < 1 ? 1 : (splits > 64 ? 64 : splits);
+        const int64_t gc = (int64_t)ngroups * C;
+        splits = det_splits(splits, 2 * gc);
+        if (splits < 1) return hipErrorInvalidValue;
+        a.bpart = nullptr;
+        a.ppart = t_det.base;
+        hipLaunchKernelGGL(gn_param_grad_kernel, dim3(ceil_div(C, 64), ngroups, splits), dim3(256), 0, s, a);
+        hipError_t e = launch_slab_reduce(a.ppart, splits, 2 * gc, 1, (int)gc, dgamma, 0, 1, s);
+        if (e != hipSuccess) return e;
+        return launch_slab_reduce(a.ppart + gc, splits, 2 * gc, 1, (int)gc, dbeta, 0, 1, s);
+    }
     hipError_t e = hipMemsetAsync(bsums, 0, (size_t)B * ngroups * 2 * sizeof(double), s);
     if (e != hipSuccess) return e;
-    dim3 grid((unsigned)ceil_div64((int64_t)rows_per_scene * C, 1024), ngroups, B);
     hipLaunchKernelGGL(gn_bwd_reduce_kernel, grid, dim3(256), 0, s, a);
     hipLaunchKernelGGL(gn_bwd_apply_kernel, grid, dim3(256), 0, s, a);
     if (dgamma) {
@@ -831,6 +1141,18 @@ hipError_t launch_refpoint_bwd(const float* g_ref, const float* ref0, int B, int
 hipError_t launch_sample_bwd(const float* tokens, const double* T_cl, const float* cam, const float* ref, ScaleBox sb, int B, int V,
                              int h, int w, int C, int Q, const float* g_tgt, float* g_tokens, float* g_ref, hipStream_t s) {
     const int nwv = V < 16 ? V : 16;
+    if (t_det.base && g_tokens) {
+        // deterministic form: the coordinate gradient as above, the token gradient gathered per token in query order
+        if ((int64_t)B * Q * V * 8 > t_det.floats) return hipErrorInvalidValue;
+        if (g_ref)
+            hipLaunchKernelGGL(sample_bwd_kernel, dim3(B * Q), dim3(nwv * 64), 0, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, g_tgt,
+                               nullptr, g_ref);
+        hipLaunchKernelGGL(sample_det_records_kernel, dim3(ceil_div(B * Q, 64)), dim3(64), 0, s, T_cl, cam, ref, sb, B * Q, Q, V, h, w,
+                           t_det.base);
+        hipLaunchKernelGGL(sample_det_gather_kernel, dim3(ceil_div(w, kDetTile) * ceil_div(h, kDetTile), V, B), dim3(256), 0, s,
+                           t_det.base, g_tgt, Q, V, h, w, C, g_tokens);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(sample_bwd_kernel, dim3(B * Q), dim3(nwv * 64), 0, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, g_tgt, g_tokens,
                        g_ref);
     return hipGetLastError();

@@ -551,7 +551,8 @@ hipError_t launch_set_loss(const float* logits, const float* center, const float
                            const float* t_center, const float* t_size, const float* t_rot, const int32_t* t_label, const int32_t* t_sym,
                            int nmax, const int32_t* pairs, const float* coef, int P, const float* row_weight, const float* class_weight,
                            const float* w4, int background, float* terms, float* g_logits, float* g_center, float* g_size, float* g_o6,
-                           int32_t* cls, hipStream_t s);
+                           int32_t* cls, hipStream_t s, float* det_part = nullptr);   // det_part: setloss_part_floats(P, I*B*Q) floats
+inline int64_t setloss_part_floats(int64_t P, int64_t rows) { return 3 * ((P + 255) / 256) + (rows + 255) / 256; }
 // terms = 11: attention mode 4 with per-head tiers — head h as mode-4 stages, or in the split layout where bit h of safe_mask is set;
 // every (scene, head) region of the cache then spans ceil(N / 32) * 16 KB (the split layout's size)
 hipError_t launch_kvproj_split(const void* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N,
@@ -586,6 +587,30 @@ __device__ __forceinline__ void gn_mean_rstd(double S, double Q, double inv_cnt,
     rstd = (float)(1.0 / sqrt(var + (double)eps));
 }
 struct ScaleBox { float lo[3]; float hi[3]; };
+// ---- deterministic mode (parq_set_deterministic, PARQ_RAYPE_BWD_DETERMINISTIC).  While a DetScope is alive on the enqueuing host
+// thread, the backward launchers take their fixed-order forms: row-split reductions write one fp32 partial per row range into this
+// scratch (plain stores) and a second launch sums the partials in index order; the token-gradient scatter becomes a gather per
+// destination token.  Nothing changes while no scope is alive (the default path).
+struct DetScratch {
+    float* base = nullptr;            // device scratch, 16-byte aligned
+    int64_t floats = 0;
+};
+const DetScratch* det_scratch();      // nullptr outside a DetScope
+struct DetScope {
+    DetScratch saved;
+    DetScope(float* base, int64_t floats);
+    ~DetScope();
+};
+// scratch floats the fixed-order forms need for one call: the row-split slabs, plus `sample_rows` gather records (B*Q*V of the
+// project + sample backward) and `dq_floats` dQ partials of the short-key attention backward (det_attn_dq_floats)
+int64_t det_scratch_floats(int64_t sample_rows, int64_t dq_floats);
+int64_t det_attn_dq_floats(int B, int H, int Lq, int Lk);
+int64_t det_kvbwd_floats();            // row-range partials of kvproj_bwd_split_kernel (launch_kvproj_bwd_split, launch_tn_split_512x256)
+// out[r][c] (+)= sum over s of part[s * stride + r * cols + c], in s order
+hipError_t launch_slab_reduce(const float* part, int S, int64_t stride, int R, int cols, float* out, int64_t ldo, int accumulate,
+                              hipStream_t s);
+// sums[(scene * ngroups + g) * kGnSlots + slot][2] = the moments of rows slot, slot + kGnSlots, ... of x's (scene, group) block, fixed order
+hipError_t launch_gn_moments_det(const float* x, int64_t ldx, int C, int ngroups, int rows_per_scene, int B, double* sums, hipStream_t s);
 // ---- backward (backward.hip, attn_bwd.hip)
 hipError_t launch_transpose(const float* src, int64_t ld_src, float* dst, int64_t ld_dst, int R, int Cc, hipStream_t s);
 hipError_t launch_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, float* out, int64_t ldo, int M, int N, int K,

@@ -39,6 +39,8 @@ struct KvBwdArgs {
     float* db;                                   // [2C], +=
     const float* scale;                          // power of two applied to g
     int M, nsplit;
+    float* part;                                 // deterministic mode: [nsplit][512][256] partials of this launch's dW block, then
+                                                 // [nsplit][512] of db — plain stores, summed in row-range order; null = atomics
 };
 
 // position (in 16-bit units) of rows [8 q, 8 q + 8) of column c inside an operand image: 64 bytes per column, the 16-byte chunk
@@ -152,11 +154,20 @@ __global__ __launch_bounds__(512, 1) void kvproj_bwd_split_kernel(KvBwdArgs a) {
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
+            if (a.part) {
+                float* o = a.part + ((int64_t)split * 2 * kCols + slab * kCols + wn * 64 + i * 32) * kCols + wk * 128 + j * 32 + li;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[(int64_t)mfma32_row(r, lane) * kCols] = acc[i][j][r] * inv_sc;
+                continue;
+            }
             float* o = a.dW + (int64_t)(slab * kCols + wn * 64 + i * 32) * a.ldw + wk * 128 + j * 32 + li;
 #pragma unroll
             for (int r = 0; r < 16; ++r) atomicAdd(o + (int64_t)mfma32_row(r, lane) * a.ldw, acc[i][j][r] * inv_sc);
         }
-    if (isA && a.db) atomicAdd(a.db + slab * kCols + col, csum);
+    if (isA && a.db) {
+        if (a.part) a.part[(int64_t)a.nsplit * 2 * kCols * kCols + (int64_t)split * 2 * kCols + slab * kCols + col] = csum;
+        else atomicAdd(a.db + slab * kCols + col, csum);
+    }
 }
 
 // scale[0] = 2^(10 - exponent(max)) from the float bit pattern in bits[0] (1 when the maximum is 0 or not finite)
@@ -167,9 +178,36 @@ __global__ void pow2_scale_kernel(const unsigned int* __restrict__ bits, float* 
     scale[0] = ldexpf(1.f, 10 - ex);
 }
 
+// the row-split launch: in deterministic mode (common.hpp DetScratch) every row range writes its partial block and db slice, summed
+// into dW / db in range order behind it (one launch more; the partials of all ranges are 512 x 256 floats each)
+hipError_t launch_split_rows(KvBwdArgs a, int64_t M, size_t ldsb, hipStream_t s) {
+    const int steps = (int)((M + kTM - 1) / kTM);
+    int nsplit = device_num_cus() / 2;
+    if (nsplit < 1) nsplit = 1;
+    if (nsplit > steps) nsplit = steps;
+    const DetScratch* det = det_scratch();
+    const int64_t per = (int64_t)2 * kCols * kCols + 2 * kCols;
+    a.part = nullptr;
+    if (det) {
+        if (det->floats / per < nsplit) nsplit = (int)(det->floats / per);
+        if (nsplit < 1) return hipErrorInvalidValue;
+        a.part = det->base;
+    }
+    a.nsplit = nsplit;
+    hipLaunchKernelGGL(kvproj_bwd_split_kernel, dim3(2 * nsplit), dim3(512), ldsb, s, a);
+    if (!det) return hipGetLastError();
+    hipError_t e = launch_slab_reduce(a.part, nsplit, (int64_t)2 * kCols * kCols, 2 * kCols, kCols, a.dW, a.ldw, 1, s);
+    if (e != hipSuccess || !a.db) return e;
+    return launch_slab_reduce(a.part + (int64_t)nsplit * 2 * kCols * kCols, nsplit, 2 * kCols, 1, 2 * kCols, a.db, 0, 1, s);
+}
+
 }  // namespace
 
 bool kvproj_bwd_split_supported(int C) { return C == kCols; }
+int64_t det_kvbwd_floats() {
+    const int n = device_num_cus() / 2;
+    return (int64_t)(n < 1 ? 1 : n) * (2 * kCols * kCols + 2 * kCols);
+}
 
 // g [M][2C], tokens [M][C] -> dW [2C][C] (+=), db [2C] (+=).  absmax_bits: device word holding the bit pattern of max |g|
 // (non-negative floats order like unsigned integers); scale_scratch: one device float.
@@ -184,13 +222,7 @@ hipError_t launch_tn_split_512x256(const float* g, int64_t ldg, const float* x, 
     hipLaunchKernelGGL(pow2_scale_kernel, dim3(1), dim3(1), 0, s, absmax_bits, scale_scratch);
     KvBwdArgs a;
     a.g = g; a.ldg = ldg; a.x = x; a.ldx = ldx; a.dW = out; a.ldw = ldo; a.db = db; a.scale = scale_scratch; a.M = (int)M;
-    const int steps = (int)((M + kTM - 1) / kTM);
-    int nsplit = device_num_cus() / 2;
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > steps) nsplit = steps;
-    a.nsplit = nsplit;
-    hipLaunchKernelGGL(kvproj_bwd_split_kernel, dim3(2 * nsplit), dim3(512), ldsb, s, a);
-    return hipGetLastError();
+    return launch_split_rows(a, M, ldsb, s);
 }
 
 hipError_t launch_kvproj_bwd_split(const float* g, const float* tokens, int64_t M, int C, float* dW, float* db,
@@ -202,13 +234,7 @@ hipError_t launch_kvproj_bwd_split(const float* g, const float* tokens, int64_t 
     hipLaunchKernelGGL(pow2_scale_kernel, dim3(1), dim3(1), 0, s, absmax_bits, scale_scratch);
     KvBwdArgs a;
     a.g = g; a.ldg = 2 * C; a.x = tokens; a.ldx = C; a.dW = dW; a.ldw = C; a.db = db; a.scale = scale_scratch; a.M = (int)M;
-    const int steps = (int)((M + kTM - 1) / kTM);
-    int nsplit = device_num_cus() / 2;
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > steps) nsplit = steps;
-    a.nsplit = nsplit;
-    hipLaunchKernelGGL(kvproj_bwd_split_kernel, dim3(2 * nsplit), dim3(512), ldsb, s, a);
-    return hipGetLastError();
+    return launch_split_rows(a, M, ldsb, s);
 }
 
 }  // namespace parq

@@ -32,6 +32,8 @@ struct SetLossArgs {
     float* terms;                                      // [4]
     float *g_logits, *g_center, *g_size, *g_o6;
     int32_t* cls;                                      // [I*B*Q] scratch: class target per row
+    float* part;                                       // deterministic form: per-workgroup term partials (pairs: 3 per block, rows: 1),
+                                                       // summed in block order by setloss_terms_kernel; null = float atomics
     float ry_c[42], ry_s[42];                          // cos / sin of the candidates: 2-fold at 0, 4-fold at 2, 36-fold at 6
 };
 
@@ -174,7 +176,12 @@ __global__ __launch_bounds__(256) void setloss_pairs_kernel(SetLossArgs a) {
     lc = block_sum(lc, sh);
     ls = block_sum(ls, sh);
     lr = block_sum(lr, sh);
-    if (threadIdx.x == 0) { atomicAdd(a.terms + 0, lc); atomicAdd(a.terms + 1, ls); atomicAdd(a.terms + 2, lr); }
+    if (threadIdx.x == 0) {
+        if (a.part) {
+            float* p = a.part + 3 * blockIdx.x;
+            p[0] = lc; p[1] = ls; p[2] = lr;
+        } else { atomicAdd(a.terms + 0, lc); atomicAdd(a.terms + 1, ls); atomicAdd(a.terms + 2, lr); }
+    }
 }
 
 __global__ __launch_bounds__(256) void setloss_rows_kernel(SetLossArgs a) {
@@ -196,7 +203,23 @@ __global__ __launch_bounds__(256) void setloss_rows_kernel(SetLossArgs a) {
         for (int j = 0; j < a.ncls; ++j) g[j] = s * (expf(x[j] - lse) - (j == c ? 1.f : 0.f));
     }
     lk = block_sum(lk, sh);
-    if (threadIdx.x == 0) atomicAdd(a.terms + 3, lk);
+    if (threadIdx.x == 0) {
+        if (a.part) a.part[3 * ceil_div(a.P, 256) + blockIdx.x] = lk;
+        else atomicAdd(a.terms + 3, lk);
+    }
+}
+
+// deterministic form: terms[j] = the block partials of term j summed in block order (one thread per term)
+__global__ void setloss_terms_kernel(SetLossArgs a) {
+    const int j = threadIdx.x;
+    if (j >= 4) return;
+    const int nbp = ceil_div(a.P, 256), nbr = ceil_div(a.I * a.B * a.Q, 256);
+    float t = 0.f;
+    if (j < 3)
+        for (int i = 0; i < nbp; ++i) t += a.part[3 * i + j];
+    else
+        for (int i = 0; i < nbr; ++i) t += a.part[3 * nbp + i];
+    a.terms[j] = t;
 }
 
 }  // namespace
@@ -205,14 +228,14 @@ hipError_t launch_set_loss(const float* logits, const float* center, const float
                            const float* t_center, const float* t_size, const float* t_rot, const int32_t* t_label, const int32_t* t_sym,
                            int nmax, const int32_t* pairs, const float* coef, int P, const float* row_weight, const float* class_weight,
                            const float* w4, int background, float* terms, float* g_logits, float* g_center, float* g_size, float* g_o6,
-                           int32_t* cls, hipStream_t s) {
+                           int32_t* cls, hipStream_t s, float* det_part) {
     SetLossArgs a;
     a.logits = logits; a.center = center; a.size = size; a.o6 = o6;
     a.t_center = t_center; a.t_size = t_size; a.t_rot = t_rot; a.t_label = t_label; a.t_sym = t_sym;
     a.pairs = pairs; a.coef = coef; a.row_weight = row_weight; a.class_weight = class_weight;
     for (int i = 0; i < 4; ++i) a.w[i] = w4[i];
     a.I = I; a.B = B; a.Q = Q; a.ncls = ncls; a.nmax = nmax; a.P = P; a.background = background;
-    a.terms = terms; a.g_logits = g_logits; a.g_center = g_center; a.g_size = g_size; a.g_o6 = g_o6; a.cls = cls;
+    a.terms = terms; a.g_logits = g_logits; a.g_center = g_center; a.g_size = g_size; a.g_o6 = g_o6; a.cls = cls; a.part = det_part;
     // float32 roundings of cos / sin evaluated in double, as torch.tensor([[math.cos(t), ...]]) does (parq_amd/loss.py roty)
     const int ms[3] = {2, 4, 36}, offs[3] = {0, 2, 6};
     for (int c = 0; c < 3; ++c)
@@ -225,6 +248,7 @@ hipError_t launch_set_loss(const float* logits, const float* center, const float
     hipLaunchKernelGGL(setloss_init_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, s, a);
     if (P > 0) hipLaunchKernelGGL(setloss_pairs_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(setloss_rows_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, s, a);
+    if (det_part) hipLaunchKernelGGL(setloss_terms_kernel, dim3(1), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

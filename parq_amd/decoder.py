@@ -643,6 +643,12 @@ class PARQDecoder(_Tracked, nn.Module):
             # torch.use_deterministic_algorithms(True): the iterations of the chain backward run in turn with plain accumulation
             # instead of on eight streams with float atomics (include/parq_hip.h parq_set_backward_streams)
             _lib.check(_lib.load().parq_set_backward_streams(self._h, det), "parq_set_backward_streams")
+            # ... and every other reduction of the training step takes its fixed-order form (include/parq_hip.h
+            # parq_set_deterministic): the same bits on every run.  It enlarges the training workspace, hence the reset below
+            # (head dim 32 has no fixed-order attention backward: the handle stays in the default form, and the training entry
+            # points refuse or warn, _check_deterministic_training; inference is deterministic either way)
+            on = int(det == 1 and self.dim_in // self.num_heads != 32)
+            _lib.check(_lib.load().parq_set_deterministic(self._h, on), "parq_set_deterministic")
             self._bwd_streams_set = det
             self._train_ws = None
         if self._bwd_batched_set != bool(self.backward_batched):
@@ -691,6 +697,18 @@ class PARQDecoder(_Tracked, nn.Module):
         (their graphs are keyed apart in _enqueue_forward)."""
         cache = self.attention_mode != "fp32" and self.dim_in // self.num_heads in (64, 256)
         return 0 if cache or tt == 0 else 1
+
+    def _check_deterministic_training(self):
+        """torch.use_deterministic_algorithms(True) and a training configuration without a fixed-order backward: RuntimeError,
+        or a warning under warn_only=True, as torch does for its own nondeterministic operations."""
+        if not torch.are_deterministic_algorithms_enabled() or self.dim_in // self.num_heads != 32:
+            return
+        msg = ("parq_amd.PARQDecoder: training at head dim 32 (dim %d, %d heads) has no deterministic backward (its attention "
+               "backward adds dQ with float atomics), and torch.use_deterministic_algorithms(True) is set" % (self.dim_in, self.num_heads))
+        if not torch.is_deterministic_algorithms_warn_only_enabled():
+            raise RuntimeError(msg)
+        import warnings
+        warnings.warn(msg)
 
     def _handle_in_mode(self, mode):
         """The handle switched to `mode` without touching the user-facing ``attention_mode`` (the training entry points need
@@ -1085,6 +1103,8 @@ class PARQDecoder(_Tracked, nn.Module):
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_drop > 0 else 0
         outs = self._alloc_outputs((self.num_layers, sc.B, self.num_queries), dev)
         po = _lib.ParqOutputs(*[_lib.ptr(t) for t in outs])
+
+        self._check_deterministic_training()
 
         def enqueue():
             mode = self._train_mode()

@@ -238,16 +238,18 @@ class _SetLossFn(torch.autograd.Function):
         logits, ctr, siz, r6 = (t.detach().contiguous() for t in (logits, ctr, siz, r6))
         terms = torch.empty(4, dtype=torch.float32, device=dev)
         g = [torch.empty_like(t) for t in (logits, ctr, siz, r6)]
-        scratch = torch.empty(I * B * Q, dtype=torch.int32, device=dev)
         P = aux["P"]
+        # torch.use_deterministic_algorithms(True): the terms are summed in a fixed order (their partials follow the class targets)
+        flags = 1 if torch.are_deterministic_algorithms_enabled() else 0
+        scratch = torch.empty(lib.parq_set_loss_scratch_bytes(I, B, Q, P, flags) // 4, dtype=torch.int32, device=dev)
         host = aux["packed"]                               # int32 view: pairs [4][P] | coef [P] | row_weight [I*B*Q]
         base = host.data_ptr()
         w4 = (C.c_float * 4)(*[float(x) for x in aux["loss_weight"]])
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(lib.parq_set_loss(p(logits), p(ctr), p(siz), p(r6), I, B, Q, ncls, p(aux["t_center"]), p(aux["t_size"]), p(aux["t_rot"]),
-                                     p(aux["t_lab"]), p(aux["t_sym"]), aux["nmax"], C.c_void_p(base), C.c_void_p(base + 16 * P), P,
-                                     C.c_void_p(base + 20 * P), p(aux["class_weight"]), w4, p(terms), p(g[0]), p(g[1]), p(g[2]), p(g[3]),
-                                     p(scratch), _lib.stream_ptr()), "parq_set_loss")
+        _lib.check(lib.parq_set_loss_flags(p(logits), p(ctr), p(siz), p(r6), I, B, Q, ncls, p(aux["t_center"]), p(aux["t_size"]),
+                                           p(aux["t_rot"]), p(aux["t_lab"]), p(aux["t_sym"]), aux["nmax"], C.c_void_p(base),
+                                           C.c_void_p(base + 16 * P), P, C.c_void_p(base + 20 * P), p(aux["class_weight"]), w4, p(terms),
+                                           p(g[0]), p(g[1]), p(g[2]), p(g[3]), p(scratch), flags, _lib.stream_ptr()), "parq_set_loss_flags")
         ctx.grads = g
         c, s_, r, k = terms.unbind(0)
         return c, s_, r, k

@@ -47,7 +47,9 @@ class _RayPeFn(torch.autograd.Function):
         dev = cam.device
         lib = _lib.load()
         g = g_tokens.to(dtype=torch.float32).contiguous()
-        nbytes = lib.parq_ray_pe_backward_workspace_bytes(B, V, h, w, Cd, S)
+        # torch.use_deterministic_algorithms(True): the weight / bias gradients sum their row-range partials in a fixed order
+        flags = 1 if torch.are_deterministic_algorithms_enabled() else 0         # PARQ_RAYPE_BWD_DETERMINISTIC
+        nbytes = lib.parq_ray_pe_backward_workspace_bytes_flags(B, V, h, w, Cd, S, flags)
         bws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=dev)
         # the four parameter gradients live in ONE flat buffer, so data-parallel training averages them with a single
         # collective (train.py:103: DDP reduces every trainable parameter of the module, the encoder MLP included)
@@ -56,10 +58,11 @@ class _RayPeFn(torch.autograd.Function):
         dw1, db1, dw2, db2 = (t.view(shape) for t, shape in zip(flat.split(sizes), ((Cd, 3 * S), (Cd,), (Cd, Cd), (Cd,))))
         dfeat = torch.empty(B, V, Cd, h, w, device=dev) if ctx.want_feat else None
         w2 = mod.encoder[2].weight.detach().to(device=dev, dtype=torch.float32).contiguous()
-        _lib.check(lib.parq_ray_pe_backward(_lib.ptr(cam), _lib.ptr(T_cp), _lib.ptr(T_wp), _lib.ptr(T_wl), _lib.ptr(w2),
-                                            (C.c_float * 6)(*mod.ray_points_scale), mod.min_depth, mod.max_depth, S, B, V, h, w, Cd,
-                                            _lib.ptr(g), _lib.ptr(hold.ws), _lib.ptr(bws), bws.numel() * 4, _lib.ptr(dw1), _lib.ptr(db1),
-                                            _lib.ptr(dw2), _lib.ptr(db2), _lib.ptr(dfeat), _lib.stream_ptr()), "parq_ray_pe_backward")
+        _lib.check(lib.parq_ray_pe_backward_flags(_lib.ptr(cam), _lib.ptr(T_cp), _lib.ptr(T_wp), _lib.ptr(T_wl), _lib.ptr(w2),
+                                                  (C.c_float * 6)(*mod.ray_points_scale), mod.min_depth, mod.max_depth, S, B, V, h, w, Cd,
+                                                  _lib.ptr(g), _lib.ptr(hold.ws), _lib.ptr(bws), bws.numel() * 4, _lib.ptr(dw1),
+                                                  _lib.ptr(db1), _lib.ptr(dw2), _lib.ptr(db2), _lib.ptr(dfeat), flags, _lib.stream_ptr()),
+                   "parq_ray_pe_backward_flags")
         hold.consumed = True
         if mod.dp_all_reduce:
             from .parallel import all_reduce_mean_
