@@ -220,7 +220,8 @@ def _masked_mha(xq, xk, xv, in_w, in_b, out_w, out_b, H, pmask):
 
 @pytest.mark.parametrize("h,w,Hh,dim,mode", [(8, 10, 2, 128, None), (32, 40, 2, 128, None), (8, 10, 1, 128, None), (12, 14, 1, 256, None),
                                              (32, 36, 4, 256, None), (32, 38, 4, 256, None),   # these two: mode "split8" in training (opt-in; N = 2304 / 2432 = whole 64-key stages, the second not whole 256-key backward tiles)
-                                             (32, 36, 4, 256, "fp16"), (32, 38, 4, 256, "bf16")])   # the single-product dropout kernels on whole stages (flash_split8_kernel<..., DROP, 1, kind>)
+                                             (32, 36, 4, 256, "fp16"), (32, 38, 4, 256, "bf16"),   # the single-product dropout kernels on whole stages (flash_split8_kernel<..., DROP, 1, kind>)
+                                             (8, 10, 8, 256, None), (32, 40, 8, 256, None)])   # head dim 32: attn_bwd_kernel<32>, launch_self_attn
                                                                               # N = 160: exact-fp32 attention backward; N = 2560: split-precision
                                                                               # kernel; one head of 128 dims: materialised backward;
                                                                               # one head of 256 dims: the batched composition from split GEMMs
