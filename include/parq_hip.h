@@ -379,6 +379,28 @@ int parq_ray_pe(const float *camera, const float *T_camera_pseudoCam, const floa
                 int32_t V, int32_t hh, int32_t ww, int32_t C, const float *features_nchw, float *tokens_out,
                 int32_t flags, void *workspace, size_t workspace_bytes, parq_stream stream);
 
+/* ---- the FPN neck (model/resnet_fpn.py:62-91 of the reference) fused into the tokenisation --------------------------------
+ * level[l] (B*V, C/4, h[l], w[l]) float32 contiguous, l = 0..3: the feature maps are the four levels resized to h[layer] x w[layer]
+ * (torch's bilinear F.interpolate, align_corners=False) and concatenated along the channels — computed where they are read, the
+ * resized stack is never written.  parq_ray_pe_fpn is parq_ray_pe with the pyramid in place of features_nchw: the same
+ * workspace (parq_ray_pe_workspace_bytes_flags) and flags, except PARQ_RAYPE_NCHW_OUT (PARQ_ERR_ARG).  Geometry: C a multiple of
+ * 4 with C/4 a multiple of 16, every h, w >= 1, 0 <= layer <= 3, h[layer] x w[layer] = hh x ww; anything else is PARQ_ERR_ARG.
+ * parq_fpn_backward: from d loss / d tokens (B, V*h*w, C) it writes d level[l] (same shapes as the levels) for all four levels —
+ * the adjoint of the resize in gather form, the same fp32 weights, a fixed summation order and no atomics (bit-identical run to
+ * run).  The encoder gradients come from parq_ray_pe_backward(_flags) called with d_features_nchw = NULL. */
+typedef struct {
+    const float *level[4];
+    int32_t h[4], w[4];
+    int32_t layer;
+} parq_fpn_levels;
+int parq_ray_pe_fpn(const float *camera, const float *T_camera_pseudoCam, const float *T_world_pseudoCam,
+                    const float *T_world_local, const float *w1, const float *b1, const float *w2, const float *b2,
+                    const float *scale6_host, float min_depth, float max_depth, int32_t num_samples, int32_t B,
+                    int32_t V, int32_t hh, int32_t ww, int32_t C, const parq_fpn_levels *levels, float *tokens_out,
+                    int32_t flags, void *workspace, size_t workspace_bytes, parq_stream stream);
+int parq_fpn_backward(const float *d_tokens, int32_t B, int32_t V, int32_t C, const parq_fpn_levels *levels, float *const d_level[4],
+                      parq_stream stream);
+
 /* Backward of the encoding + tokenisation (training): given d loss / d tokens (B, V*h*w, C) it returns the gradients of
  * encoder.{0,2}.{weight,bias} and, optionally, d loss / d features (B, V, C, h, w).  `fwd_workspace` is the workspace the
  * forward call left behind (it holds the hidden layer); the geometry has no learnable part. */

@@ -5,6 +5,7 @@ Public surface mirrors the reference (ymingxie/PARQ):
     AddRayPE     (model/ray_positional_encoding.py:29)  ray-point PE (+ fused tokenisation)
     Pose, Camera (utils/wrappers.py:194,441)     tensor wrappers drivers pass in
     InFlight     (no counterpart: the reference calls its model once per batch, eval.py:46)  several forwards of one module in flight
+    ResnetFPN    (model/resnet_fpn.py:16)        wrapper of a user-supplied ResNet-FPN; its neck is fused into the tokenisation
 The compute lives in ``parq_amd/_C/libparq_hip.so`` (C ABI: include/parq_hip.h).
 """
 from .wrappers import Camera, Obb3D, Pose, TensorWrapper  # noqa: F401
@@ -21,6 +22,9 @@ def __getattr__(name):
     if name == "PARQ":
         from .module import PARQ
         return PARQ
+    if name == "ResnetFPN":
+        from .resnet_fpn import ResnetFPN
+        return ResnetFPN
     if name == "InFlight":
         from .inflight import InFlight
         return InFlight

@@ -45,6 +45,10 @@ class ParqOutputGrads(C.Structure):
                 ("size_unnormalized", C.c_void_p), ("ortho6d", C.c_void_p)]
 
 
+class ParqFpnLevels(C.Structure):
+    _fields_ = [("level", C.c_void_p * 4), ("h", C.c_int32 * 4), ("w", C.c_int32 * 4), ("layer", C.c_int32)]
+
+
 # every symbol include/parq_hip.h declares: (restype, argtypes)
 _vp, _i32, _i64, _sz, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float
 SYMBOLS = {
@@ -92,6 +96,9 @@ SYMBOLS = {
     "parq_ray_pe_workspace_bytes_flags": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "parq_ray_pe": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _f, _f, _i32, _i32, _i32, _i32, _i32, _i32,
                               _vp, _vp, _i32, _vp, _sz, _vp]),
+    "parq_ray_pe_fpn": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _f, _f, _i32, _i32, _i32, _i32, _i32, _i32,
+                                  C.POINTER(ParqFpnLevels), _vp, _i32, _vp, _sz, _vp]),
+    "parq_fpn_backward": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(ParqFpnLevels), C.POINTER(_vp), _vp]),
     "parq_ray_pe_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "parq_ray_pe_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                        _sz, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -2171,11 +2171,12 @@ size_t parq_ray_pe_workspace_bytes(int32_t B, int32_t V, int32_t hh, int32_t ww,
     return parq_ray_pe_workspace_bytes_flags(B, V, hh, ww, C, num_samples, 0);
 }
 
-int parq_ray_pe(const float* camera, const float* T_cp, const float* T_wp, const float* T_wl, const float* w1,
-                const float* b1, const float* w2, const float* b2, const float* scale6_host, float min_depth,
-                float max_depth, int32_t num_samples, int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C,
-                const float* features_nchw, float* tokens_out, int32_t flags, void* workspace, size_t workspace_bytes,
-                parq_stream stream) {
+// parq_ray_pe and parq_ray_pe_fpn: the feature maps come from features_nchw, or (fpn != nullptr) are gathered from a pyramid
+static int ray_pe_impl(const float* camera, const float* T_cp, const float* T_wp, const float* T_wl, const float* w1,
+                       const float* b1, const float* w2, const float* b2, const float* scale6_host, float min_depth,
+                       float max_depth, int32_t num_samples, int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C,
+                       const float* features_nchw, const FpnDev* fpn, float* tokens_out, int32_t flags, void* workspace,
+                       size_t workspace_bytes, parq_stream stream) {
     const int32_t nchw_out = flags & PARQ_RAYPE_NCHW_OUT;
     // 16-bit token rows (inference: the hidden layer is not kept for a backward; channels-last)
     const int out16 = (flags & PARQ_RAYPE_OUT_F16) ? kTokF16 : (flags & PARQ_RAYPE_OUT_BF16) ? kTokBF16 : kTokF32;
@@ -2211,15 +2212,74 @@ int parq_ray_pe(const float* camera, const float* T_cp, const float* T_wp, const
         // development: PARQ_RAYPE_TWO_KERNELS=1 runs the round-1 form (hidden tensor written and re-read) for A/B
         static const int two = [] { const char* e = dev_env("PARQ_RAYPE_TWO_KERNELS"); return e && e[0] == '1' ? 1 : 0; }();
         if (two && !Hd) return fail(PARQ_ERR_ARG, "the two-kernel form needs the hidden region (do not pass the no-hidden flag)");
+        if (two && fpn) return fail(PARQ_ERR_ARG, "the two-kernel development form of the ray-PE does not take pyramids");
         HIPCHK(launch_raype_fused(camera, T_cp, T_wp, T_wl, scale6_host, min_depth, max_depth, B, V, hh, ww, w1hi, w1lo, b1,
                                   w2hi, w2lo, b2, features_nchw, Hd, tabs, tabs + (int64_t)B * V * 12, tokens_out,
-                                  nchw_out ? 1 : 0, s, W2f, two | (cached ? 2 : 0), out16));
+                                  nchw_out ? 1 : 0, s, W2f, two | (cached ? 2 : 0), out16, fpn));
         return PARQ_OK;
     }
     if (nchw_out) return fail(PARQ_ERR_ARG, "NCHW output needs the fused path (C = 256, 64 samples)");
     HIPCHK(launch_raype_points(camera, T_cp, T_wp, T_wl, scale6_host, min_depth, max_depth, B, V, hh, ww, num_samples, P, s));
     HIPCHK(launch_gemm_split(P, K1, w1hi, w1lo, b1, Hd, C, M, C, K1, 1, nullptr, 1, s));
-    HIPCHK(launch_gemm_split(Hd, C, w2hi, w2lo, b2, tokens_out, C, M, C, C, 0, features_nchw, hh * ww, s, nullptr, 1.f, nullptr, 0, out16));
+    HIPCHK(launch_gemm_split(Hd, C, w2hi, w2lo, b2, tokens_out, C, M, C, C, 0, features_nchw, hh * ww, s, nullptr, 1.f, nullptr, 0, out16,
+                             fpn));
+    return PARQ_OK;
+}
+
+int parq_ray_pe(const float* camera, const float* T_cp, const float* T_wp, const float* T_wl, const float* w1,
+                const float* b1, const float* w2, const float* b2, const float* scale6_host, float min_depth,
+                float max_depth, int32_t num_samples, int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C,
+                const float* features_nchw, float* tokens_out, int32_t flags, void* workspace, size_t workspace_bytes,
+                parq_stream stream) {
+    return ray_pe_impl(camera, T_cp, T_wp, T_wl, w1, b1, w2, b2, scale6_host, min_depth, max_depth, num_samples, B, V, hh, ww, C,
+                       features_nchw, nullptr, tokens_out, flags, workspace, workspace_bytes, stream);
+}
+
+// the pyramid's geometry against the tokens' (B*V images of hh x ww, C channels): PARQ_OK or PARQ_ERR_ARG with a message
+static int fpn_check(const parq_fpn_levels* lv, int32_t hh, int32_t ww, int32_t C, FpnDev& f) {
+    if (!lv) return fail(PARQ_ERR_ARG, "NULL pyramid");
+    if (C < 4 || C % 4 != 0 || (C / 4) % 16 != 0)
+        return fail(PARQ_ERR_ARG, "pyramid: C = %d must be 4 levels of a multiple of 16 channels", (int)C);
+    if (lv->layer < 0 || lv->layer > 3) return fail(PARQ_ERR_ARG, "pyramid: layer %d outside 0..3", (int)lv->layer);
+    for (int l = 0; l < 4; ++l) {
+        if (!lv->level[l]) return fail(PARQ_ERR_ARG, "pyramid: level %d is NULL", l);
+        if (lv->h[l] < 1 || lv->w[l] < 1) return fail(PARQ_ERR_ARG, "pyramid: level %d is %d x %d", l, (int)lv->h[l], (int)lv->w[l]);
+        if ((int64_t)lv->h[l] * lv->w[l] * (C / 4) > INT32_MAX / 4) return fail(PARQ_ERR_ARG, "pyramid: level %d too large", l);
+        f.lv[l] = lv->level[l];
+        f.h[l] = lv->h[l];
+        f.w[l] = lv->w[l];
+    }
+    if (lv->h[lv->layer] != hh || lv->w[lv->layer] != ww)
+        return fail(PARQ_ERR_ARG, "pyramid: target level %d is %d x %d but the tokens are %d x %d per view", (int)lv->layer,
+                    (int)lv->h[lv->layer], (int)lv->w[lv->layer], (int)hh, (int)ww);
+    f.layer = lv->layer;
+    f.cl = C / 4;
+    return PARQ_OK;
+}
+
+int parq_ray_pe_fpn(const float* camera, const float* T_cp, const float* T_wp, const float* T_wl, const float* w1,
+                    const float* b1, const float* w2, const float* b2, const float* scale6_host, float min_depth,
+                    float max_depth, int32_t num_samples, int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C,
+                    const parq_fpn_levels* levels, float* tokens_out, int32_t flags, void* workspace, size_t workspace_bytes,
+                    parq_stream stream) {
+    if (flags & PARQ_RAYPE_NCHW_OUT) return fail(PARQ_ERR_ARG, "pyramid: channels-last tokens only (no NCHW output)");
+    FpnDev f;
+    if (int rc = fpn_check(levels, hh, ww, C, f); rc != PARQ_OK) return rc;
+    return ray_pe_impl(camera, T_cp, T_wp, T_wl, w1, b1, w2, b2, scale6_host, min_depth, max_depth, num_samples, B, V, hh, ww, C,
+                       nullptr, &f, tokens_out, flags, workspace, workspace_bytes, stream);
+}
+
+int parq_fpn_backward(const float* d_tokens, int32_t B, int32_t V, int32_t C, const parq_fpn_levels* levels, float* const d_level[4],
+                      parq_stream stream) {
+    if (!d_tokens || !d_level || !d_level[0] || !d_level[1] || !d_level[2] || !d_level[3]) return fail(PARQ_ERR_ARG, "NULL argument");
+    if (B < 1 || V < 1) return fail(PARQ_ERR_ARG, "bad dims");
+    if (!levels) return fail(PARQ_ERR_ARG, "NULL pyramid");
+    const int l = levels->layer;
+    if (l < 0 || l > 3) return fail(PARQ_ERR_ARG, "pyramid: layer %d outside 0..3", l);
+    FpnDev f;
+    if (int rc = fpn_check(levels, levels->h[l], levels->w[l], C, f); rc != PARQ_OK) return rc;
+    if ((int64_t)B * V * levels->h[l] * levels->w[l] * C > INT32_MAX) return fail(PARQ_ERR_ARG, "too many tokens");
+    HIPCHK(launch_fpn_backward(d_tokens, B * V, f, d_level, (hipStream_t)stream));
     return PARQ_OK;
 }
 

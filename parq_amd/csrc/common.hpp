@@ -566,6 +566,14 @@ hipError_t launch_widen_tokens(const void* src, float* dst, int64_t n, int tok_t
 hipError_t launch_cvt16_tokens(const void* src, void* dst, int64_t n, int kind, int tok_type, hipStream_t s);
 
 // raype.hip: ray-point positional encoding + tokenisation
+// The four FPN levels of a pyramid (parq_fpn_levels): level l is (B*V, cl, h[l], w[l]) fp32, resized bilinearly (torch's
+// align_corners=False formula) to the size of level `layer` and read as channels l*cl .. l*cl + cl - 1 of the feature maps.
+// launch_raype_fused / launch_gemm_split take one in place of `feat` (the one-pass kernel at C = 256, the generic epilogue).
+struct FpnDev {
+    const float* lv[4];
+    int h[4], w[4];
+    int layer, cl;
+};
 hipError_t launch_raype_points(const float* cam, const float* T_cp, const float* T_wp, const float* T_wl,
                                const float* scale6, float min_depth, float max_depth, int B, int V, int h, int w, int S,
                                float* P, hipStream_t s);
@@ -574,7 +582,11 @@ hipError_t launch_raype_fused(const float* cam, const float* T_cp, const float* 
                               const float* b1, const void* W2hi, const void* W2lo, const float* b2, const float* feat,
                               float* hidden, double* Tl, double* depth, float* out, int nchw_out, hipStream_t s,
                               void* W2f = nullptr, int two_kernels = 0,
-                              int out16 = kTokF32);      // out16: kTokF16 / kTokBF16 token rows (one-pass kernel, no hidden, channels-last)
+                              int out16 = kTokF32,       // out16: kTokF16 / kTokBF16 token rows (one-pass kernel, no hidden, channels-last)
+                              const FpnDev* fpn = nullptr);   // features gathered from a pyramid (feat == nullptr)
+// d level_l (B*V, cl, h[l], w[l]) for all four levels from d tokens (B*V*h*w, 4*cl): the adjoint of the bilinear gather in gather
+// form (a fixed summation order per texel, no atomics)
+hipError_t launch_fpn_backward(const float* d_tokens, int BV, const FpnDev& fpn, float* const* d_level, hipStream_t s);
 // GroupNorm(1, C) statistics from the float64 moments (sum, sum of squares) of a group, all in float64 (the variance is a difference
 // of two nearly equal numbers) with one reciprocal of the element count.  Used by the forward consumers and by the backward that
 // re-normalises from the same moments.  (An fp32 reciprocal square root was measured: the consumers' times did not move — the
@@ -679,7 +691,8 @@ hipError_t launch_gemm_split(const float* X, int64_t ldx, const void* Whi, const
                              int64_t ldy, int M, int N, int K, int relu, const float* feat, int hw, hipStream_t s,
                              const float* scale_dev = nullptr, float scale_mul = 1.f, const float* xscale_dev = nullptr,
                              int accumulate = 0,    // Y (+)= ((x * *xscale_dev) W^T) * scale_mul / *scale_dev + bias
-                             int out16 = kTokF32);  // Y as kTokF16 / kTokBF16 elements (rounded to nearest; not with accumulate)
+                             int out16 = kTokF32,   // Y as kTokF16 / kTokBF16 elements (rounded to nearest; not with accumulate)
+                             const FpnDev* fpn = nullptr);   // epilogue adds the pyramid's gathered features (feat == nullptr)
 
 // ------------------------------------------------------------------ elementwise / gather kernels
 hipError_t launch_camera_local(const float* T_cp, const float* T_wp, const float* T_wl, int B, int V,

@@ -14,6 +14,8 @@
 // tokens 197 MB written (a single fused kernel would keep p and the hidden layer in LDS; this
 // two-GEMM form is the first correct version).
 #include "common.hpp"
+#include <algorithm>
+#include <type_traits>
 #include <cstdlib>
 #include <cstdio>
 #include <vector>
@@ -120,10 +122,36 @@ struct GemmArgs {
     // optional: Y[m][n] += feat[(m / hw) * N * hw + n * hw + (m % hw)]   (NCHW feature maps, (B*V, C, h, w))
     const float* feat; int hw;
 };
+// the FPN instantiation's argument: the feature maps gathered from a pyramid instead of `feat`
+struct GemmFpnArgs : GemmArgs { FpnDev fpn; };
+
+// ---- FPN neck (model/resnet_fpn.py:62-91 of the reference): level l of the pyramid is resized to the size of level `layer` with
+// torch's upsample_bilinear2d (align_corners=False, output size given: scale = in / out in fp32) and read as channels
+// l*cl .. l*cl + cl - 1.  Nothing of the resized stack is written: every reader takes its four taps from the level itself.
+struct FpnTap { int i0, i1; float l0, l1; };
+__device__ __forceinline__ FpnTap fpn_tap(int in, int out, int dst) {
+    const float scale = (float)in / (float)out;
+    float src = scale * ((float)dst + 0.5f) - 0.5f;
+    src = src < 0.f ? 0.f : src;
+    FpnTap t;
+    t.i0 = (int)src;
+    t.i1 = t.i0 + (t.i0 < in - 1 ? 1 : 0);
+    t.l1 = src - (float)t.i0;
+    t.l0 = 1.f - t.l1;
+    return t;
+}
+// torch's order of operations: l0y (l0x a + l1x b) + l1y (l0x c + l1x d), a b on row i0, c d on row i1
+__device__ __forceinline__ float fpn_mix(const FpnTap& ty, const FpnTap& tx, float a, float b, float c, float d) {
+    return ty.l0 * (tx.l0 * a + tx.l1 * b) + ty.l1 * (tx.l0 * c + tx.l1 * d);
+}
+// v[l] for a wave-uniform l without indexing the kernel argument (selects, no private copy of the array)
+template <typename T>
+__device__ __forceinline__ T fpn_pick(const T (&v)[4], int l) { return l == 0 ? v[0] : l == 1 ? v[1] : l == 2 ? v[2] : v[3]; }
 
 // OUT: element type of Y (kTokF32, or kTokF16 / kTokBF16 rounded to nearest at the store: parq_ray_pe's 16-bit tokens)
-template <int OUT = kTokF32>
-__global__ __launch_bounds__(kThreads) void gemm_split_kernel(GemmArgs a) {
+// FPN: the epilogue adds the feature maps gathered from a.fpn (tokens of parq_ray_pe_fpn) instead of a.feat
+template <int OUT = kTokF32, bool FPN = false>
+__global__ __launch_bounds__(kThreads) void gemm_split_kernel(std::conditional_t<FPN, GemmFpnArgs, GemmArgs> a) {
     extern __shared__ __attribute__((aligned(16))) _Float16 lds[];      // A_hi | A_lo | W_hi | W_lo, each [128][64]
     _Float16* Ahi = lds;
     _Float16* Alo = lds + kBM * kBK;
@@ -256,7 +284,31 @@ __global__ __launch_bounds__(kThreads) void gemm_split_kernel(GemmArgs a) {
                 ot[(rt * 32 + mfma32_row(r, lane)) * 65 + ct * 32 + li] = acc[rt][ct][r];
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
-    if (a.feat) {
+    if constexpr (FPN) {
+        // lanes walk the 64 rows (pixels); the channels of one level share the taps of the pixel (a level boundary is wave-uniform)
+        const int m = m0 + wr * 64 + lane;
+        if (m < a.M) {
+            const FpnDev& f = a.fpn;
+            const int W = fpn_pick(f.w, f.layer), H = fpn_pick(f.h, f.layer);
+            const int img = m / a.hw, pix = m - img * a.hw;
+            const int y = pix / W, x = pix - y * W;
+            const int cbase = n0 + wc * 64, cend = min(cbase + 64, a.N);
+            for (int c = cbase; c < cend;) {
+                const int l = c / f.cl, ce = min(cend, (l + 1) * f.cl);
+                const int hl = fpn_pick(f.h, l), wl = fpn_pick(f.w, l), lhw = hl * wl;
+                const float* lp = fpn_pick(f.lv, l) + ((int64_t)img * f.cl + (c - l * f.cl)) * lhw;
+                if (l == f.layer) {
+                    for (; c < ce; ++c, lp += lhw) ot[lane * 65 + c - cbase] += lp[pix];
+                } else {
+                    const FpnTap ty = fpn_tap(hl, H, y), tx = fpn_tap(wl, W, x);
+                    const int o00 = ty.i0 * wl + tx.i0, o01 = ty.i0 * wl + tx.i1, o10 = ty.i1 * wl + tx.i0, o11 = ty.i1 * wl + tx.i1;
+                    for (; c < ce; ++c, lp += lhw) ot[lane * 65 + c - cbase] += fpn_mix(ty, tx, lp[o00], lp[o01], lp[o10], lp[o11]);
+                }
+            }
+        }
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+    } else if (a.feat) {
         // NCHW feature maps are pixel-contiguous: lanes walk the 64 rows (pixels) of one channel at a time
         const int m = m0 + wr * 64 + lane;
         if (m < a.M) {
@@ -315,6 +367,7 @@ struct RayFusedArgs {
     const float* feat;         // NCHW features (B*V, 256, h, w) or nullptr
     float* out;                // tokens [M][256] (nchw_out = 0) or encoding (B*V, 256, h, w) (nchw_out = 1)
     int nchw_out;
+    FpnDev fpn;                // one-pass FPN instantiation: the feature maps gathered from a pyramid (4 levels of 64 channels)
 };
 
 constexpr int kFC = 256;       // channels / hidden units of the fused path
@@ -656,9 +709,11 @@ __global__ void raype_pack_w2_kernel(const _Float16* __restrict__ hi, const _Flo
 // by the launcher), 32 feature tile requested one tile ahead instead of at the tile top, 64 all row stores before the generator,
 // 128 pose through per-lane loads, 256 W2 ring of three (tools/r05_raype_variants.sh, profiles/r05_raype.txt)
 // OUT: element type of the channels-last token rows (kTokF32, or kTokF16 / kTokBF16 rounded to nearest at the row store: 512-byte rows)
-template <bool KEEP, int PROBE = 0, bool NCHW = false, int OUT = kTokF32>
+// FPN: the feature tile is gathered from the pyramid a.fpn (a wave's 32 channels lie in level wave / 2)
+template <bool KEEP, int PROBE = 0, bool NCHW = false, int OUT = kTokF32, bool FPN = false>
 __global__ __launch_bounds__(kFThreads, 1) void raype_onepass_kernel(RayFusedArgs a, int ntiles, int P) {
     static_assert(OUT == kTokF32 || (!KEEP && !NCHW), "16-bit tokens: channels-last inference output only");
+    static_assert(!FPN || (!NCHW && PROBE == 0), "pyramids: channels-last tokens of the product kernel only");
     extern __shared__ __attribute__((aligned(16))) _Float16 lds[];
     __shared__ double dtab[64];
     constexpr int kStep = 2 * kFTM * 64;                                // halfs per k-step (hi + lo)
@@ -772,7 +827,48 @@ __global__ __launch_bounds__(kFThreads, 1) void raype_onepass_kernel(RayFusedArg
     // 32 distinct 64-bit addresses per lane cost 64 VGPRs of addresses and spilled the tile loop.  The descriptor's base is
     // the first image of the tile, so the 32-bit offsets stay small whatever the batch size.)
     f32x16 acc2[2];
+    auto load_features_fpn = [&](int tile) {
+        // level l = wave / 2 (64 channels a level): the target level is read as the NCHW maps are; any other level takes its four
+        // taps per value, and acc2 starts from their bilinear mix (the loads of one 4-channel group are mixed before the next)
+        const int bv0 = (tile * kFTM) / a.hw;
+        const int l = wave >> 1, cw = (wave & 1) * 32 + 4 * kh;
+        const int W = fpn_pick(a.fpn.w, a.fpn.layer), H = a.hw / W;
+        const int hl = fpn_pick(a.fpn.h, l), wl = fpn_pick(a.fpn.w, l), lhw = hl * wl;
+        const float* lbase = fpn_pick(a.fpn.lv, l) + (int64_t)bv0 * (kFC / 4) * lhw;
+        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)lbase, 0, 0x7fffffff, 0x00020000);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int m = tile * kFTM + t * 32 + li;
+            const bool ok = m < a.M;                                     // rows past the end read (and discard) pixel 0 of image bv0
+            int dbv = 0, pix = ok ? m - bv0 * a.hw : 0;
+            while (pix >= a.hw) { pix -= a.hw; ++dbv; }
+            const int rowoff = (dbv * (kFC / 4) + cw) * lhw;
+            if (l == a.fpn.layer) {
+                const int voff = (rowoff + pix) * 4;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int soff = (8 * (r >> 2) + (r & 3)) * lhw * 4;
+                    acc2[t][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0));
+                }
+            } else {
+                const int y = pix / W, x = pix - y * W;
+                const FpnTap ty = fpn_tap(hl, H, y), tx = fpn_tap(wl, W, x);
+                const int o00 = (rowoff + ty.i0 * wl + tx.i0) * 4, o01 = (rowoff + ty.i0 * wl + tx.i1) * 4;
+                const int o10 = (rowoff + ty.i1 * wl + tx.i0) * 4, o11 = (rowoff + ty.i1 * wl + tx.i1) * 4;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int soff = (8 * (r >> 2) + (r & 3)) * lhw * 4;
+                    const float va = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, o00, soff, 0));
+                    const float vb = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, o01, soff, 0));
+                    const float vc = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, o10, soff, 0));
+                    const float vd = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, o11, soff, 0));
+                    acc2[t][r] = fpn_mix(ty, tx, va, vb, vc, vd);
+                }
+            }
+        }
+    };
     auto load_features = [&](int tile) {
+        if constexpr (FPN) { load_features_fpn(tile); return; }
         const int bv0 = (tile * kFTM) / a.hw;                             // scalar: first image this tile touches
         const float* fbase = (a.feat ? a.feat : a.bias) + (int64_t)bv0 * kFC * a.hw;
         // no feature maps (AddRayPE.forward: the encoding alone): zero records -> every load returns 0, no branch per load
@@ -977,6 +1073,72 @@ __global__ __launch_bounds__(kFThreads, 1) void raype_onepass_kernel(RayFusedArg
 }
 
 
+// ------------------------------------------------------------------------------------------------
+// Adjoint of the FPN gather (parq_fpn_backward), gather form: thread (channel = lane, texel) of level l sums, in a fixed order,
+// the d tokens of every target pixel whose bilinear taps include the texel — the target level's map is a transpose.  Along each
+// axis the destination indices that read source index i (as i0 or i1) are those with i0 in {i - 1, i}: a contiguous range,
+// because i0(dst) is monotone (fpn_first_ge).  Same fp32 weights as the forward, no atomics: bit-identical run to run.
+// Block = (64 texels of one level image, 64 channels of level l); the 64 x 64 tile is transposed through LDS so that the NCHW
+// rows of d level are written texel-contiguous.
+struct FpnGrad { float* d[4]; };
+constexpr int kFbTex = 64;
+
+__device__ __forceinline__ int fpn_first_ge(int in, int out, int k) {    // first dst with i0(dst) >= k (out if none)
+    int lo = 0, hi = out;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (fpn_tap(in, out, mid).i0 >= k) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void fpn_backward_kernel(const float* __restrict__ g, FpnDev f, FpnGrad o, int C, int ncb) {
+    __shared__ float tile[64][kFbTex + 1];
+    const int l = blockIdx.y / ncb, cb = blockIdx.y - l * ncb;
+    const int hl = fpn_pick(f.h, l), wl = fpn_pick(f.w, l), lhw = hl * wl;
+    const int t0 = blockIdx.x * kFbTex;
+    if (t0 >= lhw) return;                                               // (the grid covers the largest level)
+    const int H = fpn_pick(f.h, f.layer), W = fpn_pick(f.w, f.layer);
+    const int img = blockIdx.z;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = cb * 64 + lane;
+    const float* gp = g + (int64_t)img * H * W * C + l * f.cl + (c < f.cl ? c : 0);
+    for (int k = wave; k < kFbTex; k += 4) {
+        const int t = t0 + k;
+        float acc = 0.f;
+        if (t < lhw) {
+            const int i = t / wl, j = t - i * wl;
+            if (l == f.layer) {
+                acc = gp[(int64_t)(i * W + j) * C];
+            } else {
+                const int y0 = fpn_first_ge(hl, H, i - 1), y1 = fpn_first_ge(hl, H, i + 1);
+                const int x0 = fpn_first_ge(wl, W, j - 1), x1 = fpn_first_ge(wl, W, j + 1);
+                for (int y = y0; y < y1; ++y) {
+                    const FpnTap ty = fpn_tap(hl, H, y);
+                    const float wy = (ty.i0 == i ? ty.l0 : 0.f) + (ty.i1 == i ? ty.l1 : 0.f);
+                    const float* gr = gp + (int64_t)y * W * C;
+                    float rs = 0.f;
+#pragma unroll 4
+                    for (int x = x0; x < x1; ++x) {                     // (unrolled: the loads of 4 columns in flight, sums in order)
+                        const FpnTap tx = fpn_tap(wl, W, x);
+                        const float wx = (tx.i0 == j ? tx.l0 : 0.f) + (tx.i1 == j ? tx.l1 : 0.f);
+                        rs += wx * gr[(int64_t)x * C];
+                    }
+                    acc += wy * rs;
+                }
+            }
+        }
+        tile[lane][k] = acc;
+    }
+    __syncthreads();
+    float* dl = fpn_pick(o.d, l);
+    const int t = t0 + lane;
+    for (int cc = wave; cc < 64; cc += 4) {
+        const int ch = cb * 64 + cc;
+        if (ch < f.cl && t < lhw) dl[((int64_t)img * f.cl + ch) * lhw + t] = tile[cc][lane];
+    }
+}
+
 }  // namespace
 
 hipError_t launch_raype_points(const float* cam, const float* T_cp, const float* T_wp, const float* T_wl,
@@ -997,8 +1159,9 @@ hipError_t launch_raype_fused(const float* cam, const float* T_cp, const float* 
                               float min_depth, float max_depth, int B, int V, int h, int w, const void* W1hi, const void* W1lo,
                               const float* b1, const void* W2hi, const void* W2lo, const float* b2, const float* feat,
                               float* hidden, double* Tl, double* depth, float* out, int nchw_out, hipStream_t s, void* W2f,
-                              int two_kernels, int out16) {
+                              int two_kernels, int out16, const FpnDev* fpn) {
     if (out16 != kTokF32 && (out16 != kTokF16 && out16 != kTokBF16)) return hipErrorInvalidValue;
+    if (fpn && (feat || nchw_out || (two_kernels & 1) || !W2f || fpn->cl != kFC / 4)) return hipErrorInvalidValue;   // one-pass rows only
     if (out16 != kTokF32 && (hidden || nchw_out || (two_kernels & 1) || !W2f)) return hipErrorInvalidValue;   // one-pass inference rows only
     const int S = 64;
     const int64_t M64 = (int64_t)B * V * h * w;
@@ -1034,6 +1197,19 @@ hipError_t launch_raype_fused(const float* cam, const float* T_cp, const float* 
                                reinterpret_cast<const _Float16*>(W2lo), reinterpret_cast<_Float16*>(W2f));
         a.W2f = reinterpret_cast<const _Float16*>(W2f); a.bias2 = b2;
         a.feat = feat; a.out = out; a.nchw_out = nchw_out;
+        if (fpn) {
+            a.fpn = *fpn;
+            auto go = [&](auto kern, DynLdsOnce& once) {
+                if (hipError_t e = once.ensure(reinterpret_cast<const void*>(kern), lds_f); e != hipSuccess) return e;
+                hipLaunchKernelGGL(kern, dim3(P), dim3(kFThreads), lds_f, s, a, ntiles, P);
+                return hipGetLastError();
+            };
+            static DynLdsOnce once_fk, once_f, once_fh, once_fb;
+            if (hidden) return go(raype_onepass_kernel<true, 0, false, kTokF32, true>, once_fk);
+            if (out16 == kTokF16) return go(raype_onepass_kernel<false, 0, false, kTokF16, true>, once_fh);
+            if (out16 == kTokBF16) return go(raype_onepass_kernel<false, 0, false, kTokBF16, true>, once_fb);
+            return go(raype_onepass_kernel<false, 0, false, kTokF32, true>, once_f);
+        }
         if (hidden && nchw_out) {
             static DynLdsOnce once_kn;
             if (hipError_t e = once_kn.ensure(reinterpret_cast<const void*>(&raype_onepass_kernel<true, 0, true>), lds_f); e != hipSuccess) return e;
@@ -1113,26 +1289,48 @@ hipError_t launch_raype_fused(const float* cam, const float* T_cp, const float* 
 // Y[M][N] = act(X[M][K] @ W^T + bias) (+ NCHW features); W given as fp16 hi/lo [N][K]; K % 64 == 0
 hipError_t launch_gemm_split(const float* X, int64_t ldx, const void* Whi, const void* Wlo, const float* bias, float* Y,
                              int64_t ldy, int M, int N, int K, int relu, const float* feat, int hw, hipStream_t s,
-                             const float* scale_dev, float scale_mul, const float* xscale_dev, int accumulate, int out16) {
+                             const float* scale_dev, float scale_mul, const float* xscale_dev, int accumulate, int out16,
+                             const FpnDev* fpn) {
     if (K % kBK != 0 || M < 1 || N < 1 || (relu && feat)) return hipErrorInvalidValue;
+    if (fpn && (feat || relu || accumulate || N != 4 * fpn->cl)) return hipErrorInvalidValue;
     if (out16 != kTokF32 && ((out16 != kTokF16 && out16 != kTokBF16) || accumulate)) return hipErrorInvalidValue;
     const size_t ldsb = 4 * 64 * 65 * sizeof(float);                    // 66560 B >= the 64 KB of operand staging
     GemmArgs a;
     a.X = X; a.ldx = ldx; a.Whi = reinterpret_cast<const _Float16*>(Whi); a.Wlo = reinterpret_cast<const _Float16*>(Wlo);
     a.bias = bias; a.Y = Y; a.ldy = ldy; a.M = M; a.N = N; a.K = K; a.relu = relu; a.feat = feat; a.hw = hw;
     a.scale_dev = scale_dev; a.scale_mul = scale_mul; a.xscale_dev = xscale_dev; a.accumulate = accumulate;
+
     const int nct = ceil_div(N, kBN), nrt = ceil_div(M, kBM);
     const int64_t wgs = (int64_t)ceil_div(nrt, 8) * 8 * nct;
     if (wgs > 0x7fffffffLL) return hipErrorInvalidValue;
-    auto launch = [&](auto kern, DynLdsOnce& once) {
+    auto launch = [&](auto kern, DynLdsOnce& once, const auto& args) {
         if (hipError_t e = once.ensure(reinterpret_cast<const void*>(kern), ldsb); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(kThreads), ldsb, s, a);
+        hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(kThreads), ldsb, s, args);
         return hipGetLastError();
     };
+    if (fpn) {
+        GemmFpnArgs fa;
+        static_cast<GemmArgs&>(fa) = a;
+        fa.fpn = *fpn;
+        static DynLdsOnce once_f, once_fh, once_fb;
+        if (out16 == kTokF16) return launch(gemm_split_kernel<kTokF16, true>, once_fh, fa);
+        if (out16 == kTokBF16) return launch(gemm_split_kernel<kTokBF16, true>, once_fb, fa);
+        return launch(gemm_split_kernel<kTokF32, true>, once_f, fa);
+    }
     static DynLdsOnce once, once_h, once_b;
-    if (out16 == kTokF16) return launch(gemm_split_kernel<kTokF16>, once_h);
-    if (out16 == kTokBF16) return launch(gemm_split_kernel<kTokBF16>, once_b);
-    return launch(gemm_split_kernel<kTokF32>, once);
+    if (out16 == kTokF16) return launch(gemm_split_kernel<kTokF16>, once_h, a);
+    if (out16 == kTokBF16) return launch(gemm_split_kernel<kTokBF16>, once_b, a);
+    return launch(gemm_split_kernel<kTokF32>, once, a);
+}
+
+hipError_t launch_fpn_backward(const float* d_tokens, int BV, const FpnDev& fpn, float* const* d_level, hipStream_t s) {
+    int tiles = 1;
+    for (int l = 0; l < 4; ++l) tiles = std::max(tiles, ceil_div(fpn.h[l] * fpn.w[l], kFbTex));
+    const int ncb = ceil_div(fpn.cl, 64);
+    FpnGrad o;
+    for (int l = 0; l < 4; ++l) o.d[l] = d_level[l];
+    hipLaunchKernelGGL(fpn_backward_kernel, dim3(tiles, 4 * ncb, BV), dim3(256), 0, s, d_tokens, fpn, o, 4 * fpn.cl, ncb);
+    return hipGetLastError();
 }
 
 }  // namespace parq

@@ -4,6 +4,8 @@
 that is in scope this round: ray positional encoding + tokenisation + decoder.  The 2-D backbone is not
 part of the decoder path (torchvision ResNet-FPN): pass any callable that adds
 ``all_features`` (B,T,C,h,w) and ``camera_feature`` to the batch, or feed batches that already carry them.
+``backbone2d=parq_amd.ResnetFPN(resnet_fpn)`` adds the four FPN levels instead (``fpn_features``, ``fpn_layer``): their
+resize + concat is fused into the tokenisation (AddRayPE.tokens_from_pyramid).
 Lightning is used as the base class only when it is importable (it is not on the GPU image).
 """
 from __future__ import annotations
@@ -56,13 +58,21 @@ class PARQ(_Base):
     def forward(self, batch, batch_idx=0):
         if self.backbone2d is not None:
             batch = self.backbone2d(batch)
-        feats = batch["all_features"]
-        # encoding + `images_feat = features + encoding` + both einops rearranges, fused (parq_lightning.py:72-85)
-        input_tokens = self.add_ray_pe.tokens(feats, batch["camera_feature"], batch["T_camera_pseudoCam"],
-                                              batch["T_world_pseudoCam"], batch["T_world_local"], dtype=self.token_dtype)
+        if "fpn_features" in batch:
+            # ResnetFPN's four levels: the neck's resize + concat (model/resnet_fpn.py:62-91) fused into the tokenisation
+            levels, layer = batch["fpn_features"], batch["fpn_layer"]
+            input_tokens = self.add_ray_pe.tokens_from_pyramid(levels, layer, batch["camera_feature"], batch["T_camera_pseudoCam"],
+                                                               batch["T_world_pseudoCam"], batch["T_world_local"],
+                                                               dtype=self.token_dtype)
+            feat_hw = tuple(levels[layer].shape[-2:])
+        else:
+            feats = batch["all_features"]
+            # encoding + `images_feat = features + encoding` + both einops rearranges, fused (parq_lightning.py:72-85)
+            input_tokens = self.add_ray_pe.tokens(feats, batch["camera_feature"], batch["T_camera_pseudoCam"],
+                                                  batch["T_world_pseudoCam"], batch["T_world_local"], dtype=self.token_dtype)
+            feat_hw = tuple(feats.shape[-2:])
         outputs = self.box3d_decoder(input_tokens, batch["camera_feature"], batch["T_camera_pseudoCam"],
-                                     batch["T_world_pseudoCam"], batch["T_world_local"],
-                                     feat_hw=tuple(feats.shape[-2:]))
+                                     batch["T_world_pseudoCam"], batch["T_world_local"], feat_hw=feat_hw)
         if "obbs_padded" in batch:
             self.box3d_decoder.settle_deferred()        # (InFlight) the loss reads the outputs on the host: a flagged forward is re-run first
             losses = self.box3d_decoder.loss(outputs, batch["obbs_padded"], batch["T_world_local"], batch["sym"])
@@ -100,7 +110,8 @@ class PARQ(_Base):
     def training_step(self, batch, batch_idx):
         """model/parq_lightning.py:97-100.  In train mode the decoder forward is an autograd node whose backward is the HIP
         backward chain, and AddRayPE.tokens is an autograd node too: the decoder and the ray-PE
-        encoder receive gradients, and d loss / d features is handed to whatever produced ``all_features``."""
+        encoder receive gradients, and d loss / d features is handed to whatever produced ``all_features`` (or the four
+        ``fpn_features`` levels)."""
         losses, _ = self.forward(batch, batch_idx)
         return losses["total_loss"]
 
