@@ -432,6 +432,19 @@ int parq_parse_pred(const float *center, const float *size, const float *ortho6d
                     int32_t Q, int32_t num_classes, const float *track_scale6_host, int32_t for_vis, int32_t enable_nms,
                     float *obbs_out, unsigned char *mask_out, parq_stream stream);
 
+/* ---- oriented-box IoU of the evaluation tracker (parq_amd/f1_eval.py iou3d; utils/f1_eval.py:77-175), one lane per pair ------
+ * The IoU matrices of S independent segments in ONE launch; segment s is (n_a[s] boxes of boxes_a) x (n_b[s] boxes of boxes_b).
+ * boxes_a (n_a_total, 8, 3), boxes_b (n_b_total, 8, 3): float64 corners as f1_eval.canonical() orders and rotates them.
+ * segments (S, 5) int64 on the DEVICE: [first box in boxes_a, n_a, first box in boxes_b, n_b, first element in the outputs]; the
+ * output offsets are the running sum of n_a * n_b in segment order and total_pairs is its end.  iou3d_out (total_pairs) float64: the
+ * row-major (n_a, n_b) matrices of the 3-D IoU one after another; iou2d_out: the footprint IoU likewise, or NULL.  Values: the host
+ * routine's, branch for branch in float64 without contraction — (0, 0) for a NaN in either box, for an intersection polygon of
+ * fewer than three vertices and for one of area <= 1e-14 * max(footprint areas); footprint value NaN where the 2-D union is 0.
+ * S = 0 or total_pairs = 0 (empty segments only) is valid and launches nothing.  A negative count, a NULL array that is needed or
+ * more than 2^31 - 1 workgroups of 64 pairs: PARQ_ERR_ARG.  A table row that reaches outside the box arrays writes nothing. */
+int parq_obb_iou(const double *boxes_a, int64_t n_a_total, const double *boxes_b, int64_t n_b_total, const int64_t *segments,
+                 int32_t S, int64_t total_pairs, double *iou3d_out, double *iou2d_out, parq_stream stream);
+
 /* ---- set loss for a given matching (model/parq_decoder.py:264-370), three launches --------------------------------------------
  * The reference matches predictions to boxes per (iteration, scene) on the host (utils/matcher.py: scipy LSAP + a capped random
  * neighbourhood) and then evaluates ~100 tiny tensor operations per step, forward and in autograd.  Given the matching, this entry

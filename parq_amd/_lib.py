@@ -106,6 +106,7 @@ SYMBOLS = {
     "parq_ray_pe_backward_flags": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
                                              _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "parq_parse_pred": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(_f), _i32, _i32, _vp, _vp, _vp]),
+    "parq_obb_iou": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _vp]),
     "parq_set_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp,
                                 C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "parq_set_loss_scratch_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),

@@ -2362,6 +2362,17 @@ int parq_parse_pred(const float* center, const float* size, const float* ortho6d
     return PARQ_OK;
 }
 
+int parq_obb_iou(const double* boxes_a, int64_t n_a_total, const double* boxes_b, int64_t n_b_total, const int64_t* segments, int32_t S,
+                 int64_t total_pairs, double* iou3d_out, double* iou2d_out, parq_stream stream) {
+    if (S < 0 || total_pairs < 0 || n_a_total < 0 || n_b_total < 0) return fail(PARQ_ERR_ARG, "parq_obb_iou: negative count");
+    if (S == 0 || total_pairs == 0) return PARQ_OK;                     // nothing to compute: no launch
+    if (!boxes_a || !boxes_b || !segments || !iou3d_out) return fail(PARQ_ERR_ARG, "parq_obb_iou: NULL argument");
+    if (n_a_total < 1 || n_b_total < 1) return fail(PARQ_ERR_ARG, "parq_obb_iou: %lld pairs of no boxes", (long long)total_pairs);
+    if ((total_pairs + 63) / 64 > (int64_t)INT32_MAX) return fail(PARQ_ERR_ARG, "parq_obb_iou: too many pairs");
+    HIPCHK(launch_obb_iou(boxes_a, boxes_b, segments, S, total_pairs, n_a_total, n_b_total, iou3d_out, iou2d_out, (hipStream_t)stream));
+    return PARQ_OK;
+}
+
 int parq_set_loss(const float* pred_logits, const float* center_unnormalized, const float* size_unnormalized, const float* ortho6d,
                   int32_t I, int32_t B, int32_t Q, int32_t num_classes, const float* t_center, const float* t_size, const float* t_rot,
                   const int32_t* t_label, const int32_t* t_sym, int32_t nmax, const int32_t* pairs, const float* pair_coef, int32_t P,

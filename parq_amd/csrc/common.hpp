@@ -687,6 +687,9 @@ hipError_t launch_attn_bwd_rowdot(const float* dO, const float* O, int64_t batch
 hipError_t launch_parse_pred(const float* center, const float* size, const float* rot6, const float* prob, int B, int Q, int ncls,
                              int num_semcls, const float* track_scale6, int for_vis, int enable_nms, float* obbs,
                              unsigned char* mask, hipStream_t s);
+// obb_iou.hip: the tracker's oriented-box IoU, S segments of (n_a x n_b) pairs in one launch (total >= 1)
+hipError_t launch_obb_iou(const double* boxes_a, const double* boxes_b, const int64_t* seg, int S, int64_t total, int64_t n_a_total,
+                          int64_t n_b_total, double* iou3, double* iou2, hipStream_t s);
 hipError_t launch_gemm_split(const float* X, int64_t ldx, const void* Whi, const void* Wlo, const float* bias, float* Y,
                              int64_t ldy, int M, int N, int K, int relu, const float* feat, int hw, hipStream_t s,
                              const float* scale_dev = nullptr, float scale_mul = 1.f, const float* xscale_dev = nullptr,

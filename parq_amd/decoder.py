@@ -305,6 +305,11 @@ class _TrainFn(torch.autograd.Function):
 class PARQDecoder(_Tracked, nn.Module):
     """Drop-in for ``model.parq_decoder.PARQDecoder`` (forward path)."""
 
+    # True (on the class or on one module): update_metrics / compute_metrics take the trackers' oriented-box IoU matrices from the
+    # device, one parq_obb_iou launch per step and per compute_metrics, instead of the host's pair-by-pair loop; same tracks and
+    # metrics (parq_amd/f1_eval.py)
+    metrics_on_device = False
+
     def __init__(self, cfg):
         super().__init__()
         T = cfg.TRANSFORMER
@@ -1481,7 +1486,8 @@ class PARQDecoder(_Tracked, nn.Module):
     @torch.no_grad()
     def update_metrics(self, out_dict, obbs_padded, T_world_local, scene_name=None):
         """model/parq_decoder.py:426-459: boxes + keep-mask of the last iteration (``parse_pred``, on the device), box corners
-        in world coordinates, then one step of every tracker (host side, parq_amd/f1_eval.py)."""
+        in world coordinates, then one step of every tracker (parq_amd/f1_eval.py: tracks and assignment on the host, the
+        oriented-box IoU matrices there too, or from one parq_obb_iou launch per step when ``metrics_on_device``)."""
         from .loss import parse_target
         from .wrappers import Pose, raw
         assert raw(obbs_padded).ndim == 3, tuple(raw(obbs_padded).shape)
@@ -1491,6 +1497,7 @@ class PARQDecoder(_Tracked, nn.Module):
         out["scene_name"] = scene_name
         out["pred_corners_world"] = Pose(raw(T_world_local)).transform(obbs.T_world_object.transform(obbs.bb3corners_object))
         for calc in self.metrics_calculator:
+            calc.iou_device = obbs.device if self.metrics_on_device else None
             calc.step(out, targets)
 
     def log_images(self, out_dict, obbs_padded, Ts_world_pseudoCam, Ts_world_local, T_camera_pseudoCam, rgb_img=None, calib_rgb=None,
@@ -1504,6 +1511,10 @@ class PARQDecoder(_Tracked, nn.Module):
     def compute_metrics(self):
         metrics = {}
         for calc in self.metrics_calculator:
+            if not self.metrics_on_device:
+                calc.iou_device = None
+            elif calc.iou_device is None:                              # no update_metrics yet in this mode: the module's device
+                calc.iou_device = next(self.parameters()).device
             metrics.update(calc.compute_metrics())
         return metrics
 

@@ -5,8 +5,15 @@ Mirrors the behaviour of the reference's ``F1Calculator`` (utils/f1_eval.py:254-
 a Hungarian assignment on oriented-box IoU (utils/f1_eval.py:293-352), ground truth likewise (:416-471), and at the end every
 track is greedily matched to a same-class ground-truth box at IoU thresholds 0.25 / 0.5 / 0.7 (:36-62, :473-502).
 
-This is host code on NumPy + scipy's LSAP (as in the reference): the work is a few hundred box pairs per snippet.
-The device side of the evaluation path (box building, validity window, NMS) is ``PARQDecoder.parse_pred``.
+The track store and scipy's LSAP stay on the host (as in the reference).  The cost matrix of the assignment does not have to: the
+host ``iou3d`` is a Python polygon clip plus a few NumPy calls per pair, about 0.1 ms each whether the boxes overlap or not, so one
+snippet's 30 detections x 80 tracks cost a quarter of a second, two orders of magnitude more than the decoder's forward, and
+``compute_metrics`` pays for every prediction x ground-truth pair once per threshold.  ``F1Calculator(..., iou_device="cuda")``
+takes the matrices from ``parq_obb_iou`` instead (csrc/obb_iou.hip: the same routine in float64, one lane per pair): ``step``
+packs the (detections, tracks) pairs of every scene of the batch, predictions and ground truth together, into one launch, and
+``compute_metrics`` all scenes' prediction x ground-truth pairs into one that every threshold reads.  ``iou_device=None`` (the
+default) is the host loop.  The device side of the rest of the evaluation path (box building, validity window, NMS) is
+``PARQDecoder.parse_pred``.
 
 The oriented IoU follows the reference's convention (utils/f1_eval.py:46-48,77-107): corners are re-ordered with
 [4,0,1,5,7,3,2,6] and rotated by +90 deg about x, the first four re-ordered corners (taken in reverse) are the footprint
@@ -109,10 +116,12 @@ def _iou_matrix(dets, trks) -> np.ndarray:
     return m
 
 
-def _associate(dets, trks, iou_thresh):
+def _associate(dets, trks, iou_thresh, iou=None):
     """Hungarian assignment on IoU; returns (matches [(det, trk)], unmatched detection indices in the reference's order:
-    never-assigned ones first, then assigned pairs whose IoU is under the threshold)."""
-    iou = _iou_matrix(dets, trks)
+    never-assigned ones first, then assigned pairs whose IoU is under the threshold).  `iou`: the float32 matrix when it has
+    been computed already (the batched path), else it is filled here pair by pair."""
+    if iou is None:
+        iou = _iou_matrix(dets, trks)
     rows, cols = linear_sum_assignment(-iou)
     assigned = set(int(r) for r in rows)
     unmatched = [d for d in range(len(dets)) if d not in assigned]
@@ -125,9 +134,22 @@ def _associate(dets, trks, iou_thresh):
     return matches, unmatched
 
 
-def count_matches(total_gts, total_preds, total_tps, predictions, gts, threshold):
+def count_matches(total_gts, total_preds, total_tps, predictions, gts, threshold, iou=None):
     """Greedy true-positive count of one scene (utils/f1_eval.py:36-62).  As in the reference, a prediction is not
-    consumed by its first match: it scores once for EVERY still-unused same-class ground-truth box it overlaps."""
+    consumed by its first match: it scores once for EVERY still-unused same-class ground-truth box it overlaps.
+    `iou`: the float64 (len(gts), len(predictions)) matrix when it has been computed already (the batched path)."""
+    if iou is not None:
+        for g in gts:
+            total_gts[g[0]] += 1
+        used = set()
+        for j, pred in enumerate(predictions):
+            cls = pred[0]
+            total_preds[cls] += 1
+            for i, g in enumerate(gts):
+                if g[0] == cls and iou[i, j] > threshold and i not in used:
+                    used.add(i)
+                    total_tps[cls] += 1
+        return
     used = set()
     cg = [canonical(g[1]) for g in gts]
     for g in gts:
@@ -163,16 +185,118 @@ def f1_from_counts(gts, preds, tps, verbose=False):
     return acc, rec, f1
 
 
+def canonical_stack(entries) -> np.ndarray:
+    """(n, 8, 3) float64 canonical() corners of a list of entries [class, corners, ...]."""
+    if not len(entries):
+        return np.zeros((0, 8, 3), np.float64)
+    return np.stack([canonical(e[1]) for e in entries])
+
+
+def host_iou_backend(segments):
+    """IoU source of the batched path on the host `iou3d`: segments = [(A (n_a,8,3), B (n_b,8,3)) canonical corners] ->
+    [float64 (n_a, n_b) 3-D IoU].  For tests of the packing and wave logic; the device backend is DeviceIoU."""
+    out = []
+    for A, B in segments:
+        m = np.zeros((len(A), len(B)), np.float64)
+        for i, a in enumerate(A):
+            for j, b in enumerate(B):
+                m[i, j] = iou3d(a, b)[0]
+        out.append(m)
+    return out
+
+
+def pack_segments(segments):
+    """One host buffer for one upload: (float64 buffer, offsets in doubles of boxes_a / boxes_b / the table, n_a_total, n_b_total,
+    (S, 5) int64 table [a_off, n_a, b_off, n_b, out_off], total pairs).  The table's bits ride along in the float64 buffer."""
+    S = len(segments)
+    table = np.zeros((S, 5), np.int64)
+    a_off = b_off = o_off = 0
+    for s, (A, B) in enumerate(segments):
+        assert A.shape[1:] == (8, 3) and B.shape[1:] == (8, 3), (A.shape, B.shape)
+        table[s] = (a_off, len(A), b_off, len(B), o_off)
+        a_off += len(A)
+        b_off += len(B)
+        o_off += len(A) * len(B)
+    parts = [np.ascontiguousarray(A, np.float64).reshape(-1) for A, _ in segments]
+    parts += [np.ascontiguousarray(B, np.float64).reshape(-1) for _, B in segments]
+    parts.append(table.reshape(-1).view(np.float64))
+    buf = np.concatenate(parts) if parts else np.zeros(0, np.float64)
+    return buf, (0, a_off * 24, (a_off + b_off) * 24), a_off, b_off, table, o_off
+
+
+def split_matrices(flat, table):
+    """The per-segment (n_a, n_b) views of the concatenated row-major matrices."""
+    return [flat[o:o + na * nb].reshape(na, nb) for _, na, _, nb, o in table.tolist()]
+
+
+class DeviceIoU:
+    """IoU source of the batched path on the device: one upload, one parq_obb_iou launch, one copy back per call.
+    `launches` counts the kernel launches (a call whose segments are all empty launches nothing), `pairs` the IoUs computed."""
+
+    def __init__(self, device):
+        import torch
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("iou_device must be a CUDA device or None, got %r" % (device,))
+        self.launches = 0
+        self.pairs = 0
+
+    def __call__(self, segments, footprint=False):
+        """[float64 (n_a, n_b) 3-D IoU] per segment; with footprint=True a pair (3-D list, footprint list)."""
+        import ctypes as C
+
+        import torch
+
+        from . import _lib
+        buf, (oa, ob, ot), na, nb, table, total = pack_segments(segments)
+        if total == 0:
+            zeros = [np.zeros((int(r[1]), int(r[3])), np.float64) for r in table]
+            return (zeros, [z.copy() for z in zeros]) if footprint else zeros
+        with torch.cuda.device(self.device):
+            dev = torch.from_numpy(buf).to(self.device)
+            out = torch.empty((2 if footprint else 1, total), dtype=torch.float64, device=self.device)
+            base = dev.data_ptr()
+            _lib.check(_lib.load().parq_obb_iou(C.c_void_p(base + 8 * oa), na, C.c_void_p(base + 8 * ob), nb, C.c_void_p(base + 8 * ot),
+                                                len(segments), total, C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(out[1].data_ptr()) if footprint else None,
+                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), "parq_obb_iou")
+            self.launches += 1
+            self.pairs += total
+            host = out.cpu().numpy()
+        m3 = split_matrices(host[0], table)
+        return (m3, split_matrices(host[1], table)) if footprint else m3
+
+
 class F1Calculator:
     """Accumulates per-scene prediction and ground-truth tracks over snippets; ``compute_metrics`` returns
-    {"<thr>_accuracy", "<thr>_recall", "<thr>_f1"} for thr in f1_iou_thresh."""
+    {"<thr>_accuracy", "<thr>_recall", "<thr>_f1"} for thr in f1_iou_thresh.
 
-    def __init__(self, conf_thresh, f1_iou_thresh=(0.25, 0.5, 0.7), verbose=False):
+    ``iou_device``: None (default) fills every IoU matrix on the host, pair by pair; a CUDA device makes ``step`` and
+    ``compute_metrics`` take them from one ``parq_obb_iou`` launch each (see the module docstring).  ``iou_backend``: any
+    callable [(A, B) canonical corner stacks] -> [float64 (n_a, n_b)] to run the batched path on instead (``host_iou_backend``)."""
+
+    def __init__(self, conf_thresh, f1_iou_thresh=(0.25, 0.5, 0.7), verbose=False, iou_device=None, iou_backend=None):
         self.f1_iou_thresh = list(f1_iou_thresh)
         self.conf_thresh = conf_thresh
         self.iou_thresh = 0.1
         self.verbose = verbose
+        self._iou_device = None
+        self.iou_backend = iou_backend
+        self.iou_device = iou_device
         self.reset()
+
+    @property
+    def iou_device(self):
+        return self._iou_device
+
+    @iou_device.setter
+    def iou_device(self, device):
+        if device is None:
+            if isinstance(self.iou_backend, DeviceIoU):
+                self.iou_backend = None
+        elif not (isinstance(self.iou_backend, DeviceIoU) and str(self.iou_backend.device) == str(device)):
+            self.iou_backend = DeviceIoU(device)
+        self._iou_device = device
 
     def reset(self):
         self.preds = {}
@@ -185,8 +309,33 @@ class F1Calculator:
         dets = self.parse_predictions(outputs, self.conf_thresh)
         gts = self.make_gt_list(gt_list)
         names = outputs["scene_name"]
+        if self.iou_backend is not None:
+            return self._step_batched(dets, gts, names)
         self.matching_pred(dets, names)
         self.matching_gt(gts, names)
+
+    def _step_batched(self, dets, gts, names):
+        """The sequential loops' result with the IoU matrices of a whole batch from one call of the backend.  A scene's k-th
+        visit within the batch associates with what its (k-1)-th left, so the batch is cut into waves of distinct names
+        (normally one); the prediction and the ground-truth store do not see each other and share a wave's call."""
+        seen = {}
+        waves = []
+        for b, name in enumerate(names):
+            k = seen.get(name, 0)
+            seen[name] = k + 1
+            if k == len(waves):
+                waves.append([])
+            waves[k].append(b)
+        for wave in waves:
+            jobs = []                                     # (store, this wave's entries, their scene names): predictions, ground truth
+            for store, entries in ((self.preds, dets), (self.gts, gts)):
+                mine = [b for b in wave if b < len(entries)]
+                jobs.append((store, [entries[b] for b in mine], [names[b] for b in mine]))
+            segments = [(canonical_stack(e), canonical_stack(store[n])) for store, ent, wn in jobs for e, n in zip(ent, wn) if n in store]
+            mats = iter([m.astype(np.float32) for m in self.iou_backend(segments)] if segments else [])
+            ious = [[next(mats) if n in store else None for n in wn] for store, _, wn in jobs]
+            self.matching_pred(jobs[0][1], jobs[0][2], ious[0])
+            self.matching_gt(jobs[1][1], jobs[1][2], ious[1])
 
     @staticmethod
     def parse_predictions(outputs, conf_thresh):
@@ -211,8 +360,8 @@ class F1Calculator:
             out.append([(labels[j].item(), corners[j] + np.random.randn(1) * 0.001, 1) for j in range(corners.shape[0])])
         return out
 
-    def matching_pred(self, detections, scene_names):
-        for dets, name in zip(detections, scene_names):
+    def matching_pred(self, detections, scene_names, ious=None):
+        for k, (dets, name) in enumerate(zip(detections, scene_names)):
             if name not in self.preds:
                 for k, d in enumerate(dets):
                     d[-1] = k
@@ -220,7 +369,7 @@ class F1Calculator:
                 continue
             trks = self.preds[name]
             n_before = len(trks)
-            matches, unmatched = _associate(dets, trks, self.iou_thresh)
+            matches, unmatched = _associate(dets, trks, self.iou_thresh, None if ious is None else ious[k])
             for d, t in matches:
                 dets[d][-1] = trks[t][-1]
                 if trks[t][2] < dets[d][2]:              # the more confident observation represents the track
@@ -231,15 +380,15 @@ class F1Calculator:
             self.preds[name] = copy.deepcopy(trks)
         return detections
 
-    def matching_gt(self, gts, scene_names):
+    def matching_gt(self, gts, scene_names, ious=None):
         snapshot = []
-        for dets, name in zip(gts, scene_names):
+        for k, (dets, name) in enumerate(zip(gts, scene_names)):
             if name not in self.gts:
                 self.gts[name] = dets
                 snapshot.append(copy.deepcopy(dets))
                 continue
             trks = self.gts[name]
-            matches, unmatched = _associate(dets, trks, self.iou_thresh)
+            matches, unmatched = _associate(dets, trks, self.iou_thresh, None if ious is None else ious[k])
             for d, t in matches:
                 if trks[t][2] < dets[d][2]:              # scores are the placeholder 1: never replaces
                     trks[t] = dets[d]
@@ -249,16 +398,23 @@ class F1Calculator:
         return snapshot
 
     # ---- end of epoch -------------------------------------------------------------------------------------------------
-    def counts(self, threshold):
+    def counts(self, threshold, ious=None):
         total = [{k: 0 for k in CARE_CLASSES} for _ in range(3)]
         for scene, preds in self.preds.items():
-            count_matches(total[0], total[1], total[2], preds, self.gts[scene], threshold)
+            count_matches(total[0], total[1], total[2], preds, self.gts[scene], threshold, None if ious is None else ious[scene])
         return total
+
+    def scene_ious(self):
+        """{scene: float64 (ground truth, predictions) IoU matrix} of every scene from one call of the backend."""
+        scenes = list(self.preds)
+        mats = self.iou_backend([(canonical_stack(self.gts[s]), canonical_stack(self.preds[s])) for s in scenes]) if scenes else []
+        return dict(zip(scenes, mats))
 
     def compute_metrics(self):
         metrics = {}
+        ious = self.scene_ious() if self.iou_backend is not None else None           # every threshold reads the same matrices
         for thr in self.f1_iou_thresh:
-            gts, preds, tps = self.counts(thr)
+            gts, preds, tps = self.counts(thr, ious)
             acc, rec, f1 = f1_from_counts(gts, preds, tps, self.verbose)
             metrics["{}_accuracy".format(thr)] = acc
             metrics["{}_recall".format(thr)] = rec
