@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the PARQ recurrent decoder path on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--scenes-per-gpu B] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--scenes-per-gpu B] [--dump-outputs DIR] [--full]
 
 metric  : decoder-iterations/sec = scenes x recurrent iterations / wall time of
           PARQDecoder.forward (prologue incl. the hoisted K/V projection + I iterations)
@@ -14,7 +14,10 @@ N > 1   : one process per GPU, scenes sharded data-parallel (independent, no dat
           `python -m torch.distributed.run` BEFORE it touches the GPU, forwards rank 0's JSON line and
           exits with the launcher's code; under torchrun (the driver's form) it is a rank.
 
-Also reported in the same JSON line:
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the
+JSON line (metric, value, unit, ms_per_step, dtype, the configuration, what the attention guard saw in the timed forwards).
+
+With --full (off by default), measured after the timed region in runs of their own and reported in the same JSON line:
   roofline      dominant kernel (flash_split_pipe_kernel, the dense cross-attention): algorithmic FLOP per launch
                 (4*Q*N*C per scene) / mean launch time from hipEvents recorded by the library
                 on the launch stream during an instrumented repeat of the same K steps
@@ -22,6 +25,8 @@ Also reported in the same JSON line:
   roofline_project_sample   HBM-bound gather: algorithmic bytes (4*V*Q*C + Q*C)*4 per scene
   cpu_baseline  the oracle in reference_ops mode (same ATen op sequence as the reference)
                 on the host cores, bounded sample (rank 0, N=1 only)
+  and the sub-records strict_fp16x3, guard_policy_cost, two_/three_scenes_in_flight, peaked_workload, ray_pe, device_state_under_load,
+  roofline_project_sample_b32, step_ms_hipevents, kernel_groups_ms_per_step; with --train, opt_in_train_split8.
 """
 from __future__ import annotations
 
@@ -511,7 +516,7 @@ def train_bench(args):
     per_rank_ms = [x / args.steps * 1e3 for x in parallel.gather_over_ranks(dt_own, device=red_dev)]
     final_loss, train_mode = float(loss.detach()), dec._train_mode()
     opt_in = None
-    if world == 1 and dec.attention_mode == "split8" and not dec.train_split8 and not (args.dev_lib or parq_env()):
+    if args.full and world == 1 and dec.attention_mode == "split8" and not dec.train_split8 and not (args.dev_lib or parq_env()):
         # after the timed region: the same steps with the training forward in mode split8 (PARQDecoder.train_split8, off by default)
         dec.train_split8 = True
         for _ in range(max(2, args.warmup)):
@@ -601,126 +606,12 @@ def self_launch(n, share_device=False):
     return subprocess.run(cmd, env=env).returncode
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--scenes-per-gpu", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-b32", action="store_true", help="skip the 32-scene project+sample bandwidth measurement (6.3 GB of tokens)")
-    ap.add_argument("--no-peaked", action="store_true", help="skip the peaked_workload record (the same workload with sharpened cross-attention)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes (roofline.traffic then comes from profiles/rNN_pmc.json)")
-    ap.add_argument("--pmc-child", "--kernels-only", dest="pmc_child", action="store_true",
-                    help="only the forwards of the configuration (warm-up + steps), nothing measured or printed: the command to put behind "
-                         "`rocprofv3 ... --` so that per-kernel statistics hold the timed workload's kernels and nothing else (live_pmc uses it)")
-    ap.add_argument("--train-split8", action="store_true", help="--train: run the training forward in mode split8 (PARQDecoder.train_split8)")
-    ap.add_argument("--attention-mode", default=None, choices=["split", "split8", "fp32", "fp16", "bf16"],
-                    help="cross-attention arithmetic; default = the library default (split8 at d = 256 / head dim 64: fp16 hi.hi + fp8 cross terms; "
-                         "split: three fp16 terms). "
-                         "fp16 / bf16 are the reduced-precision configurations (NOT the headline number)")
-    ap.add_argument("--train", action="store_true", help="time the training step of BASELINE config 4's per-GPU shard instead")
-    ap.add_argument("--dropout", type=float, default=0.1, help="--train: dropout rate (config/train.yaml:53 = 0.1, the default; other "
-                    "values are for kernel A/B only)")
-    ap.add_argument("--token-grad", action="store_true", help="--train: also compute d loss / d tokens (B x N x C; what a trained "
-                    "backbone or the ray-PE encoder in front of the decoder consumes)")
-    ap.add_argument("--phase-times", action="store_true", help="--train: also report the median device time of forward / loss / "
-                    "backward / optimizer over 5 extra untimed steps (phase_ms)")
-    ap.add_argument("--dev-lib", action="store_true", help="development only: bind parq_amd/_C/libparq_hip_dev.so (-DPARQ_DEV_PROBES: "
-                    "environment A/B switches and probe kernels); the line is then marked as NOT a headline number")
-    ap.add_argument("--share-device", action="store_true", help="N > 1 on a box with fewer than N GPUs: every rank uses cuda:0 and the "
-                    "process group runs over gloo — exercises the rank path (sharding, barrier, max over ranks), not a scaling number")
-    ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS), help="BASELINE.json configuration: cfg3 (default) is the one the "
-                    "metric is quoted on = the headline; cfg2 (bf16) / cfg5 (fp16) are the reduced-precision configurations, emitted as "
-                    "the same JSON line with their own roofline and bounded cpu_baseline (NOT the headline number)")
-    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
-                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32; rank 0): "
-                         "the forward's per-iteration output tensors, or with --train the loss and the updated parameters.  Inputs and "
-                         "weights are seeded, so two builds run with the same arguments can be compared output for output")
-    ap.add_argument("--dim", type=int, default=256, help="decoder width; 256 = the BASELINE metric (default).  1024 = the reference's "
-                    "shipped DEC_DIM (head dim 256): reported beside the headline, NOT the BASELINE metric")
-    args = ap.parse_args()
-    if args.steps < 1 or args.warmup < 0:
-        ap.error("--steps must be >= 1 and --warmup >= 0")
-    conf = CONFIGS[args.config]
-    if "dim" in conf:
-        args.dim = conf["dim"]
-    WORKLOAD["dim"] = args.dim
-    WORKLOAD.update({k: conf[k] for k in ("views", "image_hw", "feat_hw", "queries", "iters")})
-    if conf["mode"] and not args.attention_mode:
-        args.attention_mode = conf["mode"]
-    if args.config != "cfg3":
-        args.no_b32 = True
-    if args.dim != 256 and args.config != "shipped":
-        args.no_cpu_baseline = True                     # the bounded CPU sample is sized for the headline configuration
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(self_launch(args.gpus, args.share_device))
-    if args.dev_lib:
-        from parq_amd import _lib
-        _lib.use_dev_library()
-    if args.train:
-        return train_bench(args)
-
-    from parq_amd import parallel
-    rank, local_rank, world = parallel.env_world()
-    if world != args.gpus:
-        raise SystemExit("bench.py --gpus %d was started with WORLD_SIZE=%d" % (args.gpus, world))
-    # host placement BEFORE the first GPU call (the runtime's helper threads inherit the mask): each rank on the cores of its
-    # GPU's NUMA node, ranks that share a node on disjoint slices.  In-process sched_setaffinity, no re-exec.
-    shared_dev = world > 1 and args.share_device and torch.cuda.device_count() < world      # (device_count does not initialise the runtime)
-    pinned = parallel.pin_to_local_cores(local_rank, gpu_index_of=(lambda r: 0) if shared_dev else None) if world > 1 else []
-    torch.set_grad_enabled(False)     # the metric is the inference forward; the reference's drivers run it under no_grad (eval.py:46)
-    assert torch.cuda.is_available(), "bench.py needs a GPU (no CPU fallback in the product path)"
-    device, backend = rank_device_and_backend(args, local_rank, world)
-    parallel.init(backend=backend, device=device)                             # "nccl" is RCCL on ROCm
-    red_dev = device if backend == "nccl" else None                           # gloo reduces host scalars on the host
-
-    B = args.scenes_per_gpu
+def measure_beside(args, dec, step, inputs, B, rank, world, device):
+    """--full: what the benchmark measures beside `value`, each figure in runs of its own AFTER the timed region (every rank runs
+    the first two; the rest is single-process only): per-step hipEvent times, the library's per-kernel-group times, the strict
+    fp16 x 3 mode, the cost of the never-NaN policy, two and three scenes in flight, the live rocprofv3 --pmc passes."""
     I = WORKLOAD["iters"]
     h, w = WORKLOAD["feat_hw"]
-    cfg, W, dec = build_decoder(device)
-    if args.attention_mode:
-        dec.attention_mode = args.attention_mode
-    inputs = build_inputs(B, device, seed=1000 + rank)         # each rank owns its own scenes (sharded)
-
-    def step():
-        return dec(*inputs, feat_hw=(h, w))
-
-    if args.pmc_child:                    # live_pmc(): the kernels of this configuration under rocprofv3 --pmc, nothing printed
-        for _ in range(args.warmup + args.steps):
-            step()
-        torch.cuda.synchronize()
-        return
-
-    def barrier():
-        torch.cuda.synchronize()
-        parallel.barrier()
-        torch.cuda.synchronize()
-
-    # Device spin-up, untimed and before the W warm-up steps: the first ~12 forwards of a process run 2 - 12 % slower than the steady
-    # state (lazy code-object loading on the first, then the clock / power controller settling: tools/step_times.py prints the
-    # per-forward times).  A throughput number should not depend on how few steps the caller asks for.
-    for _ in range(PREWARM_STEPS):
-        step()
-    for _ in range(args.warmup):
-        step()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        last = step()
-    barrier()
-    dt_own = time.perf_counter() - t0
-    if args.dump_outputs and rank == 0:
-        dump_outputs(args.dump_outputs, {"it%d_%s" % (k, key): v for k, o in enumerate(last) for key, v in o.items()})
-    del last
-    dt = parallel.max_over_ranks(dt_own, device=red_dev)
-    per_rank_ms = [x / args.steps * 1e3 for x in parallel.gather_over_ranks(dt_own, device=red_dev)]
-    per_rank_cpus = parallel.gather_over_ranks(float(len(pinned)), device=red_dev)
-    try:                                  # (object collectives pickle through the backend: never let a reporting extra end a multi-GPU run)
-        per_rank_cpulists = [parallel.cpulist_string(c) for c in parallel.gather_objects(list(pinned))]
-    except Exception as exc:              # noqa: BLE001
-        per_rank_cpulists = ["unavailable: %s" % type(exc).__name__] * world
-
     # ---- per-step times from hipEvents on the launch stream (SURVEY.md 8d: median of >= 20 runs); the wall-clock mean above stays
     # the contract's `value`, this is its cross-check and its spread
     n_ev = max(20, args.steps)
@@ -731,7 +622,6 @@ def main():
         evs[i + 1].record()
     torch.cuda.synchronize()
     step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_ev))
-    pct = lambda q: step_ms[min(n_ev - 1, int(q * n_ev))]
 
     # ---- per-kernel-group times: hipEvents recorded by the library on the launch stream
     dec.profile_enable(True)
@@ -744,8 +634,6 @@ def main():
     # ---- the same forward with all three terms of every cross-attention product in fp16 (attention_mode "split"), when the timed
     # mode was "split8": untimed by the contract, reported beside `value` with the largest difference of the two modes' outputs
     strict = None
-    guard_tripped = dec.attention_too_peaked() if hasattr(dec, "attention_too_peaked") else False
-    guard_lmin = dec.attention_min_row_sum() if hasattr(dec, "attention_min_row_sum") else None
     if dec.attention_mode == "split8" and world == 1 and not (args.dev_lib or parq_env()):
         fast_out = [{k: v.clone() for k, v in o.items()} for o in step()]
         dec.attention_mode = "split"
@@ -875,85 +763,280 @@ def main():
 
     if rank == 0 and world == 1 and not args.no_pmc and not (args.dev_lib or parq_env()):
         live_pmc(args, B)                 # two short child runs under rocprofv3 --pmc (after every timed region of this process)
+    return {"step_ms": step_ms, "prof": prof, "strict": strict, "policy_cost": policy_cost, "in_flight": in_flight, "in_flight3": in_flight3}
+
+
+def full_records(args, conf, cfg, W, dec, step, inputs, beside, value, B, world, device, local_rank):
+    """--full, rank 0: the records of the JSON line that come from `measure_beside` (rooflines of the dominant kernels, per-group and
+    per-step times, the sub-records measured beside `value`) and the measurements that follow them (peaked workload, ray-PE,
+    device state under load, the 32-scene gather, the CPU baseline)."""
+    I = WORKLOAD["iters"]
+    h, w = WORKLOAD["feat_hw"]
+    prof, step_ms = beside["prof"], beside["step_ms"]
+    n_ev = len(step_ms)
+    pct = lambda q: step_ms[min(n_ev - 1, int(q * n_ev))]
+    V, Q, C = WORKLOAD["views"], WORKLOAD["queries"], WORKLOAD["dim"]
+    N = V * h * w
+    live = _LIVE_PMC["by_kernel"] is not None and _LIVE_PMC["scenes"] == B      # HBM-side bytes measured in this run (live_pmc)
+    ca_ms, ca_n = prof["cross_attn"]
+    ps_ms, ps_n = prof["project_sample"]
+    flop_per_launch = 4.0 * Q * N * C * B                       # QK^T + PV, all heads, B scenes
+    ach_tflops = flop_per_launch / (ca_ms / ca_n * 1e-3) / 1e12 if ca_n else None
+    bytes_per_launch = (4.0 * V * Q * C + Q * C) * 4.0 * B
+    ps_gbs = bytes_per_launch / (ps_ms / ps_n * 1e-3) / 1e9 if ps_n else None
+    mode = dec.attention_mode
+    split = mode in ("split", "split8")
+    split8 = mode == "split8" and C == 256 and C // WORKLOAD["heads"] == 64 and N % 64 == 0
+    half = mode in ("fp16", "bf16")
+    # dominant kernel: cross-attention QK^T + PV.  In "split" mode every fp32-accurate product costs
+    # SPLIT_PASSES fp16 MFMAs, so the matrix roof for ALGORITHMIC flops is the dense fp16 peak / 3.
+    mfma_peak = (PEAK_F16_MATRIX_TFLOPS / SPLIT_PASSES if split else
+                 PEAK_F16_MATRIX_TFLOPS if half else PEAK_F32_MATRIX_TFLOPS)
+    kv_bytes = 2.0 * N * C * (2.0 if half else 4.0) * B
+    roofline = {"bound": "mfma",
+                "kernel": (("flash_split_pipe_kernel" if C // WORKLOAD["heads"] == 64 else "flash_split256_kernel") +
+                           " (cross-attention QK^T+PV, fp16 hi/lo 3-term products, fp32 accumulate)" if split
+                           else "flash_split_pipe_kernel<4,0,1> (cross-attention QK^T+PV, single %s products, fp32 accumulate)" % mode if half
+                           else "flash_f32_kernel (cross-attention QK^T+PV, fp32 MFMA)"),
+                "achieved": ach_tflops, "peak": mfma_peak, "unit": "TFLOP/s",
+                "frac": (ach_tflops / mfma_peak) if ach_tflops else None,
+                "traffic": pmc_traffic("flash_split_pipe_kernel", B) if (split and C == 256 and (args.config == "cfg3" or live)) else None,
+                "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE: see traffic_source); algorithmic stream = 2*N*C*4*B bytes",
+                "avg_launch_ms": (ca_ms / ca_n) if ca_n else None, "launches": ca_n,
+                "algorithmic_gflop_per_launch": flop_per_launch / 1e9,
+                "peak_note": ("dense fp16 MFMA peak 2500 TFLOP/s / 3 passes per product; the fp32-MFMA peak is %.1f"
+                              % PEAK_F32_MATRIX_TFLOPS) if split else "dense fp16/bf16 MFMA peak" if half else "fp32 MFMA peak",
+                "hbm_stream_gbs": (kv_bytes / (ca_ms / ca_n * 1e-3) / 1e9) if ca_n else None,
+                "note": "launch time from hipEvents around this kernel alone (its merge kernel is group cross_attn_merge)"}
+    if not split8 and ca_n and kv_bytes / (PEAK_HBM_GBS * 1e9) > flop_per_launch / (mfma_peak * 1e12):
+        # the roof that bounds the launch is the larger of its two floors: with few queries per key (cfg 2: 128; the 16-bit modes at
+        # 256) streaming the K/V cache once at 8 TB/s takes longer than the launch's products at the dense matrix peak
+        stream_gbs = kv_bytes / (ca_ms / ca_n * 1e-3) / 1e9
+        roofline.update({"bound": "hbm", "achieved": stream_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": stream_gbs / PEAK_HBM_GBS,
+                         "algorithmic_bytes_per_launch": kv_bytes,
+                         "peak_note": "HBM3E 8 TB/s (floor %.1f us) against %.1f us of products at the matrix peak; a plain streaming kernel "
+                                      "reaches 5.6 TB/s on this part" % (kv_bytes / (PEAK_HBM_GBS * 1e9) * 1e6, flop_per_launch / (mfma_peak * 1e12) * 1e6),
+                         "mfma": {"achieved": ach_tflops, "peak": mfma_peak, "unit": "TFLOP/s", "frac": ach_tflops / mfma_peak}})
+    if split8:
+        # mode 4: one fp16 product + two MX-fp8 products per algorithmic product.  Matrix roof for algorithmic flops:
+        # 2500 / 1.5 = 1667 TFLOP/s = 30 us per launch at cfg 3; the K/V stream of the launch (N C x (4 + 2) bytes:
+        # K hi16 + hi8 + lo8, V fp16) is 37 us at 8 TB/s, so HBM is the roof that bounds this kernel (stream-only build of the
+        # kernel: 54 us = 5.5 TB/s, the streaming ceiling of this part; profiles/r04_split8_ingredient_probes.txt)
+        kv_bytes = N * C * 6.0 * B                            # K: hi16 + hi8 + lo8, V: fp16 (24 KB per 64-key stage and head)
+        stream_gbs = (kv_bytes / (ca_ms / ca_n * 1e-3) / 1e9) if ca_n else None
+        mx_peak = PEAK_F16_MATRIX_TFLOPS / 1.5
+        roofline.update({"bound": "hbm", "kernel": "flash_split8_kernel (cross-attention: Q K^T = fp16 hi.hi + MX-scaled fp8 e4m3 cross terms, "
+                                                   "P V = fp16 product with a self-consistent normaliser, fp32 accumulate)",
+                         "achieved": stream_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": (stream_gbs / PEAK_HBM_GBS) if stream_gbs else None,
+                         "traffic": pmc_traffic("flash_split8_kernel", B) if (args.config == "cfg3" or live) else None,
+                         "algorithmic_bytes_per_launch": kv_bytes, "hbm_stream_gbs": stream_gbs,
+                         "peak_note": "HBM3E 8 TB/s; a plain streaming kernel reaches 5.6 TB/s on this part (profiles/r02_hbm_stream_ceiling.txt)",
+                         "mfma": {"achieved": ach_tflops, "peak": mx_peak, "unit": "TFLOP/s", "frac": (ach_tflops / mx_peak) if ach_tflops else None,
+                                  "note": "algorithmic flops against 2500 / 1.5: Q K^T = one fp16 pass + two fp8 passes at twice the rate, P V = one fp16 pass"}})
+    kv_ms, kv_n = prof["kv_proj"]
+    kvp_bytes = ((N * C * 4.0 + N * C * 6.0) * B if split8 else
+                 3.0 * N * C * 4.0 * B if not half else (N * C * 4.0 + 2.0 * N * C * 2.0) * B)     # tokens in, K and V cache images out
+    roofline["hbm_frac"] = (roofline["hbm_stream_gbs"] / PEAK_HBM_GBS) if roofline["hbm_stream_gbs"] else None
+    traffic_source = (_LIVE_PMC["note"] if live else
+                      "recorded: %s (rocprofv3 --pmc passes of the same command), not measured in this run%s"
+                      % (_pmc_record()[1], "" if not _LIVE_PMC["note"] else " (%s)" % _LIVE_PMC["note"]))
+    roofline["traffic_source"] = traffic_source
+    roofline_kv = {"bound": "hbm", "kernel": "kvproj_dma_kernel (hoisted K/V in-projection, once per forward)",
+                   "achieved": (kvp_bytes / (kv_ms / kv_n * 1e-3) / 1e9) if kv_n else None, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                   "frac": (kvp_bytes / (kv_ms / kv_n * 1e-3) / 1e9 / PEAK_HBM_GBS) if kv_n else None,
+                   "traffic": pmc_traffic("kvproj_dma_kernel", B) if (args.config == "cfg3" or live) else None, "traffic_source": traffic_source,
+                   "algorithmic_bytes_per_launch": kvp_bytes, "avg_launch_ms": (kv_ms / kv_n) if kv_n else None, "launches": kv_n,
+                   "streaming_ceiling_ms": kvp_bytes / 5.6e12 * 1e3,
+                   "note": "reads N*C fp32 tokens, writes the K and V cache images; a plain streaming kernel with this 1:2 read/write "
+                           "shape reaches 5.6 TB/s on MI355X (profiles/r02_hbm_stream_ceiling.txt; 24 of 32 KB per stage written in mode "
+                           "split8); also 4*N*C^2 = %.1f GFLOP x 3 "
+                           "fp16 passes on the matrix pipe" % (4.0 * N * C * C * B / 1e9)}
+    out = {
+        "step_ms_hipevents": {"median": pct(0.5), "p10": pct(0.1), "p90": pct(0.9), "min": step_ms[0], "n": n_ev,
+                              "iterations_per_sec_at_median": B * I / (pct(0.5) * 1e-3),
+                              "note": "rank 0, one hipEvent pair per forward on the launch stream; `value` is the contract's wall-clock figure"},
+        "roofline": roofline,
+        "roofline_kv_proj": roofline_kv,
+        "roofline_project_sample": {"bound": "hbm", "kernel": "project_sample_kernel", "scenes": B,
+                                    "achieved": ps_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                    "frac": (ps_gbs / PEAK_HBM_GBS) if ps_gbs else None,
+                                    "traffic": pmc_traffic("project_sample_kernel", B) if (args.config == "cfg3" or live) else None,
+                                    "algorithmic_bytes_per_launch": bytes_per_launch,
+                                    "avg_launch_ms": (ps_ms / ps_n) if ps_n else None, "launches": ps_n,
+                                    "note": ("latency-bound at one scene: a %.1f us launch over a 197 MB token tensor that sits in the 256 MB "
+                                             "Infinity Cache; the bandwidth figure is roofline_project_sample_b32" % (ps_ms / ps_n * 1e3))
+                                            if (B == 1 and ps_n) else None},
+        "kernel_groups_ms_per_step": {k: v[0] / args.steps for k, v in prof.items()},
+    }
+    if beside["strict"] is not None:
+        out["strict_fp16x3"] = beside["strict"]
+    if beside["in_flight"] is not None:
+        out["two_scenes_in_flight"] = beside["in_flight"]
+        out["three_scenes_in_flight"] = beside["in_flight3"]
+    if beside["policy_cost"] is not None:
+        out["guard_policy_cost"] = beside["policy_cost"]
+        out["host_enqueue_ms"] = beside["policy_cost"]["host_enqueue_ms"]
+    if hasattr(dec, "attention_too_peaked") and split8 and world == 1 and B == 1 and not args.no_peaked and not (args.dev_lib or parq_env()):
+        out["peaked_workload"] = peaked_workload(device, inputs, h, w, args.steps)
+    if C == 256:
+        out["ray_pe"] = ray_pe_timing(B, device)
+    if world == 1:
+        out["device_state_under_load"] = device_state_under_load(step, index=local_rank)
+    if world == 1 and C == 256 and B == 1 and not args.no_b32:
+        out["roofline_project_sample_b32"] = project_sample_b32(dec, device, h, w)
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(cfg, W, inputs, view_limit=4 if args.config == "cfg5" else None)
+        out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
+    return out
+
+
+def build_parser():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--scenes-per-gpu", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything the benchmark reports beside its headline figure, each in "
+                         "runs of its own: per-step and per-kernel-group times, rooflines, the strict fp16 x 3 mode, the cost of the never-NaN "
+                         "policy, scenes in flight, live rocprofv3 --pmc traffic, the peaked workload, ray-PE, the 32-scene gather, the CPU "
+                         "baseline (with --train: the opt-in split8 training forward).  Off by default: a plain run sets up, warms up, times "
+                         "the steps and prints the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-b32", action="store_true", help="--full: skip the 32-scene project+sample bandwidth measurement (6.3 GB of tokens)")
+    ap.add_argument("--no-peaked", action="store_true", help="--full: skip the peaked_workload record (the same workload with sharpened cross-attention)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the live rocprofv3 --pmc passes (roofline.traffic then comes from profiles/rNN_pmc.json)")
+    ap.add_argument("--pmc-child", "--kernels-only", dest="pmc_child", action="store_true",
+                    help="only the forwards of the configuration (warm-up + steps), nothing measured or printed: the command to put behind "
+                         "`rocprofv3 ... --` so that per-kernel statistics hold the timed workload's kernels and nothing else (live_pmc uses it)")
+    ap.add_argument("--train-split8", action="store_true", help="--train: run the training forward in mode split8 (PARQDecoder.train_split8)")
+    ap.add_argument("--attention-mode", default=None, choices=["split", "split8", "fp32", "fp16", "bf16"],
+                    help="cross-attention arithmetic; default = the library default (split8 at d = 256 / head dim 64: fp16 hi.hi + fp8 cross terms; "
+                         "split: three fp16 terms). "
+                         "fp16 / bf16 are the reduced-precision configurations (NOT the headline number)")
+    ap.add_argument("--train", action="store_true", help="time the training step of BASELINE config 4's per-GPU shard instead")
+    ap.add_argument("--dropout", type=float, default=0.1, help="--train: dropout rate (config/train.yaml:53 = 0.1, the default; other "
+                    "values are for kernel A/B only)")
+    ap.add_argument("--token-grad", action="store_true", help="--train: also compute d loss / d tokens (B x N x C; what a trained "
+                    "backbone or the ray-PE encoder in front of the decoder consumes)")
+    ap.add_argument("--phase-times", action="store_true", help="--train: also report the median device time of forward / loss / "
+                    "backward / optimizer over 5 extra untimed steps (phase_ms)")
+    ap.add_argument("--dev-lib", action="store_true", help="development only: bind parq_amd/_C/libparq_hip_dev.so (-DPARQ_DEV_PROBES: "
+                    "environment A/B switches and probe kernels); the line is then marked as NOT a headline number")
+    ap.add_argument("--share-device", action="store_true", help="N > 1 on a box with fewer than N GPUs: every rank uses cuda:0 and the "
+                    "process group runs over gloo — exercises the rank path (sharding, barrier, max over ranks), not a scaling number")
+    ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS), help="BASELINE.json configuration: cfg3 (default) is the one the "
+                    "metric is quoted on = the headline; cfg2 (bf16) / cfg5 (fp16) are the reduced-precision configurations, emitted as "
+                    "the same JSON line with their own roofline and bounded cpu_baseline (NOT the headline number)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32; rank 0): "
+                         "the forward's per-iteration output tensors, or with --train the loss and the updated parameters.  Inputs and "
+                         "weights are seeded, so two builds run with the same arguments can be compared output for output")
+    ap.add_argument("--dim", type=int, default=256, help="decoder width; 256 = the BASELINE metric (default).  1024 = the reference's "
+                    "shipped DEC_DIM (head dim 256): reported beside the headline, NOT the BASELINE metric")
+    return ap
+
+
+def main():
+    ap = build_parser()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    conf = CONFIGS[args.config]
+    if "dim" in conf:
+        args.dim = conf["dim"]
+    WORKLOAD["dim"] = args.dim
+    WORKLOAD.update({k: conf[k] for k in ("views", "image_hw", "feat_hw", "queries", "iters")})
+    if conf["mode"] and not args.attention_mode:
+        args.attention_mode = conf["mode"]
+    if args.config != "cfg3":
+        args.no_b32 = True
+    if args.dim != 256 and args.config != "shipped":
+        args.no_cpu_baseline = True                     # the bounded CPU sample is sized for the headline configuration
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(self_launch(args.gpus, args.share_device))
+    if args.dev_lib:
+        from parq_amd import _lib
+        _lib.use_dev_library()
+    if args.train:
+        return train_bench(args)
+
+    from parq_amd import parallel
+    rank, local_rank, world = parallel.env_world()
+    if world != args.gpus:
+        raise SystemExit("bench.py --gpus %d was started with WORLD_SIZE=%d" % (args.gpus, world))
+    # host placement BEFORE the first GPU call (the runtime's helper threads inherit the mask): each rank on the cores of its
+    # GPU's NUMA node, ranks that share a node on disjoint slices.  In-process sched_setaffinity, no re-exec.
+    shared_dev = world > 1 and args.share_device and torch.cuda.device_count() < world      # (device_count does not initialise the runtime)
+    pinned = parallel.pin_to_local_cores(local_rank, gpu_index_of=(lambda r: 0) if shared_dev else None) if world > 1 else []
+    torch.set_grad_enabled(False)     # the metric is the inference forward; the reference's drivers run it under no_grad (eval.py:46)
+    assert torch.cuda.is_available(), "bench.py needs a GPU (no CPU fallback in the product path)"
+    device, backend = rank_device_and_backend(args, local_rank, world)
+    parallel.init(backend=backend, device=device)                             # "nccl" is RCCL on ROCm
+    red_dev = device if backend == "nccl" else None                           # gloo reduces host scalars on the host
+
+    B = args.scenes_per_gpu
+    I = WORKLOAD["iters"]
+    h, w = WORKLOAD["feat_hw"]
+    cfg, W, dec = build_decoder(device)
+    if args.attention_mode:
+        dec.attention_mode = args.attention_mode
+    inputs = build_inputs(B, device, seed=1000 + rank)         # each rank owns its own scenes (sharded)
+
+    def step():
+        return dec(*inputs, feat_hw=(h, w))
+
+    if args.pmc_child:                    # live_pmc(): the kernels of this configuration under rocprofv3 --pmc, nothing printed
+        for _ in range(args.warmup + args.steps):
+            step()
+        torch.cuda.synchronize()
+        return
+
+    def barrier():
+        torch.cuda.synchronize()
+        parallel.barrier()
+        torch.cuda.synchronize()
+
+    # Device spin-up, untimed and before the W warm-up steps: the first ~12 forwards of a process run 2 - 12 % slower than the steady
+    # state (lazy code-object loading on the first, then the clock / power controller settling: tools/step_times.py prints the
+    # per-forward times).  A throughput number should not depend on how few steps the caller asks for.
+    for _ in range(PREWARM_STEPS):
+        step()
+    for _ in range(args.warmup):
+        step()
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        last = step()
+    barrier()
+    dt_own = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"it%d_%s" % (k, key): v for k, o in enumerate(last) for key, v in o.items()})
+    del last
+    dt = parallel.max_over_ranks(dt_own, device=red_dev)
+    per_rank_ms = [x / args.steps * 1e3 for x in parallel.gather_over_ranks(dt_own, device=red_dev)]
+    per_rank_cpus = parallel.gather_over_ranks(float(len(pinned)), device=red_dev)
+    try:                                  # (object collectives pickle through the backend: never let a reporting extra end a multi-GPU run)
+        per_rank_cpulists = [parallel.cpulist_string(c) for c in parallel.gather_objects(list(pinned))]
+    except Exception as exc:              # noqa: BLE001
+        per_rank_cpulists = ["unavailable: %s" % type(exc).__name__] * world
+
+    # what the guard saw in the timed forwards: reads of the last forward's flag words, nothing is launched
+    guard_tripped = dec.attention_too_peaked() if hasattr(dec, "attention_too_peaked") else False
+    guard_lmin = dec.attention_min_row_sum() if hasattr(dec, "attention_min_row_sum") else None
+
+    # ---- a plain run ends here with the headline line; everything measured or checked beside `value` takes runs of its own and
+    # happens under --full only, after the timed region (measure_beside, full_records)
+    beside = measure_beside(args, dec, step, inputs, B, rank, world, device) if args.full else None
     if rank == 0:
         V, Q, C = WORKLOAD["views"], WORKLOAD["queries"], WORKLOAD["dim"]
         N = V * h * w
         total_iters = world * B * I * args.steps
-        live = _LIVE_PMC["by_kernel"] is not None and _LIVE_PMC["scenes"] == B      # HBM-side bytes measured in this run (live_pmc)
-        ca_ms, ca_n = prof["cross_attn"]
-        ps_ms, ps_n = prof["project_sample"]
-        flop_per_launch = 4.0 * Q * N * C * B                       # QK^T + PV, all heads, B scenes
-        ach_tflops = flop_per_launch / (ca_ms / ca_n * 1e-3) / 1e12 if ca_n else None
-        bytes_per_launch = (4.0 * V * Q * C + Q * C) * 4.0 * B
-        ps_gbs = bytes_per_launch / (ps_ms / ps_n * 1e-3) / 1e9 if ps_n else None
         mode = dec.attention_mode
         split = mode in ("split", "split8")
         split8 = mode == "split8" and C == 256 and C // WORKLOAD["heads"] == 64 and N % 64 == 0
         half = mode in ("fp16", "bf16")
-        # dominant kernel: cross-attention QK^T + PV.  In "split" mode every fp32-accurate product costs
-        # SPLIT_PASSES fp16 MFMAs, so the matrix roof for ALGORITHMIC flops is the dense fp16 peak / 3.
-        mfma_peak = (PEAK_F16_MATRIX_TFLOPS / SPLIT_PASSES if split else
-                     PEAK_F16_MATRIX_TFLOPS if half else PEAK_F32_MATRIX_TFLOPS)
-        kv_bytes = 2.0 * N * C * (2.0 if half else 4.0) * B
-        roofline = {"bound": "mfma",
-                    "kernel": (("flash_split_pipe_kernel" if C // WORKLOAD["heads"] == 64 else "flash_split256_kernel") +
-                               " (cross-attention QK^T+PV, fp16 hi/lo 3-term products, fp32 accumulate)" if split
-                               else "flash_split_pipe_kernel<4,0,1> (cross-attention QK^T+PV, single %s products, fp32 accumulate)" % mode if half
-                               else "flash_f32_kernel (cross-attention QK^T+PV, fp32 MFMA)"),
-                    "achieved": ach_tflops, "peak": mfma_peak, "unit": "TFLOP/s",
-                    "frac": (ach_tflops / mfma_peak) if ach_tflops else None,
-                    "traffic": pmc_traffic("flash_split_pipe_kernel", B) if (split and C == 256 and (args.config == "cfg3" or live)) else None,
-                    "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE: see traffic_source); algorithmic stream = 2*N*C*4*B bytes",
-                    "avg_launch_ms": (ca_ms / ca_n) if ca_n else None, "launches": ca_n,
-                    "algorithmic_gflop_per_launch": flop_per_launch / 1e9,
-                    "peak_note": ("dense fp16 MFMA peak 2500 TFLOP/s / 3 passes per product; the fp32-MFMA peak is %.1f"
-                                  % PEAK_F32_MATRIX_TFLOPS) if split else "dense fp16/bf16 MFMA peak" if half else "fp32 MFMA peak",
-                    "hbm_stream_gbs": (kv_bytes / (ca_ms / ca_n * 1e-3) / 1e9) if ca_n else None,
-                    "note": "launch time from hipEvents around this kernel alone (its merge kernel is group cross_attn_merge)"}
-        if not split8 and ca_n and kv_bytes / (PEAK_HBM_GBS * 1e9) > flop_per_launch / (mfma_peak * 1e12):
-            # the roof that bounds the launch is the larger of its two floors: with few queries per key (cfg 2: 128; the 16-bit modes at
-            # 256) streaming the K/V cache once at 8 TB/s takes longer than the launch's products at the dense matrix peak
-            stream_gbs = kv_bytes / (ca_ms / ca_n * 1e-3) / 1e9
-            roofline.update({"bound": "hbm", "achieved": stream_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": stream_gbs / PEAK_HBM_GBS,
-                             "algorithmic_bytes_per_launch": kv_bytes,
-                             "peak_note": "HBM3E 8 TB/s (floor %.1f us) against %.1f us of products at the matrix peak; a plain streaming kernel "
-                                          "reaches 5.6 TB/s on this part" % (kv_bytes / (PEAK_HBM_GBS * 1e9) * 1e6, flop_per_launch / (mfma_peak * 1e12) * 1e6),
-                             "mfma": {"achieved": ach_tflops, "peak": mfma_peak, "unit": "TFLOP/s", "frac": ach_tflops / mfma_peak}})
-        if split8:
-            # mode 4: one fp16 product + two MX-fp8 products per algorithmic product.  Matrix roof for algorithmic flops:
-            # 2500 / 1.5 = 1667 TFLOP/s = 30 us per launch at cfg 3; the K/V stream of the launch (N C x (4 + 2) bytes:
-            # K hi16 + hi8 + lo8, V fp16) is 37 us at 8 TB/s, so HBM is the roof that bounds this kernel (stream-only build of the
-            # kernel: 54 us = 5.5 TB/s, the streaming ceiling of this part; profiles/r04_split8_ingredient_probes.txt)
-            kv_bytes = N * C * 6.0 * B                            # K: hi16 + hi8 + lo8, V: fp16 (24 KB per 64-key stage and head)
-            stream_gbs = (kv_bytes / (ca_ms / ca_n * 1e-3) / 1e9) if ca_n else None
-            mx_peak = PEAK_F16_MATRIX_TFLOPS / 1.5
-            roofline.update({"bound": "hbm", "kernel": "flash_split8_kernel (cross-attention: Q K^T = fp16 hi.hi + MX-scaled fp8 e4m3 cross terms, "
-                                                       "P V = fp16 product with a self-consistent normaliser, fp32 accumulate)",
-                             "achieved": stream_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": (stream_gbs / PEAK_HBM_GBS) if stream_gbs else None,
-                             "traffic": pmc_traffic("flash_split8_kernel", B) if (args.config == "cfg3" or live) else None,
-                             "algorithmic_bytes_per_launch": kv_bytes, "hbm_stream_gbs": stream_gbs,
-                             "peak_note": "HBM3E 8 TB/s; a plain streaming kernel reaches 5.6 TB/s on this part (profiles/r02_hbm_stream_ceiling.txt)",
-                             "mfma": {"achieved": ach_tflops, "peak": mx_peak, "unit": "TFLOP/s", "frac": (ach_tflops / mx_peak) if ach_tflops else None,
-                                      "note": "algorithmic flops against 2500 / 1.5: Q K^T = one fp16 pass + two fp8 passes at twice the rate, P V = one fp16 pass"}})
         not_headline = bool(args.dev_lib or parq_env())
-        kv_ms, kv_n = prof["kv_proj"]
-        kvp_bytes = ((N * C * 4.0 + N * C * 6.0) * B if split8 else
-                     3.0 * N * C * 4.0 * B if not half else (N * C * 4.0 + 2.0 * N * C * 2.0) * B)     # tokens in, K and V cache images out
-        roofline["hbm_frac"] = (roofline["hbm_stream_gbs"] / PEAK_HBM_GBS) if roofline["hbm_stream_gbs"] else None
-        traffic_source = (_LIVE_PMC["note"] if live else
-                          "recorded: %s (rocprofv3 --pmc passes of the same command), not measured in this run%s"
-                          % (_pmc_record()[1], "" if not _LIVE_PMC["note"] else " (%s)" % _LIVE_PMC["note"]))
-        roofline["traffic_source"] = traffic_source
-        roofline_kv = {"bound": "hbm", "kernel": "kvproj_dma_kernel (hoisted K/V in-projection, once per forward)",
-                       "achieved": (kvp_bytes / (kv_ms / kv_n * 1e-3) / 1e9) if kv_n else None, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                       "frac": (kvp_bytes / (kv_ms / kv_n * 1e-3) / 1e9 / PEAK_HBM_GBS) if kv_n else None,
-                       "traffic": pmc_traffic("kvproj_dma_kernel", B) if (args.config == "cfg3" or live) else None, "traffic_source": traffic_source,
-                       "algorithmic_bytes_per_launch": kvp_bytes, "avg_launch_ms": (kv_ms / kv_n) if kv_n else None, "launches": kv_n,
-                       "streaming_ceiling_ms": kvp_bytes / 5.6e12 * 1e3,
-                       "note": "reads N*C fp32 tokens, writes the K and V cache images; a plain streaming kernel with this 1:2 read/write "
-                               "shape reaches 5.6 TB/s on MI355X (profiles/r02_hbm_stream_ceiling.txt; 24 of 32 KB per stage written in mode "
-                               "split8); also 4*N*C^2 = %.1f GFLOP x 3 "
-                               "fp16 passes on the matrix pipe" % (4.0 * N * C * C * B / 1e9)}
         out = {
             "metric": "decoder-iterations/sec (%d views, %d queries, d=%d)%s%s%s" % (
                 V, Q, C, "" if (C == 256 or args.config == "shipped") else " [not the BASELINE metric: non-default --dim]",
@@ -968,9 +1051,6 @@ def main():
             "per_rank_pinned_cpus": [int(x) for x in per_rank_cpus],   # host cores each rank pinned itself to (0 = mask left alone)
             "per_rank_pinned_cpulist": per_rank_cpulists,
             "rccl_version": (".".join(str(x) for x in torch.cuda.nccl.version()) if world > 1 and hasattr(torch.cuda, "nccl") else None),
-            "step_ms_hipevents": {"median": pct(0.5), "p10": pct(0.1), "p90": pct(0.9), "min": step_ms[0], "n": n_ev,
-                                  "iterations_per_sec_at_median": B * I / (pct(0.5) * 1e-3),
-                                  "note": "rank 0, one hipEvent pair per forward on the launch stream; `value` is the contract's wall-clock figure"},
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": ("f32 (cross-attention scores: fp16 hi.hi + MX-fp8 e4m3 cross terms; P V: fp16 probabilities and values with a "
                                           "self-consistent normaliser; fp32 accumulation — 4e-6..1.5e-5 from float64 at the outputs on the reference's fixtures, the "
@@ -984,45 +1064,17 @@ def main():
                        "scenes_per_gpu": B, "parallelism": "dp%d (scene-sharded, no data-path collective)" % world},
             "parity_metric": "outputs are held to the reference within 1e-4 on |a-b| / max(1,|b|) (absolute below 1, relative above; "
                              "tests/golden_util.py); reduced-precision modes: bf16 2e-3, fp16 3e-4",
-            "roofline": roofline,
-            "roofline_kv_proj": roofline_kv,
-            "roofline_project_sample": {"bound": "hbm", "kernel": "project_sample_kernel", "scenes": B,
-                                        "achieved": ps_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                        "frac": (ps_gbs / PEAK_HBM_GBS) if ps_gbs else None,
-                                        "traffic": pmc_traffic("project_sample_kernel", B) if (args.config == "cfg3" or live) else None,
-                                        "algorithmic_bytes_per_launch": bytes_per_launch,
-                                        "avg_launch_ms": (ps_ms / ps_n) if ps_n else None, "launches": ps_n,
-                                        "note": ("latency-bound at one scene: a %.1f us launch over a 197 MB token tensor that sits in the 256 MB "
-                                                 "Infinity Cache; the bandwidth figure is roofline_project_sample_b32" % (ps_ms / ps_n * 1e3))
-                                                if (B == 1 and ps_n) else None},
-            "kernel_groups_ms_per_step": {k: v[0] / args.steps for k, v in prof.items()},
+            "full": bool(args.full),
         }
-        if strict is not None:
-            out["strict_fp16x3"] = strict
-        if in_flight is not None:
-            out["two_scenes_in_flight"] = in_flight
-            out["three_scenes_in_flight"] = in_flight3
-        if policy_cost is not None:
-            out["guard_policy_cost"] = policy_cost
-            out["host_enqueue_ms"] = policy_cost["host_enqueue_ms"]
         if hasattr(dec, "attention_too_peaked"):
             # mode "split8" is kept only while every cross-attention row spreads over enough keys (its error model); a tripped guard
-            # would have switched the module to "split" and `dtype` / `roofline` above would say so
+            # would have switched the module to "split" and `dtype` above would say so
             out["attention_mode"] = mode
             out["attention_guard"] = {"row_probability_sum_threshold": 256, "tripped": bool(guard_tripped),
                                       "safe_heads": "0b" + format(int(getattr(dec, "safe_heads", 0)), "0%db" % WORKLOAD["heads"]),
                                       "smallest_row_probability_sum": guard_lmin, "policy": dec.range_check}
-            if split8 and world == 1 and B == 1 and not args.no_peaked and not (args.dev_lib or parq_env()):
-                out["peaked_workload"] = peaked_workload(device, inputs, h, w, args.steps)
-        if C == 256:
-            out["ray_pe"] = ray_pe_timing(B, device)
-        if world == 1:
-            out["device_state_under_load"] = device_state_under_load(step, index=local_rank)
-        if world == 1 and C == 256 and B == 1 and not args.no_b32:
-            out["roofline_project_sample_b32"] = project_sample_b32(dec, device, h, w)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg, W, inputs, view_limit=4 if args.config == "cfg5" else None)
-            out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
+        if args.full:
+            out.update(full_records(args, conf, cfg, W, dec, step, inputs, beside, out["value"], B, world, device, local_rank))
         print(json.dumps(out))
     if world > 1:
         parallel.barrier()

@@ -34,3 +34,12 @@ def test_dump_outputs_caps_the_total_with_a_fixed_sample(tmp_path):
         val = np.load(tmp_path / sub / "big.sample.npy")
         assert len(idx) > 0 and np.array_equal(val, big.numpy()[idx])
     assert np.array_equal(np.load(tmp_path / "a" / "big.sample_index.npy"), np.load(tmp_path / "b" / "big.sample_index.npy"))
+
+
+def test_full_is_an_option_that_is_off_by_default():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` measures the headline figure only; everything else waits for --full."""
+    ap = bench.build_parser()
+    plain = ap.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert plain.full is False and plain.steps == 5 and plain.warmup == 2 and plain.dump_outputs is None
+    assert ap.parse_args(["--full"]).full is True
+    assert ap.parse_args(["--train", "--full", "--no-cpu-baseline", "--no-b32", "--no-peaked", "--no-pmc"]).full is True

@@ -34,7 +34,7 @@ def _need_gpus(n):
 
 
 def test_bench_two_ranks_forward_line():
-    d = _run(["--steps", "4", "--warmup", "1"])
+    d = _run(["--full", "--steps", "4", "--warmup", "1"])          # --full: the roofline object asserted below is measured beside `value`
     want_backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
     assert d["n_gpus"] == 2 and d["collective_backend"] == want_backend
     assert d["rccl_ranks"] == (2 if want_backend == "nccl" else 0)            # no false RCCL claim on a shared device
@@ -91,20 +91,57 @@ def test_bench_eight_ranks_four_scenes_per_gpu_variant():
     assert d["guard_policy_cost"] is None if "guard_policy_cost" in d else True     # (single-rank extras stay out of multi-rank lines)
 
 
+PLAIN_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config")
+FULL_ONLY_KEYS = ("roofline", "roofline_kv_proj", "roofline_project_sample", "roofline_project_sample_b32", "kernel_groups_ms_per_step",
+                  "step_ms_hipevents", "strict_fp16x3", "two_scenes_in_flight", "three_scenes_in_flight", "guard_policy_cost",
+                  "host_enqueue_ms", "peaked_workload", "ray_pe", "device_state_under_load", "cpu_baseline", "speedup_vs_cpu_baseline")
+
+
+def test_bench_single_rank_plain_run_is_lean(tmp_path):
+    """The driver's N = 1 command as typed, `bench.py --gpus 1 --steps N --warmup W`: ONE JSON line with the contract's fields and the
+    --dump-outputs arrays, none of the records that take runs of their own (those wait for --full), and at most 30 s of the whole run,
+    from the start of the process to its exit, outside its N + W steps."""
+    import time
+    steps, warmup = 4, 1
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in PLAIN_KEYS:
+        assert key in d, key
+    for key in FULL_ONLY_KEYS:
+        assert key not in d, key
+    assert d["full"] is False
+    assert d["n_gpus"] == 1 and d["steps"] == steps and d["unit"] == "decoder-iterations/sec" and d["higher_is_better"] is True
+    assert d["dtype"].startswith("f32") and "10 views, 256 queries, d=256" in d["metric"]
+    assert abs(d["value"] - 8 * d["steps"] / (d["ms_per_step"] * 1e-3 * d["steps"])) < 1e-6 * d["value"]
+    assert d["attention_mode"] == "split8" and d["attention_guard"]["tripped"] is False and d["attention_guard"]["policy"] == "sync"
+    from parq_amd.decoder import OUTPUT_KEYS
+    assert sorted(os.listdir(tmp_path / "out")) == sorted("it%d_%s.npy" % (k, key) for k in range(8) for key in OUTPUT_KEYS)
+    outside = wall - (steps + warmup) * d["ms_per_step"] * 1e-3
+    print("plain run: %.1f s from start to exit, %.1f s outside its %d steps" % (wall, outside, steps + warmup))
+    assert outside <= 30.0, outside
+
+
 def test_bench_single_rank_default_line_contract(tmp_path):
-    """The driver's N = 1 command (fewer steps, without the CPU baseline and the optional records): ONE JSON line with the contract's
-    fields, the roofline object of the dominant kernel, and the sub-records measured beside `value` — the strict fp16 x 3 run and two
-    scenes in flight on two HIP streams, whose outputs must be bit for bit those of one-at-a-time forwards."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-b32",
+    """The driver's N = 1 command with --full (fewer steps, without the CPU baseline and the optional records): ONE JSON line with the
+    contract's fields, the roofline object of the dominant kernel, and the sub-records measured beside `value` — the strict fp16 x 3 run
+    and two scenes in flight on two HIP streams, whose outputs must be bit for bit those of one-at-a-time forwards."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-b32",
                         "--no-peaked", "--no-pmc", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=900,
                        cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
-    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-                "dtype", "data", "config", "roofline"):
+    for key in PLAIN_KEYS + ("roofline",):
         assert key in d, key
+    assert d["full"] is True
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["unit"] == "decoder-iterations/sec" and d["higher_is_better"] is True
     assert abs(d["value"] - 8 * d["steps"] / (d["ms_per_step"] * 1e-3 * d["steps"])) < 1e-6 * d["value"]
     # --dump-outputs: the six outputs of each of the 8 iterations of the last timed forward, finite float32

@@ -4,7 +4,7 @@ tag=${1:-batch}; kexpr=${2:-}
 cd /root/repo
 out=/root/repo/gpurun_out/$tag
 mkdir -p $out
-python bench.py > $out/bench.json 2> $out/bench.err
+python bench.py --full > $out/bench.json 2> $out/bench.err
 tail -c 600 $out/bench.json
 if [ -n "$kexpr" ]; then
   timeout 3000 python -m pytest tests -m gpu -x -q -k "$kexpr" > $out/pytest.log 2>&1

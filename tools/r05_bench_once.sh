@@ -3,7 +3,7 @@
 cd /root/repo
 out=/root/repo/gpurun_out/${1:-r05_bench_once}
 mkdir -p $out
-t0=$(date +%s); python bench.py > $out/bench.json 2> $out/bench.err; echo "bench.py wall: $(( $(date +%s) - t0 )) s"
+t0=$(date +%s); python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench.py wall: $(( $(date +%s) - t0 )) s"
 tail -2 $out/bench.err
 python - <<PY
 import json

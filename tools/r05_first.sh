@@ -8,5 +8,5 @@ echo "pytest rc=$?"; tail -25 $out/pytest_tiers.log
 timeout 600 python tools/split8_guard_sweep.py 1 2 2.5 3 4 6 > $out/guard_sweep_noise.txt 2>&1
 SMOOTH=1 timeout 600 python tools/split8_guard_sweep.py 1 2 3 4 6 8 > $out/guard_sweep_smooth.txt 2>&1
 cat $out/guard_sweep_noise.txt $out/guard_sweep_smooth.txt
-python bench.py > $out/bench.json 2> $out/bench.err
+python bench.py --full > $out/bench.json 2> $out/bench.err
 tail -c 1500 $out/bench.json

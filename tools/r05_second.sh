@@ -5,7 +5,7 @@ out=/root/repo/gpurun_out/${1:-r05_second}
 mkdir -p $out
 timeout 3000 python -m pytest tests -m gpu -q --durations=12 > $out/pytest.log 2>&1
 echo "pytest rc=$?"; tail -40 $out/pytest.log
-python bench.py > $out/bench.json 2> $out/bench.err
+python bench.py --full > $out/bench.json 2> $out/bench.err
 tail -3 $out/bench.err
 python - <<PY
 import json

@@ -4,9 +4,9 @@ cd /root/repo
 out=/root/repo/gpurun_out/r06p2
 rm -rf $out; mkdir -p $out
 timeout 3000 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 | tee $out/tests.log
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err
-timeout 900 python bench.py --config shipped --steps 20 --warmup 3 > $out/bench_shipped.json 2>> $out/bench.err
-timeout 900 python bench.py --config shipped --scenes-per-gpu 4 --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_shipped_4scenes.json 2>> $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err
+timeout 900 python bench.py --full --config shipped --steps 20 --warmup 3 > $out/bench_shipped.json 2>> $out/bench.err
+timeout 900 python bench.py --full --config shipped --scenes-per-gpu 4 --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_shipped_4scenes.json 2>> $out/bench.err
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('/root/repo/gpurun_out/r06p2/bench*.json')):
