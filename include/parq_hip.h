@@ -233,6 +233,42 @@ int parq_iterate(parq_handle h, const parq_scene *scene, void *workspace, size_t
                  int32_t layer_num, const float *ref_in, const parq_outputs *outs, float *ref_out,
                  parq_stream stream);
 
+/* ---- cross-attention maps ------------------------------------------------------------------------------------------------------
+ * The reference's decoder layer calls nn.MultiheadAttention with need_weights=True and drops the result
+ * (model/transformer_parq.py:377-380): the head-averaged attention of every query over all V*h*w pixel tokens.  Here the
+ * probabilities only exist as matrix-pipe fragments inside the flash kernels; parq_attention_map recomputes them ON REQUEST for the
+ * LAST iteration that ran in `workspace` (parq_forward / parq_forward_replay: the last iteration; parq_iterate: that iteration) from
+ * what that iteration left there — the projected queries ("cross_q") and the K cache of the layer that ran:
+ *     P[b,h,q,n] = softmax_n( q_h[b,q] . k_h[b,n] / sqrt(dh) ),   n in token order (v*h + y)*w + x,
+ * with k exactly what the forward's cache holds for that head: hi + lo in the split layout (modes 1 and 4's fp16 x 3 heads), the fp16
+ * hi plus the decoded e4m3 residual for mode-4 stages (per head, following parq_set_head_tiers), the single 16-bit value in modes 2 / 3,
+ * fp32 K in mode 0 and at head dims without a cache.  No dropout, no key mask.  The forward path is untouched: it writes no
+ * log-sum-exp, the map kernels compute their own row maxima and sums (attn_map.hip: row statistics over key splits and a merge, then
+ * the score tiles again, exp2(s - m) / l, heads summed in registers).  Scores are fp16 x 3 products of q split hi / lo in the kernel with
+ * fp32 accumulation, as the forward's (a K element outside the fp16 range — possible in mode 0 and with bf16 caches only — gives a
+ * non-finite row).  Every head dim parq_create accepts; any Q and N.
+ *   what       PARQ_MAP_HEAD_MEAN  out (B, n_sel, N)     mean over the heads (torch's average_attn_weights=True; the reference's tensor)
+ *              PARQ_MAP_PER_HEAD   out (B, H, n_sel, N)
+ *              PARQ_MAP_VIEW_MASS  out (B, n_sel, V)     the head mean summed over each view's h*w tokens; the map itself is not written
+ *   out_type   PARQ_MAP_F32 or PARQ_MAP_F16 (the fp32 value rounded to nearest even)
+ *   query_index  device int32[n_sel], rows of the Q queries in any order, repeats allowed (every index in [0, Q)); NULL = all Q rows
+ *              (n_sel 0 or Q).  A row's values do not depend on which rows are computed beside it.
+ *   scratch    parq_attention_map_scratch_bytes(h, B, V, hh, ww, n_sel) bytes (n_sel <= 0: all Q), 16-byte aligned.
+ * Deterministic: no atomics, two calls give the same bits.  Only enqueues on `stream`, which must be ordered behind the forward.
+ * Returns PARQ_ERR_STATE if no iteration has run in that workspace since it was prepared, if the last call there was a training
+ * forward or a view-sharded iteration (not supported), or if the handle's attention mode / token type changed since (head tiers may
+ * change: a head is read in the layout the cache was written in);
+ * PARQ_ERR_WORKSPACE for a short workspace or scratch.
+ * Which iteration last ran where is a host-side note of the handle, keyed by the workspace address: a call that rewrites a workspace
+ * drops the note on entry and leaves the new one once it has enqueued all its work (a forward that fails part-way leaves none).  The
+ * notes of the 256 most recently written workspaces are kept; the oldest goes first. */
+enum { PARQ_MAP_HEAD_MEAN = 0, PARQ_MAP_PER_HEAD = 1, PARQ_MAP_VIEW_MASS = 2 };
+enum { PARQ_MAP_F32 = 0, PARQ_MAP_F16 = 1 };
+size_t parq_attention_map_scratch_bytes(parq_handle h, int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t n_sel);
+int parq_attention_map(parq_handle h, const parq_scene *scene, const void *workspace, size_t workspace_bytes,
+                       const int32_t *query_index, int32_t n_sel, int32_t what, int32_t out_type, void *out, void *scratch,
+                       size_t scratch_bytes, parq_stream stream);
+
 /* Intra-scene view sharding ("split-N"; no reference analogue — the reference holds all views of a scene in one
  * process, model/transformer_parq.py:129-161, 377-380).  A scene whose K/V stream is too large or too slow for one GPU (BASELINE
  * cfg 5: 20 views of 240x320 features = 1.5 M keys) is split by VIEWS: every rank calls parq_prepare with ITS views (tokens,
@@ -257,7 +293,8 @@ int parq_iterate_sharded(parq_handle h, const parq_scene *scene, void *workspace
 
 /* Introspection for parity tests: where a named intermediate of the last parq_iterate lives
  * inside the workspace (offset and element count in floats).  Names: "T_camera_local_f64" and
- * "gn_sums_f64" (float64 payloads), "kv_cache", "ref", "ref_next", "posemb" (after an iteration: pos2posemb3d of the NEXT
+ * "gn_sums_f64" (float64 payloads), "kv_cache" (fp32 K / V; empty where the 16-bit cache is used), "kv_cache16" (that cache, raw: the block
+ * layouts of flash_split.hip / flash_split8.hip, one region per layer; empty otherwise), "ref", "ref_next", "posemb" (after an iteration: pos2posemb3d of the NEXT
  * reference points, written by the decode kernel), "pos_hidden" (relu of the position MLP's first layer for THIS iteration's
  * reference points), "pos_feat" (the position MLP's output; only written where its last layer is not folded into the two
  * in-projections that consume it, i.e. by the training forward), "tgt",

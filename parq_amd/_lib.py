@@ -67,6 +67,8 @@ SYMBOLS = {
     "parq_graph_destroy": (C.c_int, [_vp]),
     "parq_prepare": (C.c_int, [_vp, C.POINTER(ParqScene), _vp, _sz, _vp]),
     "parq_iterate": (C.c_int, [_vp, C.POINTER(ParqScene), _vp, _sz, _i32, _vp, C.POINTER(ParqOutputs), _vp, _vp]),
+    "parq_attention_map_scratch_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32]),
+    "parq_attention_map": (C.c_int, [_vp, C.POINTER(ParqScene), _vp, _sz, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "parq_workspace_lookup": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.c_char_p, C.POINTER(_sz), C.POINTER(_sz)]),
     "parq_set_attention_mode": (C.c_int, [_vp, _i32]),
     "parq_set_token_type": (C.c_int, [_vp, _i32]),

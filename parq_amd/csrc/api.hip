@@ -99,6 +99,18 @@ struct Workspace {
 
 struct ProfEvent { hipEvent_t a, b; int which; };
 
+// what the last call that ran an iteration in a workspace left there (host-side note, keyed by the workspace address): the layer whose
+// K cache that iteration read and the settings the cache was written under.  parq_attention_map reads "cross_q" and that cache.
+// A call that rewrites a workspace drops its note on entry and leaves a new one only once it has enqueued everything; the handle keeps
+// the kMapRecs most recently written notes (it never learns that a workspace was freed: a note for a freed address is only ever
+// replaced by the next call that runs at that address).
+struct MapRec {
+    int B, V, h, w, li, mode, tok, state;     // state: 1 inference / stepping iteration, 2 training forward, 3 view-sharded iteration
+    uint32_t safe;
+    uint64_t seq;                             // order of writing: the oldest note is the one evicted
+};
+constexpr size_t kMapRecs = 256;
+
 }  // namespace
 
 struct parq_ctx {
@@ -161,6 +173,17 @@ struct parq_ctx {
     std::vector<ProfEvent> events;
     double prof_ms[PARQ_PROF_COUNT] = {0};
     int64_t prof_n[PARQ_PROF_COUNT] = {0};
+    std::map<const void*, MapRec> map_recs;       // parq_attention_map: the last iteration of every workspace this handle ran in
+    void note_iteration(const void* wsp, const parq_scene* sc, int layer_num, int state) {
+        if (!map_recs.count(wsp) && map_recs.size() >= kMapRecs) {
+            auto oldest = map_recs.begin();
+            for (auto it = map_recs.begin(); it != map_recs.end(); ++it)
+                if (it->second.seq < oldest->second.seq) oldest = it;
+            map_recs.erase(oldest);
+        }
+        map_recs[wsp] = MapRec{sc->B, sc->V, sc->h, sc->w, cfg.share_weights ? 0 : layer_num, attn_mode, tok_type, state, safe_heads(), ++map_seq};
+    }
+    uint64_t map_seq = 0;
 };
 
 namespace {
@@ -1369,6 +1392,7 @@ int parq_prepare(parq_handle h, const parq_scene* scene, void* workspace, size_t
     Workspace ws;
     carve_workspace(h, scene->B, scene->V, scene->h, scene->w, &ws);
     if (workspace_bytes < (size_t)ws.total * sizeof(float)) return fail(PARQ_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, (size_t)ws.total * sizeof(float));
+    h->map_recs.erase(workspace);         // the K cache is rewritten: "cross_q" of an earlier iteration no longer belongs to it
     return do_prepare(h, scene, (float*)workspace, ws, (hipStream_t)stream);
 }
 
@@ -1387,12 +1411,14 @@ int parq_iterate(parq_handle h, const parq_scene* scene, void* workspace, size_t
     float* wsp = (float*)workspace;
     hipStream_t s = (hipStream_t)stream;
     const float* ref = ref_in ? ref_in : wsp + ws.ref;
+    h->map_recs.erase(workspace);         // "cross_q" is rewritten: the note returns once the iteration is enqueued whole
     rc = do_iterate(h, scene, wsp, ws, layer_num, ref, ref_in == nullptr && h->emb_valid, outs, wsp + ws.ref_next, s);
     h->emb_valid = (rc == PARQ_OK);        // the decode kernel left pos2posemb3d(ref_next) in the workspace
     if (rc) return rc;
     const size_t rb = (size_t)scene->B * h->Q * 3 * sizeof(float);
     HIPCHK(hipMemcpyAsync(wsp + ws.ref, wsp + ws.ref_next, rb, hipMemcpyDeviceToDevice, s));
     if (ref_out) HIPCHK(hipMemcpyAsync(ref_out, wsp + ws.ref_next, rb, hipMemcpyDeviceToDevice, s));
+    h->note_iteration(workspace, scene, layer_num, 1);
     return PARQ_OK;
 }
 
@@ -1425,6 +1451,7 @@ int parq_iterate_sharded(parq_handle h, const parq_scene* scene, void* workspace
     const float* ref = ref_in ? ref_in : wsp + ws.ref;
     ShardIO sh;
     sh.mask = 1 << phase; sh.in = xchg_in; sh.out = xchg_out; sh.nranks = nranks;
+    h->map_recs.erase(workspace);
     rc = do_iterate(h, scene, wsp, ws, layer_num, ref, ref_in == nullptr && h->emb_valid, outs, wsp + ws.ref_next, s, 0, nullptr, false, sh);
     if (rc) return rc;
     if (phase == 2) {
@@ -1433,6 +1460,7 @@ int parq_iterate_sharded(parq_handle h, const parq_scene* scene, void* workspace
         HIPCHK(hipMemcpyAsync(wsp + ws.ref, wsp + ws.ref_next, rb, hipMemcpyDeviceToDevice, s));
         if (ref_out) HIPCHK(hipMemcpyAsync(ref_out, wsp + ws.ref_next, rb, hipMemcpyDeviceToDevice, s));
     }
+    h->note_iteration(workspace, scene, layer_num, 3);
     return PARQ_OK;
 }
 
@@ -1480,9 +1508,12 @@ int parq_forward(parq_handle h, const parq_scene* scene, void* workspace, size_t
     Workspace ws;
     int rc = forward_checks(h, scene, workspace, workspace_bytes, outs, &ws);
     if (rc) return rc;
+    h->map_recs.erase(workspace);         // the cache and "cross_q" are rewritten: the note returns once the forward is enqueued whole
     rc = do_prepare(h, scene, (float*)workspace, ws, (hipStream_t)stream, false, nullptr, true);
     if (rc) return rc;
-    return forward_iterations(h, scene, (float*)workspace, ws, outs, (hipStream_t)stream, false);
+    rc = forward_iterations(h, scene, (float*)workspace, ws, outs, (hipStream_t)stream, false);
+    if (rc == PARQ_OK) h->note_iteration(workspace, scene, h->I - 1, 1);
+    return rc;
 }
 
 /* ---- a captured forward (include/parq_hip.h) ---------------------------------------------------------------------------------- */
@@ -1558,12 +1589,77 @@ int parq_forward_replay(parq_handle h, parq_graph_t g, const parq_scene* scene, 
         return fail(PARQ_ERR_STATE, "parq_forward_replay: the graph was recorded for another shape / workspace / weight arena / range mirror or under "
                                     "other attention settings (mode, head tiers, seam fusion) or token type: capture again");
     hipStream_t s = (hipStream_t)stream;
+    h->map_recs.erase(workspace);
     // launched directly with THIS call's pointers: prologue (which also leaves them in the workspace for the recorded part) + K/V projection
     rc = do_prepare(h, scene, (float*)workspace, ws, s, false, outs, true);
     if (rc) return rc;
     HIPCHK(hipGraphLaunch(g->exec, s));
     h->ref_state = 0;
     h->prepared = false;
+    h->note_iteration(workspace, scene, h->I - 1, 1);
+    return PARQ_OK;
+}
+
+/* ---- cross-attention maps (include/parq_hip.h; attn_map.hip) --------------------------------------------------------------------- */
+size_t parq_attention_map_scratch_bytes(parq_handle h, int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t n_sel) {
+    if (!h || B < 1 || V < 1 || hh < 1 || ww < 1) return 0;
+    if ((int64_t)V * hh * ww > INT32_MAX) return 0;
+    const int nsel = n_sel > 0 ? n_sel : h->Q;
+    return attn_map_scratch_bytes(B, h->H, h->dh, V * hh * ww, V, hh * ww, nsel);
+}
+
+int parq_attention_map(parq_handle h, const parq_scene* scene, const void* workspace, size_t workspace_bytes, const int32_t* query_index,
+                       int32_t n_sel, int32_t what, int32_t out_type, void* out, void* scratch, size_t scratch_bytes, parq_stream stream) {
+    if (!h || !workspace || !out || !scratch) return fail(PARQ_ERR_ARG, "NULL argument");
+    if (!scene || scene->B < 1 || scene->V < 1 || scene->h < 2 || scene->w < 2) return fail(PARQ_ERR_ARG, "bad scene dims");
+    if (what < 0 || what > 2) return fail(PARQ_ERR_ARG, "what must be 0 (head mean), 1 (per head) or 2 (view mass)");
+    if (out_type != PARQ_MAP_F32 && out_type != PARQ_MAP_F16) return fail(PARQ_ERR_ARG, "out_type must be 0 (fp32) or 1 (fp16)");
+    if (query_index ? n_sel < 1 : (n_sel != 0 && n_sel != h->Q)) return fail(PARQ_ERR_ARG, "n_sel must be >= 1 with query_index, 0 or num_queries without");
+    if (((uintptr_t)scratch & 15) != 0) return fail(PARQ_ERR_ARG, "scratch must be 16-byte aligned");
+    const auto it = h->map_recs.find(workspace);
+    if (it == h->map_recs.end()) return fail(PARQ_ERR_STATE, "parq_attention_map: no iteration has run in this workspace since it was prepared");
+    const MapRec& r = it->second;
+    if (r.state == 2) return fail(PARQ_ERR_STATE, "parq_attention_map: the last call in this workspace was a training forward; maps are computed after inference forwards and parq_iterate only");
+    if (r.state == 3) return fail(PARQ_ERR_STATE, "parq_attention_map: the last iteration in this workspace was view-sharded (its keys are one rank's views); not supported");
+    if (r.B != scene->B || r.V != scene->V || r.h != scene->h || r.w != scene->w) return fail(PARQ_ERR_ARG, "parq_attention_map: the scene dims differ from those of the iteration that ran in this workspace");
+    if (r.mode != h->attn_mode || r.tok != h->tok_type)
+        return fail(PARQ_ERR_STATE, "parq_attention_map: attention mode / token type changed since the iteration ran (the workspace is carved differently)");
+    const int B = scene->B, V = scene->V, C = h->C;
+    const int64_t N64 = (int64_t)V * scene->h * scene->w;
+    if (N64 > INT32_MAX) return fail(PARQ_ERR_ARG, "too many keys");
+    const int N = (int)N64;
+    Workspace ws;
+    carve_workspace(h, B, V, scene->h, scene->w, &ws);
+    if (workspace_bytes < (size_t)ws.total * sizeof(float)) return fail(PARQ_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, (size_t)ws.total * sizeof(float));
+    const int nsel = query_index ? n_sel : h->Q;
+    const size_t need = attn_map_scratch_bytes(B, h->H, h->dh, N, V, scene->h * scene->w, nsel);
+    if (scratch_bytes < need) return fail(PARQ_ERR_WORKSPACE, "scratch too small: %zu < %zu", scratch_bytes, need);
+    const float* wsp = reinterpret_cast<const float*>(workspace);
+    AttnMapArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = B; a.H = h->H; a.dh = h->dh; a.C = C; a.N = N; a.V = V; a.hw = scene->h * scene->w; a.nsel = nsel;
+    a.what = what; a.out_f16 = out_type == PARQ_MAP_F16; a.out = out;
+    if (h->cache_mode()) {
+        // the layer's cache, read as the forward's cross-attention reads it (do_iterate)
+        a.kbase = reinterpret_cast<const char*>(wsp + ws.kvc) + (size_t)r.li * kvsplit_cache_bytes(B, h->vheads(), N, h->terms());
+        const int nblk = (N + 31) / 32;
+        // (the head tiers the cache was WRITTEN under, which a guard may have changed on the handle since: ctx terms_for with r.safe)
+        const bool m4 = h->attn_mode == 4 && C == 256 && flash_split8_supported(h->dh, N);
+        const int tf = (m4 && r.safe != h->all_heads()) ? 8 : h->terms();
+        if (tf == 8) {
+            a.klayout = kMapStage8;
+            a.safe_mask = r.safe;
+            a.head_bytes = a.safe_mask ? (int64_t)kvsplit_cache_bytes(1, 1, N, 3) : (int64_t)(N / 64) * kStage8Bytes;
+        } else if (tf == 3) {
+            a.klayout = kMapSplit3; a.head_bytes = (int64_t)nblk * 16384;
+        } else {
+            a.klayout = h->kind() == kBF16 ? kMapBF16 : kMapF16; a.head_bytes = (int64_t)nblk * 8192;
+        }
+    } else {
+        a.klayout = kMapF32;
+        a.kbase = wsp + ws.kv + (int64_t)r.li * B * 2 * N * C;
+    }
+    HIPCHK(launch_attn_map(a, wsp + ws.qc, query_index, h->Q, scratch, (hipStream_t)stream));
     return PARQ_OK;
 }
 
@@ -1598,6 +1694,7 @@ int parq_workspace_lookup(parq_handle h, int32_t B, int32_t V, int32_t hh, int32
     const E table[] = {
         {"T_camera_local_f64", ws.T_cl, (int64_t)B * V * 24},
         {"kv_cache", ws.kv, h->cache_mode() ? 0 : (int64_t)h->nl * B * 2 * N * C},
+        {"kv_cache16", ws.kvc, h->cache_mode() ? (int64_t)(h->nl * kvsplit_cache_bytes(B, h->vheads(), (int)N, h->terms()) / sizeof(float)) : 0},
         {"ref", ws.ref, M * 3}, {"ref_next", ws.ref_next, M * 3}, {"posemb", ws.emb, M * 384}, {"pos_hidden", ws.pe_h, M * C}, {"pos_feat", ws.pos, M * C},
         {"tgt", ws.tgt, M * C}, {"self_qkv", ws.qkv, M * 3 * C}, {"attn", ws.attn, M * C}, {"xa_prenorm1", ws.xa, M * C},
         {"cross_q", ws.qc, M * C}, {"xb_prenorm2", ws.xb, M * C}, {"ffn_hidden", ws.ffn, M * F},
@@ -1689,6 +1786,7 @@ int parq_forward_train(parq_handle h, const parq_scene* scene, void* workspace, 
     if (workspace_bytes < (size_t)ws.train_total * sizeof(float)) return fail(PARQ_ERR_WORKSPACE, "training workspace too small: %zu < %zu", workspace_bytes, (size_t)ws.train_total * sizeof(float));
     float* wsp = (float*)workspace;
     hipStream_t s = (hipStream_t)stream;
+    h->note_iteration(workspace, scene, h->I - 1, 2);     // (before anything is enqueued: whatever an inference forward left here is gone)
     rc = do_prepare(h, scene, wsp, ws, s, true);
     if (rc) return rc;
     const int64_t M = (int64_t)scene->B * h->Q;

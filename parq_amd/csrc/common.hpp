@@ -540,6 +540,25 @@ hipError_t launch_kvsplit8_convert(const float* K, const float* V, int64_t k_bat
 hipError_t launch_flash_split8(const FlashArgs& a, const void* cache, hipStream_t s);
 // attention modes 2 / 3 on whole 64-key stages of the single-product cache (flash_split8.hip); flash_split8_supported(dh, Lk) says where
 hipError_t launch_flash_single_stage(const FlashArgs& a, const void* cache, hipStream_t s, int kind);
+// attn_map.hip: the cross-attention probabilities of a finished iteration, recomputed from its projected queries and the K cache
+// (parq_attention_map).  klayout says how K of a head is stored; kMapStage8 with safe_mask: head h is in the split layout where bit h is set.
+enum : int { kMapF32 = 0, kMapSplit3 = 1, kMapF16 = 2, kMapBF16 = 3, kMapStage8 = 4 };
+struct AttnMapArgs {
+    const void* kbase;          // fp32 head-major K/V of the layer ([b][K heads | V heads][N][dh]) or the layer's cache
+    int klayout; unsigned safe_mask;
+    int64_t head_bytes;         // cache layouts: bytes between the regions of two (scene, 64-dim cache head) pairs
+    int B, H, dh, C, N, V, hw;  // hw = keys per view (N = V * hw)
+    int nsel;                   // selected query rows
+    int what, out_f16;          // 0 head mean (B, nsel, N) | 1 per head (B, H, nsel, N) | 2 view mass (B, nsel, V); element type of out
+    void* out;
+    // filled by launch_attn_map from the scratch
+    int qtiles, nsel_pad, nsplit, nseg;
+    float scale_log2;
+    const half8* qfrag;
+    float* part_m; float* part_l; float* stat_m; float* stat_il; float* vpart;
+};
+size_t attn_map_scratch_bytes(int B, int H, int dh, int N, int V, int hw, int nsel);
+hipError_t launch_attn_map(AttnMapArgs a, const float* cross_q, const int* query_index, int Q, void* scratch, hipStream_t s);
 // kvproj_split.hip: tokens -> split cache directly (W pre-split with launch_split_f32)
 hipError_t launch_split_f32(const float* src, void* hi, void* lo, int64_t n, hipStream_t s);
 // elementwise.hip: up to kGatherMax device-to-device float copies in ONE launch (the weight pack: ~50 tensors per training step)

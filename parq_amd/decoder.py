@@ -1064,6 +1064,7 @@ class PARQDecoder(_Tracked, nn.Module):
         else:
             _lib.check(lib.parq_forward(h, C.byref(sc), _lib.ptr(ws), ws.numel() * 4, C.byref(po), stream), "parq_forward")
         self._mark_first_forward(dev)
+        self._map_note(dev, "infer")                        # cross_attention_map: this stream's workspace holds an inference forward
         return run
 
     def _capture(self, entry, key, sc, stream):
@@ -1122,6 +1123,7 @@ class PARQDecoder(_Tracked, nn.Module):
                 self._train_ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=dev)
             _lib.check(lib.parq_forward_train(h, C.byref(sc), _lib.ptr(self._train_ws), self._train_ws.numel() * 4, C.byref(po),
                                               _lib.stream_ptr()), "parq_forward_train")
+            self._map_note(dev, "train")                      # cross_attention_map refuses on this stream: inference and stepping only
             self._mark_first_forward(dev)
             # the stash is laid out for `mode`: backward() uses exactly this mode, whatever attention_mode says by then
             self._train_state = (sc, keep, outs, po, dev, mode, p_drop, seed)
@@ -1259,6 +1261,7 @@ class PARQDecoder(_Tracked, nn.Module):
         _lib.check(_lib.load().parq_iterate(h, C.byref(sc), _lib.ptr(ws), ws.numel() * 4, int(layer_num),
                                             _lib.ptr(ref_in), C.byref(po), _lib.ptr(nxt), _lib.stream_ptr()),
                    "parq_iterate")
+        self._map_note(dev, "infer")
         return dict(zip(OUTPUT_KEYS, outs)), nxt
 
     @torch.no_grad()
@@ -1389,6 +1392,98 @@ class PARQDecoder(_Tracked, nn.Module):
         _lib.check(_lib.load().parq_workspace_lookup(self._handle(), sc.B, sc.V, sc.h, sc.w, name.encode(),
                                                      C.byref(off), C.byref(n)), "parq_workspace_lookup")
         return ws[off.value: off.value + n.value]
+
+    # ------------------------------------------------------------------ cross-attention maps (include/parq_hip.h parq_attention_map)
+    def _map_note(self, dev, kind):
+        """What last ran on the current stream of `dev`: "infer" (a forward or an iteration in an inference workspace) or "train".
+        Per stream, like the inference workspaces (a training forward that switches the handle's mode drops those of every stream:
+        _handle_in_mode; the map call then finds none and raises)."""
+        last, key = self.__dict__.setdefault("_map_last", {}), (dev.index, _raw_stream(dev))
+        last.pop(key, None)
+        last[key] = kind                                   # (re-)insert as the most recent
+        while len(last) > 64:
+            last.pop(next(iter(last)))
+
+    def _map_call(self, queries, what, dtype, out):
+        last = self.__dict__.get("_map_last", {})
+        if not last:
+            raise RuntimeError("parq_amd.PARQDecoder: no cross-attention map yet — call it after an inference forward() or an iterate(k)")
+        if dtype not in (torch.float32, torch.float16):
+            raise ValueError("cross-attention maps come as torch.float32 or torch.float16, not %s" % (dtype,))
+        hd = self._handle()                                # first: a pending mode change drops the cached workspaces
+        found = None
+        for k in reversed(list(self._ws)):                 # most recently used first; the one this stream's forwards ran in
+            dev = torch.device("cuda", k[4])
+            if _raw_stream(dev) == k[5]:
+                found = (k, self._ws[k], dev)
+                break
+        if found is not None:
+            kind = last.get((found[0][4], found[0][5]))    # the note of the workspace's own (device, stream)
+        else:                                              # no workspace: what last ran on a stream that is current on its device
+            kind = next((v for (d, st), v in reversed(list(last.items())) if _raw_stream(torch.device("cuda", d)) == st), None)
+        if kind == "train":
+            raise RuntimeError("parq_amd.PARQDecoder: cross-attention maps after a training forward are out of scope (its queries live in "
+                               "the per-iteration stash, its probabilities see dropout); run an inference forward() under torch.no_grad() "
+                               "or prepare() / iterate(k) first")
+        if found is None:
+            raise RuntimeError("parq_amd.PARQDecoder: no inference workspace of the current stream holds a forward (with InFlight, call "
+                               "this on the ticket's stream after result())")
+        (B, V, h, w), entry, dev = found[0][:4], found[1], found[2]
+        lib = _lib.load()
+        Q, H = self.num_queries, self.num_heads
+        idx = None
+        nsel = Q
+        if isinstance(queries, torch.Tensor) and queries.device == dev and queries.dtype in (torch.int32, torch.int64):
+            # an index tensor staged on the device is used as it is: no copy back to check it (the kernel clamps an index into [0, Q))
+            idx = queries.reshape(-1).to(torch.int32).contiguous()
+            nsel = idx.numel()
+            if nsel == 0:
+                raise IndexError("queries must be a non-empty selection of indices in [0, %d)" % Q)
+        elif queries is not None:
+            idx = torch.as_tensor(queries, device="cpu").reshape(-1).to(torch.int64)
+            if idx.numel() == 0 or int(idx.min()) < 0 or int(idx.max()) >= Q:
+                raise IndexError("queries must be a non-empty selection of indices in [0, %d)" % Q)
+            nsel = idx.numel()
+            idx = idx.to(device=dev, dtype=torch.int32)
+        shape = {0: (B, nsel, V, h, w), 1: (B, H, nsel, V, h, w), 2: (B, nsel, V)}[what]
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
+            raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (dtype, shape, dev))
+        sc = _lib.ParqScene(B, V, h, w, None, None, None, None, None)
+        nb = lib.parq_attention_map_scratch_bytes(hd, B, V, h, w, nsel)
+        scratch = torch.empty((nb + 3) // 4, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.parq_attention_map(hd, C.byref(sc), _lib.ptr(entry.ws), entry.ws.numel() * 4,
+                                              None if idx is None else C.c_void_p(idx.data_ptr()), 0 if idx is None else nsel, what,
+                                              1 if dtype == torch.float16 else 0, C.c_void_p(out.data_ptr()), _lib.ptr(scratch),
+                                              scratch.numel() * 4, C.c_void_p(_raw_stream(dev))), "parq_attention_map")
+        return out
+
+    @torch.no_grad()
+    def cross_attention_map(self, queries=None, per_head=False, dtype=torch.float32, out=None):
+        """The cross-attention probabilities of the last iteration that ran on the current stream: after an inference ``forward()``
+        the last iteration's, after ``iterate(k)`` that iteration's.  Returns ``(B, Qsel, V, h, w)`` — the mean over the heads, what
+        the reference's ``nn.MultiheadAttention(need_weights=True)`` computes and drops (model/transformer_parq.py:377-380) — or
+        ``(B, H, Qsel, V, h, w)`` with ``per_head``; every row sums to 1 over ``(V, h, w)``.  ``queries``: an index tensor or list
+        (any order, repeats allowed; default all ``num_queries`` rows; checked on the host, except an integer tensor already on the
+        device, which is used as it is with its indices clamped into range).  ``dtype``: ``torch.float32`` or ``torch.float16``; ``out``:
+        a tensor of that shape to write into.  Computed by HIP kernels from what the forward left in its workspace (the projected
+        queries and the K cache, i.e. with the keys the forward's cache holds; q is split hi / lo in fp16 and the scores are fp16 x 3
+        products whatever the mode: include/parq_hip.h parq_attention_map); the forward itself is untouched and nothing is stored
+        during it.  Reads the most recently used workspace of the current stream and only enqueues on it.  Under
+        ``range_check = "sync"`` a re-run forward leaves the re-run's queries and cache there: after heads were moved to the
+        fp16 x 3 tier the map describes the numbers that were returned; after a range fallback (mode "fp32" because a token or K
+        element reached 60000) the heads holding an element beyond the fp16 range come out non-finite — the kernels split fp32 keys
+        into fp16 hi / lo.  With ``InFlight``: call it under the ticket's stream after ``result()``.  RuntimeError before any
+        forward and after a training forward on the same stream (out of scope)."""
+        return self._map_call(queries, 1 if per_head else 0, dtype, out)
+
+    @torch.no_grad()
+    def cross_attention_view_mass(self, queries=None):
+        """``(B, Qsel, V)``: how much of each query's head-averaged attention falls into each view — ``cross_attention_map`` summed
+        over ``(h, w)``, without writing the map; bit-identical from call to call."""
+        return self._map_call(queries, 2, torch.float32, None)
 
     # ------------------------------------------------------------------ profiling hooks used by bench.py
     def profile_enable(self, on=True):
