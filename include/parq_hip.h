@@ -147,10 +147,25 @@ int parq_set_attention_mode(parq_handle h, int32_t mode);
  * projection and project + sample read half the bytes and no fp32 copy exists (attention mode 0, and head dims without the split
  * cache, widen into the workspace instead: it grows by B*N*C floats there).  The range check of modes 1 and 2 sees the same values.
  * parq_forward_capture records the type; parq_forward_replay refuses (PARQ_ERR_STATE) a graph recorded under another one.
- * Training (parq_forward_train, parq_backward) and parq_iterate_sharded read fp32 tokens only and return PARQ_ERR_ARG otherwise.
+ * Training (parq_forward_train, parq_backward) reads that type only after parq_set_train_token_type named it too (below) and returns
+ * PARQ_ERR_ARG otherwise; parq_iterate_sharded reads fp32 tokens only (view sharding is outside the 16-bit path).
  * Default PARQ_TOKENS_F32; an unknown type is PARQ_ERR_ARG. */
 enum { PARQ_TOKENS_F32 = 0, PARQ_TOKENS_F16 = 1, PARQ_TOKENS_BF16 = 2 };
 int parq_set_token_type(parq_handle h, int32_t type);
+/* The element type parq_forward_train / parq_backward accept (the opt-in to training on 16-bit tokens): both run when the handle's
+ * token type (above) EQUALS this one, and refuse with PARQ_ERR_ARG otherwise — a caller who switched the inference type and forgot
+ * the training side gets an error, not 16-bit rows read as floats (and the other way round).  With both set to a 16-bit type the
+ * training forward reads the caller's rows as the inference forward does, and the three token readers of the backward — the K/V
+ * projection's weight gradient (split-precision and generic kernels) and the coordinate gradient of project + sample — widen them in
+ * registers: outputs and gradients are those of the same calls on the fp32 copy of the tokens, and no such copy exists (attention
+ * mode 0 / head dims without the split cache keep the widened workspace copy of parq_set_token_type, which the backward then reads;
+ * parq_train_workspace_bytes follows the token type as parq_workspace_bytes does).  fp16 tokens cost the split-precision weight
+ * gradient two matrix products instead of three (an fp16 value has no low half).
+ * `d_tokens` of parq_backward stays fp32 in every type: the token gradient accumulates in fp32 from two sources (the float atomics or
+ * the gather of project + sample, then the g W_kv product added on top), so a 16-bit result would need a second dense fp32 buffer or
+ * two roundings; the caller rounds it once (autograd casts it to the tokens' dtype anyway).
+ * Default PARQ_TOKENS_F32; an unknown type is PARQ_ERR_ARG. */
+int parq_set_train_token_type(parq_handle h, int32_t type);
 /* Per-head tiers of attention mode 4 (inference; head dim 64, dim 256, at most 16 heads).  Bit h of `safe_mask` moves head h to the
  * fp16 x 3 arithmetic of mode 1 INSIDE a mode-4 forward: the K/V projection writes that head's cache region in the split layout, the
  * cross-attention of an iteration runs as two launches over complementary head sets (flash_split8_kernel over the others,

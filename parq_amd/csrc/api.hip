@@ -128,6 +128,7 @@ struct parq_ctx {
     int attn_mode = 1;                // 0: fp32 MFMA, 1: split fp16x3, 2: fp16, 3: bf16 (1..3: head dims 64 and 256), 4: split with fp8 cross terms
     int kv16_state = 1;               // what the arena's 16-bit W_kv copy currently holds (same numbering)
     int tok_type = 0;                 // parq_set_token_type: element type of every scene's tokens (kTokF32 / kTokF16 / kTokBF16)
+    int train_tok_type = 0;           // parq_set_train_token_type: the type parq_forward_train / parq_backward accept (they run when it equals tok_type)
     float drop_p = 0.f;               // training dropout (decoder layer, transformer_parq.py:339-386) and its base seed
     uint32_t drop_seed = 0;
     uint32_t site_seed(int k, int site) const { return rng_stream(drop_seed, (uint32_t)(k * 8 + site)); }
@@ -383,6 +384,17 @@ int carve_workspace(const parq_ctx* c, int B, int V, int h, int w, Workspace* ws
     ws->g_det = take(ws->g_det_floats);
     ws->train_total = off;
     return PARQ_OK;
+}
+
+// the tokens as the backward reads them: the caller's rows in the handle's token type, or — attention mode 0 / head dims without the
+// split cache, where the training forward widened 16-bit tokens into the workspace (do_prepare) — that fp32 copy
+const void* bwd_tokens(const parq_ctx* c, const parq_scene* sc, const float* wsp, const Workspace& ws, int* type) {
+    if (c->tok_type != kTokF32 && !c->cache_mode()) {
+        *type = kTokF32;
+        return wsp + ws.tok32;
+    }
+    *type = c->tok_type;
+    return sc->tokens;
 }
 
 int check_scene(const parq_ctx* c, const parq_scene* s) {
@@ -1111,8 +1123,12 @@ int do_backward_iter(parq_ctx* c, const parq_scene* sc, float* wsp, const Worksp
         HIPCHK(launch_add(gC, gB, gC, (int64_t)M * C, s));                                      // gC = d / d tgt
     }
     // ---- project + sample (transformer_parq.py:321)
-    HIPCHK(launch_sample_bwd(sc->tokens, reinterpret_cast<const double*>(wsp + ws.T_cl), sc->camera, ref, c->sb, B, sc->V, sc->h, sc->w,
-                             C, Q, gC, g_tokens, k == 0 ? gRef : nullptr, s));
+    {
+        int tt;
+        const void* tok = bwd_tokens(c, sc, wsp, ws, &tt);
+        HIPCHK(launch_sample_bwd(tok, reinterpret_cast<const double*>(wsp + ws.T_cl), sc->camera, ref, c->sb, B, sc->V, sc->h, sc->w,
+                                 C, Q, gC, g_tokens, k == 0 ? gRef : nullptr, s, tt));
+    }
     // ---- position MLP (transformer_parq.py:176-180,317): pos = relu(emb W0^T + b0) W2^T + b2
     HIPCHK(launch_gemm_tn(gPos, C, wi + ws.pe_h, C, G + ar.pe2_w, C, M, C, C, acc, s, G + ar.pe2_b));
     {
@@ -1138,6 +1154,9 @@ int do_backward_kvproj(parq_ctx* c, const parq_scene* sc, float* wsp, const Work
     const int64_t N = (int64_t)sc->V * sc->h * sc->w;
     if ((int64_t)B * N > (int64_t)INT32_MAX) return fail(PARQ_ERR_ARG, "B*N too large");
     float* wT = wsp + ws.wT;            // W_kv^T [C][2C]
+    int tt;
+    const void* tok = bwd_tokens(c, sc, wsp, ws, &tt);
+    const size_t tb = tt == kTokF32 ? 4 : 2;
     for (int li = 0; li < c->nl; ++li) {
         const LayerW& L = c->ar.layers[li];
         const float* g = wsp + ws.g_kv + (int64_t)li * B * 2 * N * C;          // [B*N][2C]
@@ -1146,8 +1165,8 @@ int do_backward_kvproj(parq_ctx* c, const parq_scene* sc, float* wsp, const Work
         const bool split_ok = ws.bwd_batched && !split_off;                      // the batched backward leaves max |g| in g_kvmax
         if (split_ok && kvproj_bwd_split_supported(C)) {
             // dW, db on the fp16 matrix pipe (hi/lo split); g is scaled by the power of two derived from max |g| (attention epilogue)
-            HIPCHK(launch_kvproj_bwd_split(g, sc->tokens, Mr, C, G + L.cross_in_w + (int64_t)C * C, G + L.cross_in_b + C,
-                                           reinterpret_cast<const unsigned int*>(wsp + ws.g_kvmax), wsp + ws.g_kvmax + 1, s));
+            HIPCHK(launch_kvproj_bwd_split(g, tok, Mr, C, G + L.cross_in_w + (int64_t)C * C, G + L.cross_in_b + C,
+                                           reinterpret_cast<const unsigned int*>(wsp + ws.g_kvmax), wsp + ws.g_kvmax + 1, s, tt));
         } else if (split_ok && C % 256 == 0) {
             // wider models (C = 1024: 805 GFLOP): the same kernel per 512 x 256 block of dW_kv; the bias gradient falls out of the
             // blocks of the first column slice
@@ -1155,10 +1174,11 @@ int do_backward_kvproj(parq_ctx* c, const parq_scene* sc, float* wsp, const Work
             float* db = G + L.cross_in_b + C;
             for (int n0 = 0; n0 < 2 * C; n0 += 512)
                 for (int k0 = 0; k0 < C; k0 += 256)
-                    HIPCHK(launch_tn_split_512x256(g + n0, 2 * C, sc->tokens + k0, C, Mr, dW + (int64_t)n0 * C + k0, C, k0 == 0 ? db + n0 : nullptr,
-                                                   reinterpret_cast<const unsigned int*>(wsp + ws.g_kvmax), wsp + ws.g_kvmax + 1, s));
+                    HIPCHK(launch_tn_split_512x256(g + n0, 2 * C, reinterpret_cast<const char*>(tok) + k0 * tb, C, Mr, dW + (int64_t)n0 * C + k0, C,
+                                                   k0 == 0 ? db + n0 : nullptr, reinterpret_cast<const unsigned int*>(wsp + ws.g_kvmax),
+                                                   wsp + ws.g_kvmax + 1, s, tt));
         } else {
-            HIPCHK(launch_gemm_tn(g, 2 * C, sc->tokens, C, G + L.cross_in_w + (int64_t)C * C, C, Mr, 2 * C, C, 1, s));
+            HIPCHK(launch_gemm_tn(g, 2 * C, tok, C, G + L.cross_in_w + (int64_t)C * C, C, Mr, 2 * C, C, 1, s, nullptr, 0, tt));
             HIPCHK(launch_colsum(g, 2 * C, Mr, 2 * C, G + L.cross_in_b + C, 1, s));
         }
         if (g_tokens) {
@@ -1724,6 +1744,13 @@ int parq_set_token_type(parq_handle h, int32_t type) {
     return PARQ_OK;
 }
 
+int parq_set_train_token_type(parq_handle h, int32_t type) {
+    if (!h) return fail(PARQ_ERR_ARG, "NULL handle");
+    if (type != kTokF32 && type != kTokF16 && type != kTokBF16) return fail(PARQ_ERR_ARG, "token type must be 0 (fp32), 1 (fp16) or 2 (bf16), not %d", type);
+    h->train_tok_type = type;
+    return PARQ_OK;
+}
+
 int parq_set_head_tiers(parq_handle h, uint32_t safe_mask, int32_t poison_on_peaked) {
     if (!h) return fail(PARQ_ERR_ARG, "NULL handle");
     if (safe_mask != 0 && h->H > 16) return fail(PARQ_ERR_ARG, "per-head tiers need at most 16 heads");
@@ -1774,7 +1801,8 @@ size_t parq_grad_arena_bytes(parq_handle h) { return h ? (size_t)h->ar.rowmajor_
 int parq_forward_train(parq_handle h, const parq_scene* scene, void* workspace, size_t workspace_bytes, const parq_outputs* outs,
                        parq_stream stream) {
     if (!h || !workspace) return fail(PARQ_ERR_ARG, "NULL argument");
-    if (h->tok_type != kTokF32) return fail(PARQ_ERR_ARG, "parq_forward_train reads fp32 tokens only: set token type 0");
+    if (h->tok_type != h->train_tok_type)
+        return fail(PARQ_ERR_ARG, "parq_forward_train reads fp32 tokens only unless parq_set_train_token_type names the token type (token type %d, training token type %d)", h->tok_type, h->train_tok_type);
     if (!h->packed) return fail(PARQ_ERR_STATE, "parq_pack_weights must be called first");
     if (h->dh % 16 != 0) return fail(PARQ_ERR_ARG, "training needs a head dim that is a multiple of 16");
     int rc = check_scene(h, scene);
@@ -1842,7 +1870,8 @@ int parq_wait_iteration(parq_handle h, int32_t k) {
 int parq_backward(parq_handle h, const parq_scene* scene, void* workspace, size_t workspace_bytes, const parq_outputs* outs,
                   const parq_output_grads* g, float* grad_arena, float* d_tokens, parq_stream stream) {
     if (!h || !workspace || !outs || !g || !grad_arena) return fail(PARQ_ERR_ARG, "NULL argument");
-    if (h->tok_type != kTokF32) return fail(PARQ_ERR_ARG, "parq_backward reads fp32 tokens only: set token type 0");
+    if (h->tok_type != h->train_tok_type)
+        return fail(PARQ_ERR_ARG, "parq_backward reads fp32 tokens only unless parq_set_train_token_type names the token type (token type %d, training token type %d)", h->tok_type, h->train_tok_type);
     if (!h->packed) return fail(PARQ_ERR_STATE, "parq_pack_weights must be called first");
     int rc = check_scene(h, scene);
     if (rc) return rc;

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
 // 4 waves owns a 32x32 output tile, the waves split the rows and reduce through LDS.
 struct TnArgs {
     const float* A; int64_t lda;
-    const float* B; int64_t ldb;
+    const void* B; int64_t ldb;       // fp32; gemm_tn_kernel<TT>: elements of token type TT, widened as they are loaded
     float* out; int64_t ldo;
     int M, N, K;
     int accumulate;     // 0 overwrite, 1 add (the launch owns out), 2 add with atomics (launches on other streams add to out too)
@@ -58,6 +58,8 @@ struct TnArgs {
 // 5 TFLOP/s.  A workgroup owns a 64 x 64 output tile; 32 rows of both operands are staged per step as they lie in memory
 // ([m][64 columns], coalesced 256-byte row pieces) — for a contraction over m that layout IS the operand layout of
 // v_mfma_f32_32x32x2_f32 (lane = column, two consecutive m per instruction), so no transposes: 16 MFMAs per wave and step.
+// TT: element type of B (16-bit memory tokens: one 16-byte piece = 8 columns, widened before the LDS write)
+template <int TT>
 __global__ __launch_bounds__(256) void gemm_tn_tile64_kernel(TnArgs a) {
     __shared__ __attribute__((aligned(16))) float As[2][32][64 + 32];      // dY rows m, columns n0 .. n0 + 63 (96-float rows: the two m of
     __shared__ __attribute__((aligned(16))) float Bs[2][32][64 + 32];      // an instruction read disjoint halves of the 64 banks)
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(256) void gemm_tn_tile64_kernel(TnArgs a) {
     float4 ra[2], rb[2];
     // 16-byte loads where base and row stride allow them (row slices of wider buffers need not be aligned)
     const bool avec = ((reinterpret_cast<uintptr_t>(a.A) & 15) == 0) && (a.lda % 4 == 0);
-    const bool bvec = ((reinterpret_cast<uintptr_t>(a.B) & 15) == 0) && (a.ldb % 4 == 0);
+    const bool bvec = ((reinterpret_cast<uintptr_t>(a.B) & 15) == 0) && (a.ldb % (TT == kTokF32 ? 4 : 8) == 0);
     auto fetch = [&](int m0) {
         const int m = m0 + sr;
 #pragma unroll
@@ -84,7 +86,8 @@ __global__ __launch_bounds__(256) void gemm_tn_tile64_kernel(TnArgs a) {
         }
         if (m < a.M) {
             const float* ap = a.A + (int64_t)m * a.lda + n0 + sc;
-            const float* bp = a.B + (int64_t)m * a.ldb + k0 + sc;
+            const int64_t bo = (int64_t)m * a.ldb + k0 + sc;
+            const float* bp = reinterpret_cast<const float*>(a.B) + bo;        // (fp32 B)
             if (n0 + sc + 8 <= a.N && avec) { ra[0] = *reinterpret_cast<const float4*>(ap); ra[1] = *reinterpret_cast<const float4*>(ap + 4); }
             else {
                 float t[8];
@@ -92,7 +95,15 @@ __global__ __launch_bounds__(256) void gemm_tn_tile64_kernel(TnArgs a) {
                 for (int e = 0; e < 8; ++e) t[e] = n0 + sc + e < a.N ? ap[e] : 0.f;
                 ra[0] = float4{t[0], t[1], t[2], t[3]}; ra[1] = float4{t[4], t[5], t[6], t[7]};
             }
-            if (k0 + sc + 8 <= a.K && bvec) { rb[0] = *reinterpret_cast<const float4*>(bp); rb[1] = *reinterpret_cast<const float4*>(bp + 4); }
+            if constexpr (TT != kTokF32) {
+                float t[8];
+                if (k0 + sc + 8 <= a.K && bvec) widen8<TT>(*reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(a.B) + bo), t);
+                else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) t[e] = k0 + sc + e < a.K ? load_tok<TT>(a.B, bo + e) : 0.f;
+                }
+                rb[0] = float4{t[0], t[1], t[2], t[3]}; rb[1] = float4{t[4], t[5], t[6], t[7]};
+            } else if (k0 + sc + 8 <= a.K && bvec) { rb[0] = *reinterpret_cast<const float4*>(bp); rb[1] = *reinterpret_cast<const float4*>(bp + 4); }
             else {
                 float t[8];
 #pragma unroll
@@ -134,6 +145,7 @@ __global__ __launch_bounds__(256) void gemm_tn_tile64_kernel(TnArgs a) {
     }
 }
 
+template <int TT>
 __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs a) {
     __shared__ __attribute__((aligned(16))) float red[4 * 4 * 4 * 64];
     __shared__ float cred[4][32];
@@ -153,7 +165,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs a) {
         kok[s] = k0 + s * 16 + li < a.K;
     }
     const float* Ap = a.A + n0 + li;
-    const float* Bp = a.B + k0 + li;
+    const int64_t Bo = k0 + li;                   // element offset into B
     // rows: blockIdx.y owns a contiguous chunk; inside it groups of 4 rows are dealt round-robin to the 4 waves
     const int chunk = (((a.M + (int)gridDim.y - 1) / (int)gridDim.y) + 15) / 16 * 16;
     const int m_begin = (int)blockIdx.y * chunk;
@@ -175,7 +187,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs a) {
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 av[i][s] = Ap[(int64_t)mc * a.lda + ncl[s]];
-                bv[i][s] = Bp[(int64_t)mc * a.ldb + kcl[s]];
+                bv[i][s] = load_tok<TT>(a.B, Bo + (int64_t)mc * a.ldb + kcl[s]);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -202,7 +214,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs a) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             av[s] = (mok && nok[s]) ? Ap[(int64_t)m * a.lda + s * 16] : 0.f;
-            bv[s] = (mok && kok[s]) ? Bp[(int64_t)m * a.ldb + s * 16] : 0.f;
+            bv[s] = (mok && kok[s]) ? load_tok<TT>(a.B, Bo + (int64_t)m * a.ldb + s * 16) : 0.f;
             cs[s] += av[s];
         }
 #pragma unroll
@@ -687,7 +699,9 @@ __global__ void refpoint_bwd_kernel(const float* __restrict__ g_ref, const float
 //   d sample / du = sum_c g_c ((a01 - a00) wy0 + (a11 - a10) wy1)  (out-of-range corners count as zero), likewise dv;
 //   u = x / zc fx + cx, zc = max(z, eps): dz only while z > eps;  (x, y, z) = R P + t;  P = ref (hi - lo) + lo.
 // One workgroup per (scene, query), one wave per view slot — the same geometry code path as the forward kernel.
-__global__ __launch_bounds__(1024) void sample_bwd_kernel(const float* __restrict__ tokens, const double* __restrict__ T_cl,
+// TT: element type of the token rows (read for the coordinate gradient only), widened as they are loaded
+template <int TT>
+__global__ __launch_bounds__(1024) void sample_bwd_kernel(const void* __restrict__ tokens, const double* __restrict__ T_cl,
                                                           const float* __restrict__ cam, const float* __restrict__ ref, ScaleBox sb,
                                                           int V, int h, int w, int C, int Q, const float* __restrict__ g_tgt,
                                                           float* __restrict__ g_tokens, float* __restrict__ g_ref) {
@@ -755,8 +769,8 @@ __global__ __launch_bounds__(1024) void sample_bwd_kernel(const float* __restric
                 if (k11) atomicAdd(g_tokens + o11 + c, gc * wy1 * wx1);
             }
             if (g_ref) {
-                const float a00 = k00 ? tokens[o00 + c] : 0.f, a01 = k01 ? tokens[o01 + c] : 0.f;
-                const float a10 = k10 ? tokens[o10 + c] : 0.f, a11 = k11 ? tokens[o11 + c] : 0.f;
+                const float a00 = k00 ? load_tok<TT>(tokens, o00 + c) : 0.f, a01 = k01 ? load_tok<TT>(tokens, o01 + c) : 0.f;
+                const float a10 = k10 ? load_tok<TT>(tokens, o10 + c) : 0.f, a11 = k11 ? load_tok<TT>(tokens, o11 + c) : 0.f;
                 su += gc * ((a01 - a00) * wy0 + (a11 - a10) * wy1);
                 sv += gc * ((a10 - a00) * wx0 + (a11 - a01) * wx1);
             }
@@ -976,14 +990,38 @@ hipError_t launch_transpose(const float* src, int64_t ld_src, float* dst, int64_
     hipLaunchKernelGGL(transpose_kernel, dim3(ceil_div(Cc, 32), ceil_div(R, 32)), dim3(256), 0, s, src, ld_src, dst, ld_dst, R, Cc);
     return hipGetLastError();
 }
-hipError_t launch_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, float* out, int64_t ldo, int M, int N, int K,
-                          int accumulate, hipStream_t s, float* bias, int bias_from) {
+namespace {
+void launch_gemm_tn_kernel(const TnArgs& a, dim3 grid, int b_type, hipStream_t s) {
+    if (b_type == kTokF16) hipLaunchKernelGGL(gemm_tn_kernel<kTokF16>, grid, dim3(256), 0, s, a);
+    else if (b_type == kTokBF16) hipLaunchKernelGGL(gemm_tn_kernel<kTokBF16>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(gemm_tn_kernel<kTokF32>, grid, dim3(256), 0, s, a);
+}
+template <int TT>
+void launch_sample_bwd_kernel(const void* tokens, const double* T_cl, const float* cam, const float* ref, ScaleBox sb, int B, int V, int h,
+                              int w, int C, int Q, const float* g_tgt, float* g_tokens, float* g_ref, hipStream_t s) {
+    const int nwv = V < 16 ? V : 16;
+    hipLaunchKernelGGL(sample_bwd_kernel<TT>, dim3(B * Q), dim3(nwv * 64), 0, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, g_tgt, g_tokens,
+                       g_ref);
+}
+void launch_sample_bwd_typed(int tok_type, const void* tokens, const double* T_cl, const float* cam, const float* ref, ScaleBox sb, int B,
+                             int V, int h, int w, int C, int Q, const float* g_tgt, float* g_tokens, float* g_ref, hipStream_t s) {
+    if (tok_type == kTokF16) launch_sample_bwd_kernel<kTokF16>(tokens, T_cl, cam, ref, sb, B, V, h, w, C, Q, g_tgt, g_tokens, g_ref, s);
+    else if (tok_type == kTokBF16) launch_sample_bwd_kernel<kTokBF16>(tokens, T_cl, cam, ref, sb, B, V, h, w, C, Q, g_tgt, g_tokens, g_ref, s);
+    else launch_sample_bwd_kernel<kTokF32>(tokens, T_cl, cam, ref, sb, B, V, h, w, C, Q, g_tgt, g_tokens, g_ref, s);
+}
+}  // namespace
+hipError_t launch_gemm_tn(const float* A, int64_t lda, const void* B, int64_t ldb, float* out, int64_t ldo, int M, int N, int K,
+                          int accumulate, hipStream_t s, float* bias, int bias_from, int b_type) {
+    if (b_type != kTokF32 && b_type != kTokF16 && b_type != kTokBF16) return hipErrorInvalidValue;
     TnArgs a;
     a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.out = out; a.ldo = ldo; a.M = M; a.N = N; a.K = K; a.accumulate = accumulate;
     a.bias = bias; a.bias_from = bias_from; a.part = nullptr;
     // large outputs from few rows (C = 1024 layers): 64 x 64 tiles with LDS-staged rows
     if ((int64_t)N * K >= (1 << 19) && M <= 4096) {
-        hipLaunchKernelGGL(gemm_tn_tile64_kernel, dim3(ceil_div(N, 64) * ceil_div(K, 64)), dim3(256), 0, s, a);
+        const dim3 grid(ceil_div(N, 64) * ceil_div(K, 64));
+        if (b_type == kTokF16) hipLaunchKernelGGL(gemm_tn_tile64_kernel<kTokF16>, grid, dim3(256), 0, s, a);
+        else if (b_type == kTokBF16) hipLaunchKernelGGL(gemm_tn_tile64_kernel<kTokBF16>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(gemm_tn_tile64_kernel<kTokF32>, grid, dim3(256), 0, s, a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || !bias) return e;
         return launch_colsum(A + bias_from, lda, M, N - bias_from, bias + bias_from, accumulate, s);     // not fused in that kernel
@@ -1007,13 +1045,13 @@ hipError_t launch_gemm_tn(const float* A, int64_t lda, const float* B, int64_t l
         // deterministic form: one [N][K] (+ bias [N]) partial per row range, summed in range order
         splits = det_splits(splits, (int64_t)N * K + N);
         a.part = t_det.base;
-        hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles, splits), dim3(256), 0, s, a);
+        launch_gemm_tn_kernel(a, dim3(tiles, splits), b_type, s);
         hipError_t e = launch_slab_reduce(a.part, splits, (int64_t)N * K, N, K, out, ldo, accumulate ? 1 : 0, s);
         if (e != hipSuccess || !bias || bias_from >= N) return e;
         return launch_slab_reduce(a.part + (int64_t)splits * N * K + bias_from, splits, N, 1, N - bias_from, bias + bias_from, 0,
                                   accumulate ? 1 : 0, s);
     }
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles, splits), dim3(256), 0, s, a);
+    launch_gemm_tn_kernel(a, dim3(tiles, splits), b_type, s);
     return hipGetLastError();
 }
 hipError_t launch_colsum(const float* X, int64_t ldx, int M, int N, float* out, int accumulate, hipStream_t s) {
@@ -1138,23 +1176,20 @@ hipError_t launch_refpoint_bwd(const float* g_ref, const float* ref0, int B, int
     return hipGetLastError();
 }
 
-hipError_t launch_sample_bwd(const float* tokens, const double* T_cl, const float* cam, const float* ref, ScaleBox sb, int B, int V,
-                             int h, int w, int C, int Q, const float* g_tgt, float* g_tokens, float* g_ref, hipStream_t s) {
-    const int nwv = V < 16 ? V : 16;
+hipError_t launch_sample_bwd(const void* tokens, const double* T_cl, const float* cam, const float* ref, ScaleBox sb, int B, int V,
+                             int h, int w, int C, int Q, const float* g_tgt, float* g_tokens, float* g_ref, hipStream_t s, int tok_type) {
+    if (tok_type != kTokF32 && tok_type != kTokF16 && tok_type != kTokBF16) return hipErrorInvalidValue;
     if (t_det.base && g_tokens) {
         // deterministic form: the coordinate gradient as above, the token gradient gathered per token in query order
         if ((int64_t)B * Q * V * 8 > t_det.floats) return hipErrorInvalidValue;
-        if (g_ref)
-            hipLaunchKernelGGL(sample_bwd_kernel, dim3(B * Q), dim3(nwv * 64), 0, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, g_tgt,
-                               nullptr, g_ref);
+        if (g_ref) launch_sample_bwd_typed(tok_type, tokens, T_cl, cam, ref, sb, B, V, h, w, C, Q, g_tgt, nullptr, g_ref, s);
         hipLaunchKernelGGL(sample_det_records_kernel, dim3(ceil_div(B * Q, 64)), dim3(64), 0, s, T_cl, cam, ref, sb, B * Q, Q, V, h, w,
                            t_det.base);
         hipLaunchKernelGGL(sample_det_gather_kernel, dim3(ceil_div(w, kDetTile) * ceil_div(h, kDetTile), V, B), dim3(256), 0, s,
                            t_det.base, g_tgt, Q, V, h, w, C, g_tokens);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(sample_bwd_kernel, dim3(B * Q), dim3(nwv * 64), 0, s, tokens, T_cl, cam, ref, sb, V, h, w, C, Q, g_tgt, g_tokens,
-                       g_ref);
+    launch_sample_bwd_typed(tok_type, tokens, T_cl, cam, ref, sb, B, V, h, w, C, Q, g_tgt, g_tokens, g_ref, s);
     return hipGetLastError();
 }
 

@@ -348,6 +348,14 @@ __device__ __forceinline__ f32x4 load_tok4(const void* row, int c4) {
     }
 }
 
+// one token at element index i of `base` -> fp32
+template <int TT>
+__device__ __forceinline__ float load_tok(const void* base, int64_t i) {
+    if constexpr (TT == kTokF32) return reinterpret_cast<const float*>(base)[i];
+    else if constexpr (TT == kTokF16) return (float)reinterpret_cast<const _Float16*>(base)[i];
+    else return bf16_bits_to_f32(reinterpret_cast<const unsigned short*>(base)[i]);
+}
+
 template <int KIND>
 __device__ __forceinline__ f32x16 mfma16(half8 a, half8 b, f32x16 c) {
     if constexpr (KIND == kF16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
@@ -644,8 +652,9 @@ hipError_t launch_slab_reduce(const float* part, int S, int64_t stride, int R, i
 hipError_t launch_gn_moments_det(const float* x, int64_t ldx, int C, int ngroups, int rows_per_scene, int B, double* sums, hipStream_t s);
 // ---- backward (backward.hip, attn_bwd.hip)
 hipError_t launch_transpose(const float* src, int64_t ld_src, float* dst, int64_t ld_dst, int R, int Cc, hipStream_t s);
-hipError_t launch_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, float* out, int64_t ldo, int M, int N, int K,
-                          int accumulate, hipStream_t s, float* bias = nullptr, int bias_from = 0);   // bias[n] (+)= column sums of A, n >= bias_from
+hipError_t launch_gemm_tn(const float* A, int64_t lda, const void* B, int64_t ldb, float* out, int64_t ldo, int M, int N, int K,
+                          int accumulate, hipStream_t s, float* bias = nullptr, int bias_from = 0,    // bias[n] (+)= column sums of A, n >= bias_from
+                          int b_type = kTokF32);      // element type of B (16-bit memory tokens are widened as they are loaded; ldb in elements)
 hipError_t launch_colsum(const float* X, int64_t ldx, int M, int N, float* out, int accumulate, hipStream_t s);
 hipError_t launch_add(const float* a, const float* b, float* y, int64_t n, hipStream_t s);
 hipError_t launch_axpy_rows(const float* x, int64_t ldx, float* y, int64_t ldy, int M, int N, int accumulate, hipStream_t s);
@@ -662,8 +671,9 @@ hipError_t launch_decode_bwd(const float* g_logits, const float* g_center, const
 hipError_t launch_head3_bwd(const float* g_h3, const float* w3, float* g_act, int M, int C, hipStream_t s);
 hipError_t launch_posemb_bwd(const float* g_emb, const float* ref, const float* dim_t, int M, float* g_ref, hipStream_t s);
 hipError_t launch_refpoint_bwd(const float* g_ref, const float* ref0, int B, int Q, float* g_w, hipStream_t s);
-hipError_t launch_sample_bwd(const float* tokens, const double* T_cl, const float* cam, const float* ref, ScaleBox sb, int B, int V,
-                             int h, int w, int C, int Q, const float* g_tgt, float* g_tokens, float* g_ref, hipStream_t s);
+hipError_t launch_sample_bwd(const void* tokens, const double* T_cl, const float* cam, const float* ref, ScaleBox sb, int B, int V,
+                             int h, int w, int C, int Q, const float* g_tgt, float* g_tokens, float* g_ref, hipStream_t s,
+                             int tok_type = kTokF32);     // element type of `tokens` (read for g_ref only)
 hipError_t launch_attn_bwd(const float* q, int64_t q_batch, int64_t q_head, int64_t q_row, const float* k, int64_t k_batch,
                            int64_t k_head, int64_t k_row, const float* v, int64_t v_batch, int64_t v_head, int64_t v_row,
                            const float* dO, int64_t do_batch, int64_t do_head, int64_t do_row, const float* lse, const float* D,
@@ -690,10 +700,11 @@ hipError_t launch_attn_bwd_batched(const float* q, const int64_t* q_off, int64_t
 size_t attn_bwd_pack_floats(int B, int H, int Lq, int n_it);
 // kvproj_bwd.hip: dW_kv / db_kv of the hoisted projection on the fp16 matrix pipe (hi/lo split), C = 256
 bool kvproj_bwd_split_supported(int C);
-hipError_t launch_tn_split_512x256(const float* g, int64_t ldg, const float* x, int64_t ldx, int64_t M, float* out, int64_t ldo,
-                                   float* db, const unsigned int* absmax_bits, float* scale_scratch, hipStream_t s);
-hipError_t launch_kvproj_bwd_split(const float* g, const float* tokens, int64_t M, int C, float* dW, float* db,
-                                   const unsigned int* absmax_bits, float* scale_scratch, hipStream_t s);
+// x_type / tok_type: element type of x / tokens (kTokF32 / kTokF16 / kTokBF16); fp16 runs two MFMAs per product (its lo half is zero)
+hipError_t launch_tn_split_512x256(const float* g, int64_t ldg, const void* x, int64_t ldx, int64_t M, float* out, int64_t ldo,
+                                   float* db, const unsigned int* absmax_bits, float* scale_scratch, hipStream_t s, int x_type = kTokF32);
+hipError_t launch_kvproj_bwd_split(const float* g, const void* tokens, int64_t M, int C, float* dW, float* db,
+                                   const unsigned int* absmax_bits, float* scale_scratch, hipStream_t s, int tok_type = kTokF32);
 // dst = dropout(src): keep mask of stream `seed` over the (M, N) index space, scaled by 1 / (1 - p)
 hipError_t launch_dropout_apply(const float* src, float* dst, int M, int N, float p, uint32_t seed, hipStream_t s);
 size_t attn_bwd_dq_partial_floats(int B, int H, int Lq, int Lk, int dh, bool grouped = false);      // grouped: the batched kernel's slots

@@ -195,15 +195,15 @@ class _TransformerParams(_Tracked, nn.Module):
 # (fp32-class accuracy, default at head dims 64 and 256), "fp32" = exact fp32 MFMA, "fp16" / "bf16" = single reduced-precision
 # products (BASELINE configs 2 and 5; head dim 64 with dim 128 / 256, head dim 256 with dim a multiple of 128)
 ATTENTION_MODES = {"fp32": 0, "split": 1, "fp16": 2, "bf16": 3, "split8": 4}
-# element types the inference entry points take tokens in as they are (include/parq_hip.h parq_set_token_type); anything else is
-# converted to fp32 first
+# element types the inference and training entry points take tokens in as they are (include/parq_hip.h parq_set_token_type,
+# parq_set_train_token_type); anything else is converted to fp32 first
 TOKEN_TYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
 class _Stash:
     """What one training forward leaves for its backward: the training workspace (saved activations of every iteration, K / V,
-    log-sum-exp rows), the call's state tuple (scene, inputs, output tensors, attention mode, dropout probability and seed) and
-    the workspace generation it was written in.  Owned by the autograd node; the module only keeps a weak reference, so a later
+    log-sum-exp rows), the call's state tuple (scene, inputs, output tensors, attention mode, dropout probability and seed, token
+    type) and the workspace generation it was written in.  Owned by the autograd node; the module only keeps a weak reference, so a later
     training forward knows whether the workspace is still needed (then it takes a fresh one) or free to be reused."""
     __slots__ = ("ws", "state", "gen", "consumed", "__weakref__")
 
@@ -633,6 +633,7 @@ class PARQDecoder(_Tracked, nn.Module):
             self._h = h
             self._mode_set = None
             self._tok_set = 0                # the handle's default token type (fp32)
+            self._train_tok_set = 0          # and the one its training entry points accept
             self._tiers_set = None
             self._seams_set = None
             self._bwd_batched_set = None
@@ -715,12 +716,17 @@ class PARQDecoder(_Tracked, nn.Module):
         import warnings
         warnings.warn(msg)
 
-    def _handle_in_mode(self, mode):
+    def _handle_in_mode(self, mode, tok=0):
         """The handle switched to `mode` without touching the user-facing ``attention_mode`` (the training entry points need
         the exact-fp32 attention kernels: their backward reads the fp32 K/V cache); the next inference call switches back.
-        Its token type is fp32: the training and view-sharded entry points read fp32 tokens only."""
+        `tok` (TOKEN_TYPES value) becomes both its token type and the type its training entry points accept
+        (parq_set_train_token_type): forward_train / backward pass the type of their forward's tokens, the view-sharded entry
+        point reads fp32 tokens only and leaves it 0."""
         h = self._handle(apply_mode=False)
-        self._token_type(h, 0)
+        self._token_type(h, tok)
+        if self._train_tok_set != tok:
+            _lib.check(_lib.load().parq_set_train_token_type(h, tok), "parq_set_train_token_type")
+            self._train_tok_set = tok
         if self._mode_set != mode:
             _lib.check(_lib.load().parq_set_attention_mode(h, ATTENTION_MODES[mode]), "parq_set_attention_mode")
             self._mode_set = mode
@@ -934,9 +940,12 @@ class PARQDecoder(_Tracked, nn.Module):
         parameter or the tokens require grad) the result carries a graph — in ``train()`` mode with the decoder layer's dropout,
         in ``eval()`` mode without it (the reference differentiates in eval mode too, model/parq_decoder.py:134-163).  Under
         ``torch.no_grad()`` (eval.py:46, Lightning's validation loop), or with nothing that requires grad, the inference chain
-        runs: no saved activations, the folded position MLP, one K/V workspace.  Tokens: the inference chain takes float16 / bfloat16
-        tokens as they are (bit-identical to the call on ``tokens.float()``, without that fp32 copy; include/parq_hip.h
-        parq_set_token_type); the autograd path and ``forward_view_sharded`` convert them to float32 as before, like any other dtype."""
+        runs: no saved activations, the folded position MLP, one K/V workspace.  Tokens: the inference chain AND the autograd path
+        (``forward_train`` / ``backward`` too) take float16 / bfloat16 tokens as they are — outputs bit-identical to the call on
+        ``tokens.float()``, gradients those of that call (bit-identical in deterministic mode), without that fp32 copy
+        (include/parq_hip.h parq_set_token_type, parq_set_train_token_type).  The token gradient is computed in float32 and cast to
+        the tokens' dtype by autograd (``backward()`` returns it in float32; a 16-bit ``d_tokens`` at the C ABI is out of scope).
+        ``forward_view_sharded`` converts them to float32 as before, like any other dtype."""
         if torch.is_grad_enabled() and (self.training or self._needs_graph(intput_tokens)):
             if not self.training and not getattr(self, "_warned_eval_autograd", False):
                 import warnings
@@ -1095,7 +1104,8 @@ class PARQDecoder(_Tracked, nn.Module):
             # (it would re-run into the workspace we are about to leave) and give this forward a workspace of its own
             self._resolve_train_range()
             self._train_ws = None
-        sc, keep, dev = self._scene(intput_tokens, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, feat_hw)
+        sc, keep, dev = self._scene(intput_tokens, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, feat_hw, native16=True)
+        tt = TOKEN_TYPES[keep[0].dtype]         # travels with the state: backward() and a range re-run read THIS forward's tokens
         self._ensure_packed(dev)
         self._order_behind_pack(dev)
         self._set_mirror(0)
@@ -1114,7 +1124,7 @@ class PARQDecoder(_Tracked, nn.Module):
 
         def enqueue():
             mode = self._train_mode()
-            h = self._handle_in_mode(mode)
+            h = self._handle_in_mode(mode, tt)                # (before the workspace is sized: mode "fp32" carves a widened copy)
             _lib.check(lib.parq_set_dropout(h, p_drop, seed), "parq_set_dropout")
             nbytes = lib.parq_train_workspace_bytes(h, sc.B, sc.V, sc.h, sc.w)
             old_ws = self._train_ws
@@ -1126,7 +1136,7 @@ class PARQDecoder(_Tracked, nn.Module):
             self._map_note(dev, "train")                      # cross_attention_map refuses on this stream: inference and stepping only
             self._mark_first_forward(dev)
             # the stash is laid out for `mode`: backward() uses exactly this mode, whatever attention_mode says by then
-            self._train_state = (sc, keep, outs, po, dev, mode, p_drop, seed)
+            self._train_state = (sc, keep, outs, po, dev, mode, p_drop, seed, tt)
             own = self._stash_owner() if self._stash_owner is not None else None
             if own is not None and old_ws is not None and own.ws is old_ws and not own.consumed and getattr(old_ws, "_parq_gen", None) == own.gen:
                 # a re-run (range fallback) after the autograd node of THIS forward took the stash: new mode, and — where the new
@@ -1171,16 +1181,18 @@ class PARQDecoder(_Tracked, nn.Module):
     def backward(self, grad_outputs, want_token_grad=True, _stash=None):
         """Backward of the last ``forward_train``.  ``grad_outputs``: dict with any of pred_logits / center_unnormalized /
         size_unnormalized / ortho6d -> (I, B, Q, k) cotangents (missing = zero).  Returns ({reference tensor name:
-        gradient}, d_tokens or None); gradients of tensors registered under two names are returned once per name."""
+        gradient}, d_tokens or None); gradients of tensors registered under two names are returned once per name.  ``d_tokens``
+        is float32 whatever the tokens' dtype (it accumulates in float32 from two sources; the autograd node casts it once)."""
         if _stash is None and self._train_state is None:
             raise RuntimeError("backward() needs a preceding forward_train()")
         state = _stash.state if _stash is not None else self._train_state
         train_ws = _stash.ws if _stash is not None else self._train_ws
         if state is self._train_state:                         # the most recent forward: its range check may still be pending
             self._resolve_train_range(in_backward=True)
-        sc, keep, outs, po, dev, mode, p_drop, seed = state
-        # the mode the stash was written in (forward_train), not whatever attention_mode says now: the workspace layout differs
-        lib, h = _lib.load(), self._handle_in_mode(mode)
+        sc, keep, outs, po, dev, mode, p_drop, seed, tt = state
+        # the mode and token type the stash was written in (forward_train), not whatever attention_mode says or the last call read:
+        # the workspace layout differs
+        lib, h = _lib.load(), self._handle_in_mode(mode, tt)
         _lib.check(lib.parq_set_dropout(h, p_drop, seed), "parq_set_dropout")      # the masks of THAT forward (another one may have run since)
         gs = []
         for key, wd in (("pred_logits", self.num_semcls + 1), ("center_unnormalized", 3), ("size_unnormalized", 3), ("ortho6d", 6)):

@@ -42,7 +42,9 @@ class PARQ(_Base):
         self.for_vis = _get(cfg, "MODEL.DECODER.FOR_VIS")
         # None: float32 tokens (the reference).  torch.float16 / torch.bfloat16: the inference chain hands the decoder 16-bit tokens
         # written by the ray-PE kernel, which the decoder reads as they are (bit-identical to decoding their float32 upcast); with a
-        # graph the ray-PE node stays float32 and its output is converted, and the decoder's autograd path upcasts again
+        # graph the ray-PE node stays float32 and its output is converted (the node emitting 16-bit tokens itself is out of scope:
+        # its 16-bit output needs the no-hidden flag), and the decoder's autograd path reads the 16-bit tokens as they are too — no
+        # float32 copy of the tokens lives from the forward to the backward
         self.token_dtype = None
         self.synced_metrics = {}          # validation metrics averaged over the ranks (what the reference logs with sync_dist=True)
 
