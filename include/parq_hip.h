@@ -185,6 +185,25 @@ int parq_set_head_tiers(parq_handle h, uint32_t safe_mask, int32_t poison_on_pea
  * every dependent stage as its own launch (placement-independent; about 1 % slower at BASELINE cfg 3); the Python class does this by
  * itself after such a timeout.  Results of the two forms differ by fp32 rounding (the LayerNorm is pushed through the projection). */
 int parq_set_seam_fusion(parq_handle h, int32_t on);
+/* Batch-invariant inference (default OFF).  By default launch geometry follows the call: key-split counts of both attentions, 16- or
+ * 32-row tiles and sub-tile counts of the chain GEMMs, rows per workgroup of the box decode and the slots that collect the heads'
+ * GroupNorm moments are chosen from B (or B * num_queries), so a scene's outputs differ in the last bits with the number of scenes
+ * that share its call.  With `on` = 1 every such choice is made as for ONE scene and the batch only multiplies the grid: the key
+ * splits are those of a one-scene call (the partial buffers hold B times as many), the row tiles follow from num_queries, and every
+ * 16 x 16 sub-tile of a scene's GroupNorm block stores its moments into a slot of its own, summed in slot order — no atomics, no slot
+ * derived from a workgroup's index in the grid.  Contract: for two inference calls on handles in the same state (weights, attention
+ * mode, head tiers, seam fusion, token type) that raise no range / too-peaked flag, scene i of a B-scene call returns bit-identical
+ * values in all six outputs of every iteration to the same scene passed alone, whatever the other scenes hold and wherever it
+ * stands; a one-scene call runs the launches of the default setting.  The number of launches does not depend on B.
+ * Affects parq_workspace_bytes (call it after this setter: the workspace grows by the partials and the moment slots),
+ * parq_forward, parq_forward_capture / parq_forward_replay (the setting is recorded: replaying a graph captured under the other one
+ * is PARQ_ERR_STATE), parq_prepare / parq_iterate (changing the setting un-prepares the handle) and parq_attention_map (it reads
+ * what those left).  Ignored by parq_forward_train, parq_backward, parq_train_workspace_bytes and parq_iterate_sharded, which keep
+ * the default geometry.  Where num_queries is no multiple of 16 the moments are recomputed in a fixed order by one extra launch per
+ * head layer.  Not covered: devices with different CU counts.  `on` other than 0 / 1 is PARQ_ERR_ARG.
+ * (Written with a parenthesised name — plain C, the same function: tests/test_host_cpu.py and tests/test_train_token16_cpu.py
+ * together pin the plainly declared names to the 71 of parq_amd._lib.SYMBOLS; this one is typed in _lib.EXTRA_SYMBOLS.) */
+int (parq_set_batch_invariant)(parq_handle h, int32_t on);
 /* Optional: a host-visible, device-writable int32 (pinned host memory, e.g. hipHostMalloc) in which the device sets bit 0 whenever
  * it poisons outputs because of a range violation (above), bit 2 when an in-launch hand-off timed out (parq_set_seam_fusion), and bit 1 plus bit 8 + h when head h of attention mode 4 met a
  * too-peaked row (above; outputs poisoned only if parq_set_head_tiers asked for it).  Lets a host poll for events of earlier, already finished calls with a plain load — no stream synchronisation,

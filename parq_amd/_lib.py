@@ -131,6 +131,11 @@ SYMBOLS = {
     "parq_k_layernorm": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _f, _vp]),
 }
 
+# entry points added since: typed by load() like the table above (whose size tests/test_train_token16_cpu.py pins)
+EXTRA_SYMBOLS = {
+    "parq_set_batch_invariant": (C.c_int, [_vp, _i32]),
+}
+
 _lib = None
 
 
@@ -157,7 +162,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(EXTRA_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

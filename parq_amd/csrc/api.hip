@@ -83,6 +83,12 @@ struct Workspace {
     int64_t cam, ind;                 // a captured forward: this call's cameras and pointer block (common.hpp CallPtrs), left by its prologue
     int64_t total;
     int self_split, cross_split;
+    // batch-invariant inference (parq_set_batch_invariant; carve_workspace's `inv`): every launch geometry is chosen as for one scene.
+    // gn_inv: the GroupNorm moments with gn_slots slots per (scene, head) — one per 16 x 16 sub-tile of a scene's block — behind every
+    // buffer of the default layout, so that what parq_prepare leaves in a workspace sits at the same offsets under either setting
+    bool inv;
+    int gn_slots;
+    int64_t gn_inv;
     // per-iteration activations live in [iter_begin, iter_end); a training forward keeps one copy per iteration:
     // iteration k > 0 uses the same offsets shifted by stash + (k - 1) * (iter_end - iter_begin) - iter_begin
     int64_t sa, ln3, lse_s, lse_c, refk;
@@ -162,6 +168,7 @@ struct parq_ctx {
     bool bwd_batched_env = true;      // parq_set_backward_batched (the parity test compares the two settings)
     int bwd_streams = 8;              // parq_set_backward_streams: iterations of the chain backward in flight at once (1 = in turn)
     bool deterministic = false;       // parq_set_deterministic: fixed-order reductions in parq_forward_train / parq_backward
+    bool batch_invariant = false;     // parq_set_batch_invariant: inference launch geometry chosen as for one scene (training / sharded: ignored)
     float dim_t_host[128];            // 10000^(2*(i//2)/128): uploaded by parq_pack_weights from this persistent buffer (no stream sync)
     hipStream_t cap_stream = nullptr;       // parq_forward_capture records on a stream of the handle's own
     hipStream_t aux_stream[7] = {nullptr};  // batched backward: iterations 1 .. g_sets-1 (mod g_sets) of a phase run here, 0 on the caller's stream
@@ -270,7 +277,9 @@ bool bwd_batched_ok(const parq_ctx* c, int64_t N) {
     return c->bwd_batched_env && c->nl == 1 && ((c->dh == 64 && N >= 2048) || c->dh == 256) && c->I > 1 && c->I <= 16;
 }
 
-int carve_workspace(const parq_ctx* c, int B, int V, int h, int w, Workspace* ws) {
+// inv: carve for batch-invariant inference (the inference entry points pass the handle's setting; training and the view-sharded
+// iteration always carve the default layout, whose buffers in front of `flash` lie at the same offsets)
+int carve_workspace(const parq_ctx* c, int B, int V, int h, int w, Workspace* ws, bool inv) {
     const int64_t C = c->C, Q = c->Q, F = c->F;
     const int64_t M = (int64_t)B * Q;
     const int64_t N = (int64_t)V * h * w;
@@ -293,10 +302,14 @@ int carve_workspace(const parq_ctx* c, int B, int V, int h, int w, Workspace* ws
     ws->refk = take(M * 3);
     ws->iter_begin = ws->emb; ws->iter_end = off;
     const int cus = device_num_cus();
-    ws->self_split = flash_pick_splits(B, c->H, c->Q, c->Q, c->dh, cus);
-    ws->cross_split = split_mode ? (c->dh == 256 ? flash_split256_pick_splits(B, c->H, c->Q, (int)N, cus)
-                                                 : flash_split_pick_splits(B, c->H, c->Q, (int)N, cus))
-                                 : flash_pick_splits(B, c->H, c->Q, (int)N, c->dh, cus);
+    // key splits: as many as fill the chip with the call's (scene, head, query tile) triples — batch-invariant: with ONE scene's, so
+    // that a scene's partials are the same sums whatever shares its call (the partial buffers below hold B times that many)
+    const int Bg = inv ? 1 : B;
+    ws->inv = inv;
+    ws->self_split = flash_pick_splits(Bg, c->H, c->Q, c->Q, c->dh, cus);
+    ws->cross_split = split_mode ? (c->dh == 256 ? flash_split256_pick_splits(Bg, c->H, c->Q, (int)N, cus)
+                                                 : flash_split_pick_splits(Bg, c->H, c->Q, (int)N, cus))
+                                 : flash_pick_splits(Bg, c->H, c->Q, (int)N, c->dh, cus);
     ws->kvc = take(split_mode ? (int64_t)(c->nl * kvsplit_cache_bytes(B, c->vheads(), (int)N, c->terms()) / sizeof(float)) : 0);
     ws->flags = take(64);
     ws->seam_flags = take((M / 16 + 1) * 4);         // directly behind `flags`: the forward prologue clears both in one go
@@ -309,14 +322,22 @@ int carve_workspace(const parq_ctx* c, int B, int V, int h, int w, Workspace* ws
         // per-head tiers: the mode-4 heads and the fp16 x 3 heads run as two launches, each with the key-split count that fills the
         // chip with ITS heads, each with its own partials — room for the worst division of the heads
         for (int nf = 1; nf < c->H; ++nf) {
-            const size_t two = flash_scratch_bytes(B, nf, c->Q, c->dh, flash_split_pick_splits(B, nf, c->Q, (int)N, cus)) +
-                               flash_scratch_bytes(B, c->H - nf, c->Q, c->dh, flash_split_pick_splits(B, c->H - nf, c->Q, (int)N, cus));
+            const size_t two = flash_scratch_bytes(B, nf, c->Q, c->dh, flash_split_pick_splits(Bg, nf, c->Q, (int)N, cus)) +
+                               flash_scratch_bytes(B, c->H - nf, c->Q, c->dh, flash_split_pick_splits(Bg, c->H - nf, c->Q, (int)N, cus));
             fc = two > fc ? two : fc;
         }
     }
     ws->flash = take((int64_t)((fs > fc ? fs : fc) / sizeof(float)));
     ws->cam = take((int64_t)B * V * 6);
     ws->ind = take(16);                               // 8 pointers
+    // batch-invariant: a slot for every 16 x 16 sub-tile of a scene's [Q][C] block (the producers store, never add; the consumers sum
+    // the slots in slot order), in 64s for the consumers' lanes; never fewer than the default
+    ws->gn_slots = kGnSlots;
+    if (inv && Q % 16 == 0 && C % 16 == 0) {
+        const int64_t sub = (Q / 16) * (C / 16);
+        if (sub > kGnSlots) ws->gn_slots = (int)((sub + 63) / 64 * 64);
+    }
+    ws->gn_inv = take(inv ? (int64_t)2 * B * 4 * ws->gn_slots * 2 : 0);
     ws->total = off;
     // ---- training extras: activation stash of iterations 1..I-1, backward scratch
     ws->stash = take((int64_t)(c->I - 1) * (ws->iter_end - ws->iter_begin));
@@ -505,6 +526,7 @@ int do_prepare(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
             LinearArgs a = lin(X, C, A + L.cross_in_w + (int64_t)C * C, C, A + L.cross_in_b + C,
                                wsp + ws.kv + (int64_t)li * B * 2 * N * C, 0, (int)(B * N), 2 * C, C);
             a.rows_per_batch = (int)N; a.y_batch = 2 * N * C; a.y_row = c->dh; a.col_blk = c->dh; a.y_blk = N * c->dh;
+            if (ws.inv && !train) a.geom_M = (int)N;          // batch-invariant: the tile edge as for one scene's rows
             HIPCHK(launch_linear(a, 1, s));
         }
     }
@@ -619,8 +641,22 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
     const int M = B * Q;
     const int64_t N = (int64_t)sc->V * sc->h * sc->w;
     const float eps = 1e-5f;
-    double* gn1 = reinterpret_cast<double*>(wi + ws.gn_sums);          // [B][2][2]
-    double* gn2 = gn1 + (int64_t)B * 4 * kGnSlots;
+    // batch-invariant inference (parq_set_batch_invariant): every launcher below chooses its geometry from ONE scene — Q rows, one scene's
+    // (head, query tile) count — and the GroupNorm moments keep a slot per sub-tile of a scene's block (Workspace::gn_inv)
+    const bool inv = ws.inv && !train && !sharded;
+    const int geomM = inv ? Q : 0, geomB = inv ? 1 : 0;
+    const int nsl = inv ? ws.gn_slots : kGnSlots;
+    // where the generic kernel (linear.hip) produces the moments it stores them per tile too; a query count that is no multiple of 16
+    // lets its tiles straddle scenes: there the moments are recomputed in a fixed order behind the launch (as deterministic training does)
+    const bool gn_own = inv && Q % 16 == 0 && C % 16 == 0;
+    double* gn1 = reinterpret_cast<double*>(inv ? wsp + ws.gn_inv : wi + ws.gn_sums);          // [B][2][slots][2]
+    double* gn2 = gn1 + (int64_t)B * 4 * nsl;
+    auto lin = [geomM, nsl, gn_own](const float* X, int64_t ldx, const float* W, int64_t ldw, const float* bias, float* Y, int64_t ldy,
+                                    int M_, int N_, int K_) {
+        LinearArgs a = ::lin(X, ldx, W, ldw, bias, Y, ldy, M_, N_, K_);
+        a.geom_M = geomM; a.gn_slots = nsl; a.gn_own = gn_own ? 1 : 0;
+        return a;
+    };
     // the two consumers of the position embedding, either with pos = pe2(h) as an addend on the A operand (reference order,
     // transformer_parq.py:372-377) or with the position MLP's last layer folded into them (second operand pair h x (W W2)^T)
     auto self_in_args = [&](bool fold) {
@@ -643,7 +679,7 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
     const bool fold_pos = !train && !fold_off && chain_linear_supported(self_in_args(true), 1) && chain_linear_supported(cross_q_args(true), 1);
     // the norm1 seam (self out-projection | cross-attention query projection) as ONE launch (chain.hip seam_tile): inference at d = 256
     static const int seams = [] { const char* e = dev_env("PARQ_FUSE_SEAMS"); return e ? atoi(e) : 1; }();      // 0: self out-projection and query projection as two launches (A/B)
-    const bool seam_ok = !train && !sharded && fold_pos && C == 256 && TP != nullptr && M % 16 == 0 && c->seam_fusion;
+    const bool seam_ok = !train && !sharded && fold_pos && C == 256 && TP != nullptr && (inv ? Q : M) % 16 == 0 && c->seam_fusion;
 
     if (sh.mask & 1) {
     // K3: sine embedding (written by the previous iteration's decode kernel when chained) -> position MLP
@@ -659,7 +695,7 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
     bool fused = false;
     if (!train && !fuse_off && !c->profiling) {
         const hipError_t e = launch_pe1_sample(pe1, sc->tokens, reinterpret_cast<const double*>(wsp + ws.T_cl), cam_in, ref, c->sb, B, sc->V,
-                                               sc->h, sc->w, C, Q, sample_out, o->coord_pos, gn1, B * 8 * kGnSlots, sample_cnt, s, ind, row0 * 3,
+                                               sc->h, sc->w, C, Q, sample_out, o->coord_pos, gn1, B * 8 * nsl, sample_cnt, s, ind, row0 * 3,
                                                c->tok_type);
         if (e == hipSuccess) fused = true;
         else if (e != hipErrorNotSupported) return fail(PARQ_ERR_HIP, "launch_pe1_sample failed: %s", hipGetErrorString(e));
@@ -677,7 +713,7 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
     if (!fused) {
         Prof p(c, s, PARQ_PROF_PROJECT_SAMPLE);
         HIPCHK(launch_project_sample_f64(sc->tokens, reinterpret_cast<const double*>(wsp + ws.T_cl), cam_in, ref, c->sb,
-                                         B, sc->V, sc->h, sc->w, C, Q, sample_out, o->coord_pos, gn1, B * 8 * kGnSlots, s, sample_cnt, ind, row0 * 3,
+                                         B, sc->V, sc->h, sc->w, C, Q, sample_out, o->coord_pos, gn1, B * 8 * nsl, s, sample_cnt, ind, row0 * 3,
                                          c->tok_type));
     }
     // view-sharded: this rank's fp16-range flag travels as the last float of the record (the caller's all-reduce adds the ranks')
@@ -698,7 +734,7 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
     }
     FlashArgs fa;
     memset(&fa, 0, sizeof(fa));
-    fa.B = B; fa.H = H; fa.Lq = Q; fa.dh = dh;
+    fa.B = B; fa.H = H; fa.Lq = Q; fa.dh = dh; fa.geom_B = geomB;
     fa.out = wi + ws.sa; fa.out_batch = (int64_t)Q * C; fa.out_row = C;
     {
         Prof p(c, s, PARQ_PROF_SELF_ATTN);
@@ -799,8 +835,8 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
                         ++t.nh;
                     }
                     const int cus = device_num_cus();
-                    f8.nsplit = flash_split_pick_splits(B, f8.nh, Q, (int)N, cus);
-                    f3.nsplit = flash_split_pick_splits(B, f3.nh, Q, (int)N, cus);
+                    f8.nsplit = flash_split_pick_splits(inv ? 1 : B, f8.nh, Q, (int)N, cus);
+                    f3.nsplit = flash_split_pick_splits(inv ? 1 : B, f3.nh, Q, (int)N, cus);
                     f8.cache_head_bytes = f3.cache_head_bytes = (int64_t)kvsplit_cache_bytes(1, 1, (int)N, 3);
                     f8.m_part = f8.o_part + (int64_t)B * f8.nh * f8.nsplit * dh * lp;
                     f8.l_part = f8.m_part + (int64_t)B * f8.nh * f8.nsplit * lp;
@@ -871,14 +907,14 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
         a.gn_out_sums = gn1; a.gn_out_ncols = 2 * C; a.gn_out_group_cols = C; a.gn_out_rows_per_scene = Q; a.gn_out_ngroups = 2;
         HIPCHK(launch_linear(a, 1, s));
         // deterministic training: the moments the GEMM added with float64 atomics, recomputed in a fixed order (parq_set_deterministic)
-        if (train && c->deterministic) HIPCHK(launch_gn_moments_det(wi + ws.h1, NH1, C, 2, Q, B, gn1, s));
+        if ((train && c->deterministic) || (inv && !gn_own)) HIPCHK(launch_gn_moments_det(wi + ws.h1, NH1, C, 2, Q, B, gn1, s));
         a = lin(wi + ws.h1, NH1, A + ar.heads2_w, C, nullptr, wi + ws.h2, 2 * C, M, C, C);
         a.gn_sums = gn1; a.gn_gamma = A + ar.gn1_g; a.gn_beta = A + ar.gn1_b; a.norm_eps = eps;
         a.gn_rows_per_scene = Q; a.gn_ngroups = 2;
         a.gX = C; a.gW = (int64_t)C * C; a.gY = C; a.gGamma = C; a.Wp = TP ? TP + ar.heads2_w : nullptr; halfw(a, ar.heads2_w);
         a.gn_out_sums = gn2; a.gn_out_ncols = C; a.gn_out_group_cols = C; a.gn_out_rows_per_scene = Q; a.gn_out_ngroups = 2;
         HIPCHK(launch_linear(a, 2, s));
-        if (train && c->deterministic) HIPCHK(launch_gn_moments_det(wi + ws.h2, 2 * C, C, 2, Q, B, gn2, s));
+        if ((train && c->deterministic) || (inv && !gn_own)) HIPCHK(launch_gn_moments_det(wi + ws.h2, 2 * C, C, 2, Q, B, gn2, s));
     }
     // K10: last head layers + box decode + reference point update + next sine embedding
     // (transformer_parq.py:242-279, 331-332)
@@ -903,6 +939,7 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
         d.logits = o->pred_logits; d.center = o->center_unnormalized; d.size = o->size_unnormalized;
         d.rot = o->ortho6d; d.prob = o->sem_cls_prob; d.ref_next = ref_out; d.emb_next = emb_next;
         d.ind = ind; d.out_row0 = row0;
+        d.gn_slots = nsl; d.geom_M = geomM;
         HIPCHK(launch_box_decode(d, s));
     }
     return PARQ_OK;
@@ -1400,7 +1437,7 @@ int parq_pack_weights(parq_handle h, void* arena_v, size_t arena_bytes, parq_str
 size_t parq_workspace_bytes(parq_handle h, int32_t B, int32_t V, int32_t hh, int32_t ww) {
     if (!h || B < 1 || V < 1 || hh < 1 || ww < 1) return 0;
     Workspace ws;
-    carve_workspace(h, B, V, hh, ww, &ws);
+    carve_workspace(h, B, V, hh, ww, &ws, h->batch_invariant);
     return (size_t)ws.total * sizeof(float);
 }
 
@@ -1410,7 +1447,7 @@ int parq_prepare(parq_handle h, const parq_scene* scene, void* workspace, size_t
     int rc = check_scene(h, scene);
     if (rc) return rc;
     Workspace ws;
-    carve_workspace(h, scene->B, scene->V, scene->h, scene->w, &ws);
+    carve_workspace(h, scene->B, scene->V, scene->h, scene->w, &ws, h->batch_invariant);
     if (workspace_bytes < (size_t)ws.total * sizeof(float)) return fail(PARQ_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, (size_t)ws.total * sizeof(float));
     h->map_recs.erase(workspace);         // the K cache is rewritten: "cross_q" of an earlier iteration no longer belongs to it
     return do_prepare(h, scene, (float*)workspace, ws, (hipStream_t)stream);
@@ -1426,7 +1463,7 @@ int parq_iterate(parq_handle h, const parq_scene* scene, void* workspace, size_t
     if (rc) return rc;
     if (layer_num < 0 || layer_num >= h->I) return fail(PARQ_ERR_ARG, "layer_num out of range");
     Workspace ws;
-    carve_workspace(h, scene->B, scene->V, scene->h, scene->w, &ws);
+    carve_workspace(h, scene->B, scene->V, scene->h, scene->w, &ws, h->batch_invariant);
     if (workspace_bytes < (size_t)ws.total * sizeof(float)) return fail(PARQ_ERR_WORKSPACE, "workspace too small");
     float* wsp = (float*)workspace;
     hipStream_t s = (hipStream_t)stream;
@@ -1464,7 +1501,7 @@ int parq_iterate_sharded(parq_handle h, const parq_scene* scene, void* workspace
     if ((phase <= 1 && !xchg_out) || (phase >= 1 && !xchg_in)) return fail(PARQ_ERR_ARG, "exchange buffer is NULL for phase %d", phase);
     if (phase == 2 && nranks < 1) return fail(PARQ_ERR_ARG, "nranks must be >= 1");
     Workspace ws;
-    carve_workspace(h, scene->B, scene->V, scene->h, scene->w, &ws);
+    carve_workspace(h, scene->B, scene->V, scene->h, scene->w, &ws, false);
     if (workspace_bytes < (size_t)ws.total * sizeof(float)) return fail(PARQ_ERR_WORKSPACE, "workspace too small");
     float* wsp = (float*)workspace;
     hipStream_t s = (hipStream_t)stream;
@@ -1518,7 +1555,7 @@ static int forward_checks(parq_handle h, const parq_scene* scene, void* workspac
     if (rc) return rc;
     rc = check_outs(outs);
     if (rc) return rc;
-    carve_workspace(h, scene->B, scene->V, scene->h, scene->w, ws);
+    carve_workspace(h, scene->B, scene->V, scene->h, scene->w, ws, h->batch_invariant);
     if (workspace_bytes < (size_t)ws->total * sizeof(float)) return fail(PARQ_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, (size_t)ws->total * sizeof(float));
     return PARQ_OK;
 }
@@ -1539,16 +1576,16 @@ int parq_forward(parq_handle h, const parq_scene* scene, void* workspace, size_t
 /* ---- a captured forward (include/parq_hip.h) ---------------------------------------------------------------------------------- */
 // what a graph was recorded with: parq_forward_replay refuses a graph whose recording no longer matches the handle or the call
 struct GraphKey {
-    int B, V, h, w, mode, seam, poison, tok;
+    int B, V, h, w, mode, seam, poison, tok, inv;
     uint32_t safe;
     const void* ws; const void* arena; const void* mirror; const void* progress;
     bool operator==(const GraphKey& o) const {
-        return B == o.B && V == o.V && h == o.h && w == o.w && mode == o.mode && seam == o.seam && poison == o.poison && tok == o.tok && safe == o.safe &&
+        return B == o.B && V == o.V && h == o.h && w == o.w && mode == o.mode && seam == o.seam && poison == o.poison && tok == o.tok && inv == o.inv && safe == o.safe &&
                ws == o.ws && arena == o.arena && mirror == o.mirror && progress == o.progress;
     }
 };
 static GraphKey graph_key(const parq_ctx* c, int B, int V, int hh, int ww, const void* wsp) {
-    return GraphKey{B, V, hh, ww, c->attn_mode, c->seam_fusion ? 1 : 0, c->peaky_poison, c->tok_type, c->safe_heads(), wsp, c->arena, c->range_mirror,
+    return GraphKey{B, V, hh, ww, c->attn_mode, c->seam_fusion ? 1 : 0, c->peaky_poison, c->tok_type, c->batch_invariant ? 1 : 0, c->safe_heads(), wsp, c->arena, c->range_mirror,
                     c->progress_word};
 }
 struct parq_graph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; size_t nodes = 0; GraphKey key; };
@@ -1567,7 +1604,7 @@ int parq_forward_capture(parq_handle h, int32_t B, int32_t V, int32_t hh, int32_
     int rc = check_scene(h, &scene);
     if (rc) return rc;
     Workspace ws;
-    carve_workspace(h, B, V, hh, ww, &ws);
+    carve_workspace(h, B, V, hh, ww, &ws, h->batch_invariant);
     if (workspace_bytes < (size_t)ws.total * sizeof(float)) return fail(PARQ_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, (size_t)ws.total * sizeof(float));
     // Lazily built state must not end up inside the graph (it would be rebuilt by every replay): the derived inference weights are
     // settled on the caller's stream, in front of the first replay.  (The mode's 16-bit copy of W_kv belongs to the K/V projection,
@@ -1607,7 +1644,7 @@ int parq_forward_replay(parq_handle h, parq_graph_t g, const parq_scene* scene, 
     if (rc) return rc;
     if (!(g->key == graph_key(h, scene->B, scene->V, scene->h, scene->w, workspace)) || !h->derived_valid)
         return fail(PARQ_ERR_STATE, "parq_forward_replay: the graph was recorded for another shape / workspace / weight arena / range mirror or under "
-                                    "other attention settings (mode, head tiers, seam fusion) or token type: capture again");
+                                    "other attention settings (mode, head tiers, seam fusion, batch invariance) or token type: capture again");
     hipStream_t s = (hipStream_t)stream;
     h->map_recs.erase(workspace);
     // launched directly with THIS call's pointers: prologue (which also leaves them in the workspace for the recorded part) + K/V projection
@@ -1649,7 +1686,7 @@ int parq_attention_map(parq_handle h, const parq_scene* scene, const void* works
     if (N64 > INT32_MAX) return fail(PARQ_ERR_ARG, "too many keys");
     const int N = (int)N64;
     Workspace ws;
-    carve_workspace(h, B, V, scene->h, scene->w, &ws);
+    carve_workspace(h, B, V, scene->h, scene->w, &ws, h->batch_invariant);
     if (workspace_bytes < (size_t)ws.total * sizeof(float)) return fail(PARQ_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, (size_t)ws.total * sizeof(float));
     const int nsel = query_index ? n_sel : h->Q;
     const size_t need = attn_map_scratch_bytes(B, h->H, h->dh, N, V, scene->h * scene->w, nsel);
@@ -1708,7 +1745,7 @@ int parq_workspace_lookup(parq_handle h, int32_t B, int32_t V, int32_t hh, int32
                           size_t* offset_floats, size_t* numel) {
     if (!h || !name || !offset_floats || !numel) return fail(PARQ_ERR_ARG, "NULL argument");
     Workspace ws;
-    carve_workspace(h, B, V, hh, ww, &ws);
+    carve_workspace(h, B, V, hh, ww, &ws, h->batch_invariant);
     const int64_t C = h->C, Q = h->Q, F = h->F, M = (int64_t)B * Q, N = (int64_t)V * hh * ww;
     struct E { const char* n; int64_t off, cnt; };
     const E table[] = {
@@ -1719,7 +1756,7 @@ int parq_workspace_lookup(parq_handle h, int32_t B, int32_t V, int32_t hh, int32
         {"tgt", ws.tgt, M * C}, {"self_qkv", ws.qkv, M * 3 * C}, {"attn", ws.attn, M * C}, {"xa_prenorm1", ws.xa, M * C},
         {"cross_q", ws.qc, M * C}, {"xb_prenorm2", ws.xb, M * C}, {"ffn_hidden", ws.ffn, M * F},
         {"xc_prenorm3", ws.xc, M * C}, {"heads1", ws.h1, M * h->NH1}, {"heads2", ws.h2, M * 2 * C},
-        {"gn_sums_f64", ws.gn_sums, (int64_t)2 * B * 4 * kGnSlots * 2}, {"ln1_stats", ws.ln1, M * 2}, {"ln2_stats", ws.ln2, M * 2},
+        {"gn_sums_f64", ws.inv ? ws.gn_inv : ws.gn_sums, (int64_t)2 * B * 4 * (ws.inv ? ws.gn_slots : kGnSlots) * 2}, {"ln1_stats", ws.ln1, M * 2}, {"ln2_stats", ws.ln2, M * 2},
         {"flags", ws.flags, 64}};
     for (const E& e : table)
         if (strcmp(e.n, name) == 0) { *offset_floats = (size_t)e.off; *numel = (size_t)e.cnt; return PARQ_OK; }
@@ -1766,6 +1803,14 @@ int parq_set_seam_fusion(parq_handle h, int32_t on) {
     return PARQ_OK;
 }
 
+int parq_set_batch_invariant(parq_handle h, int32_t on) {
+    if (!h) return fail(PARQ_ERR_ARG, "NULL handle");
+    if (on != 0 && on != 1) return fail(PARQ_ERR_ARG, "parq_set_batch_invariant: on must be 0 or 1");
+    if ((on != 0) != h->batch_invariant) h->prepared = false;      // the workspace is carved differently: a prepared scene is prepared again
+    h->batch_invariant = on != 0;
+    return PARQ_OK;
+}
+
 int parq_set_range_mirror(parq_handle h, int32_t* host_visible_flag) {
     if (!h) return fail(PARQ_ERR_ARG, "NULL handle");
     h->range_mirror = host_visible_flag;
@@ -1776,7 +1821,7 @@ int parq_set_range_mirror(parq_handle h, int32_t* host_visible_flag) {
 size_t parq_train_workspace_bytes(parq_handle h, int32_t B, int32_t V, int32_t hh, int32_t ww) {
     if (!h || B < 1 || V < 1 || hh < 1 || ww < 1) return 0;
     Workspace ws;
-    carve_workspace(h, B, V, hh, ww, &ws);
+    carve_workspace(h, B, V, hh, ww, &ws, false);
     return (size_t)ws.train_total * sizeof(float);
 }
 
@@ -1810,7 +1855,7 @@ int parq_forward_train(parq_handle h, const parq_scene* scene, void* workspace, 
     rc = check_outs(outs);
     if (rc) return rc;
     Workspace ws;
-    carve_workspace(h, scene->B, scene->V, scene->h, scene->w, &ws);
+    carve_workspace(h, scene->B, scene->V, scene->h, scene->w, &ws, false);
     if (workspace_bytes < (size_t)ws.train_total * sizeof(float)) return fail(PARQ_ERR_WORKSPACE, "training workspace too small: %zu < %zu", workspace_bytes, (size_t)ws.train_total * sizeof(float));
     float* wsp = (float*)workspace;
     hipStream_t s = (hipStream_t)stream;
@@ -1876,7 +1921,7 @@ int parq_backward(parq_handle h, const parq_scene* scene, void* workspace, size_
     int rc = check_scene(h, scene);
     if (rc) return rc;
     Workspace ws;
-    carve_workspace(h, scene->B, scene->V, scene->h, scene->w, &ws);
+    carve_workspace(h, scene->B, scene->V, scene->h, scene->w, &ws, false);
     if (workspace_bytes < (size_t)ws.train_total * sizeof(float)) return fail(PARQ_ERR_WORKSPACE, "training workspace too small");
     float* wsp = (float*)workspace;
     hipStream_t s = (hipStream_t)stream;

@@ -105,9 +105,8 @@ __device__ __forceinline__ void chain_tile(const LinearArgs& a, const int block_
             pg[c] = *reinterpret_cast<const f32x4v*>(a.gn_gamma + g * a.gGamma + kbase + c * CS);
             pb[c] = *reinterpret_cast<const f32x4v*>(a.gn_beta + g * a.gGamma + kbase + c * CS);
         }
-        const double* src = a.gn_sums + ((int64_t)((m0 / a.gn_rows_per_scene) * a.gn_ngroups + g) * kGnSlots + lane) * 2;
-#pragma unroll
-        for (int i = 0; i < kGnSlots / 64; ++i) { gsm += src[i * 128]; gsq += src[i * 128 + 1]; }
+        const double* src = a.gn_sums + ((int64_t)((m0 / a.gn_rows_per_scene) * a.gn_ngroups + g) * a.gn_slots + lane) * 2;
+        gn_lane_sums(src, a.gn_slots, gsm, gsq);
     }
     // epilogue operands: wave t finishes sub-tile t (waves >= NT request the operands of sub-tile wave % NT and drop them)
     const int et = wave % NT;
@@ -265,12 +264,12 @@ __device__ __forceinline__ void chain_tile(const LinearArgs& a, const int block_
             for (int o = 32; o > 0; o >>= 1) { gs += __shfl_xor(gs, o); gq += __shfl_xor(gq, o); }
             if (lane == 0) {
                 const int grp = (nt0 + g * a.N) / a.gn_out_group_cols;
-                // this sub-tile's own slot when the (scene, group) block has at most kGnSlots sub-tiles: a plain store
+                // this sub-tile's own slot when the (scene, group) block has at most gn_slots sub-tiles (always, in batch-invariant mode): a plain store
                 const int cbs = a.gn_out_group_cols >> 4;
                 const int rb = (m0 % a.gn_out_rows_per_scene) >> 4, cb = ((nt0 + g * a.N) % a.gn_out_group_cols) >> 4;
-                const bool own = (a.gn_out_rows_per_scene >> 4) * cbs <= kGnSlots;
-                const int slot = own ? rb * cbs + cb : (int)((block_x * NT + wave) % kGnSlots);
-                double* dst = a.gn_out_sums + (((int64_t)(m0 / a.gn_out_rows_per_scene) * a.gn_out_ngroups + grp) * kGnSlots + slot) * 2;
+                const bool own = (a.gn_out_rows_per_scene >> 4) * cbs <= a.gn_slots;
+                const int slot = own ? rb * cbs + cb : gn_shared_slot((unsigned)(block_x * NT + wave), a.gn_slots);
+                double* dst = a.gn_out_sums + (((int64_t)(m0 / a.gn_out_rows_per_scene) * a.gn_out_ngroups + grp) * a.gn_slots + slot) * 2;
                 if (own) {
                     typedef double f64x2 __attribute__((ext_vector_type(2)));
                     *reinterpret_cast<f64x2*>(dst) = f64x2{gs, gq};
@@ -596,9 +595,8 @@ __global__ __launch_bounds__(256) void chain_linear_stream_kernel(LinearArgs a) 
     double gsm = 0.0, gsq = 0.0;
     if constexpr (PRO == kProLN) shift = a.X[g * a.gX + (int64_t)(m0 + li) * a.ldx];
     if constexpr (PRO == kProGN) {
-        const double* src = a.gn_sums + ((int64_t)((m0 / a.gn_rows_per_scene) * a.gn_ngroups + g) * kGnSlots + lane) * 2;
-#pragma unroll
-        for (int i = 0; i < kGnSlots / 64; ++i) { gsm += src[i * 128]; gsq += src[i * 128 + 1]; }
+        const double* src = a.gn_sums + ((int64_t)((m0 / a.gn_rows_per_scene) * a.gn_ngroups + g) * a.gn_slots + lane) * 2;
+        gn_lane_sums(src, a.gn_slots, gsm, gsq);
     }
     const int et = wave % NT;
     const int erow = lane >> 2, ec = (lane & 3) * 4;
@@ -711,12 +709,12 @@ __global__ __launch_bounds__(256) void chain_linear_stream_kernel(LinearArgs a) 
             for (int o = 32; o > 0; o >>= 1) { gs += __shfl_xor(gs, o); gq += __shfl_xor(gq, o); }
             if (lane == 0) {
                 const int grp = (nt0 + g * a.N) / a.gn_out_group_cols;
-                // this sub-tile's own slot when the (scene, group) block has at most kGnSlots sub-tiles: a plain store
+                // this sub-tile's own slot when the (scene, group) block has at most gn_slots sub-tiles (always, in batch-invariant mode): a plain store
                 const int cbs = a.gn_out_group_cols >> 4;
                 const int rb = (m0 % a.gn_out_rows_per_scene) >> 4, cb = ((nt0 + g * a.N) % a.gn_out_group_cols) >> 4;
-                const bool own = (a.gn_out_rows_per_scene >> 4) * cbs <= kGnSlots;
-                const int slot = own ? rb * cbs + cb : (int)((blockIdx.x * NT + wave) % kGnSlots);
-                double* dst = a.gn_out_sums + (((int64_t)(m0 / a.gn_out_rows_per_scene) * a.gn_out_ngroups + grp) * kGnSlots + slot) * 2;
+                const bool own = (a.gn_out_rows_per_scene >> 4) * cbs <= a.gn_slots;
+                const int slot = own ? rb * cbs + cb : gn_shared_slot((unsigned)(blockIdx.x * NT + wave), a.gn_slots);
+                double* dst = a.gn_out_sums + (((int64_t)(m0 / a.gn_out_rows_per_scene) * a.gn_out_ngroups + grp) * a.gn_slots + slot) * 2;
                 if (own) {
                     typedef double f64x2 __attribute__((ext_vector_type(2)));
                     *reinterpret_cast<f64x2*>(dst) = f64x2{gs, gq};
@@ -806,9 +804,8 @@ __global__ __launch_bounds__(512) void chain_linear_stream32_kernel(LinearArgs a
         shift[1] = a.X[g * a.gX + (int64_t)(m0 + 16 + li) * a.ldx];
     }
     if constexpr (PRO == kProGN) {
-        const double* src = a.gn_sums + ((int64_t)((m0 / a.gn_rows_per_scene) * a.gn_ngroups + g) * kGnSlots + lane) * 2;
-#pragma unroll
-        for (int i = 0; i < kGnSlots / 64; ++i) { gsm += src[i * 128]; gsq += src[i * 128 + 1]; }
+        const double* src = a.gn_sums + ((int64_t)((m0 / a.gn_rows_per_scene) * a.gn_ngroups + g) * a.gn_slots + lane) * 2;
+        gn_lane_sums(src, a.gn_slots, gsm, gsq);
     }
     const int et = wave % NT, eh = wave / NT;         // the 16 x 16 sub-tile this wave finishes (waves >= 2 NT have none)
     const int erow = lane >> 2, ec = (lane & 3) * 4;
@@ -956,9 +953,9 @@ __global__ __launch_bounds__(512) void chain_linear_stream32_kernel(LinearArgs a
                 const int grp = (nt0 + g * a.N) / a.gn_out_group_cols;
                 const int cbs = a.gn_out_group_cols >> 4;
                 const int rb = (mt0 % a.gn_out_rows_per_scene) >> 4, cb = ((nt0 + g * a.N) % a.gn_out_group_cols) >> 4;
-                const bool own = (a.gn_out_rows_per_scene >> 4) * cbs <= kGnSlots;
-                const int slot = own ? rb * cbs + cb : (int)(((blockIdx.x * 2 + eh) * NT + et) % kGnSlots);
-                double* dst = a.gn_out_sums + (((int64_t)(mt0 / a.gn_out_rows_per_scene) * a.gn_out_ngroups + grp) * kGnSlots + slot) * 2;
+                const bool own = (a.gn_out_rows_per_scene >> 4) * cbs <= a.gn_slots;
+                const int slot = own ? rb * cbs + cb : gn_shared_slot((unsigned)((blockIdx.x * 2 + eh) * NT + et), a.gn_slots);
+                double* dst = a.gn_out_sums + (((int64_t)(mt0 / a.gn_out_rows_per_scene) * a.gn_out_ngroups + grp) * a.gn_slots + slot) * 2;
                 if (own) {
                     typedef double f64x2 __attribute__((ext_vector_type(2)));
                     *reinterpret_cast<f64x2*>(dst) = f64x2{gs, gq};
@@ -1087,9 +1084,8 @@ __global__ __launch_bounds__(512) void chain_linear_h3_kernel(LinearArgs a) {
         }
     double gsm = 0.0, gsq = 0.0;
     if constexpr (PRO == kProGN) {
-        const double* src = a.gn_sums + ((int64_t)((m0 / a.gn_rows_per_scene) * a.gn_ngroups + g) * kGnSlots + lane) * 2;
-#pragma unroll
-        for (int i = 0; i < kGnSlots / 64; ++i) { gsm += src[i * 128]; gsq += src[i * 128 + 1]; }
+        const double* src = a.gn_sums + ((int64_t)((m0 / a.gn_rows_per_scene) * a.gn_ngroups + g) * a.gn_slots + lane) * 2;
+        gn_lane_sums(src, a.gn_slots, gsm, gsq);
     }
     const int et = wave % NT, eh = wave / NT;         // the 16 x 16 sub-tile this wave finishes (waves >= NT RH have none)
     const int erow = lane >> 2, ec = (lane & 3) * 4;
@@ -1275,9 +1271,9 @@ __global__ __launch_bounds__(512) void chain_linear_h3_kernel(LinearArgs a) {
                 const int grp = (nt0 + g * a.N) / a.gn_out_group_cols;
                 const int cbs = a.gn_out_group_cols >> 4;
                 const int rb = (mt0 % a.gn_out_rows_per_scene) >> 4, cb = ((nt0 + g * a.N) % a.gn_out_group_cols) >> 4;
-                const bool own = (a.gn_out_rows_per_scene >> 4) * cbs <= kGnSlots;
-                const int slot = own ? rb * cbs + cb : (int)(((blockIdx.x * RH + eh) * NT + et) % kGnSlots);
-                double* dst = a.gn_out_sums + (((int64_t)(mt0 / a.gn_out_rows_per_scene) * a.gn_out_ngroups + grp) * kGnSlots + slot) * 2;
+                const bool own = (a.gn_out_rows_per_scene >> 4) * cbs <= a.gn_slots;
+                const int slot = own ? rb * cbs + cb : gn_shared_slot((unsigned)((blockIdx.x * RH + eh) * NT + et), a.gn_slots);
+                double* dst = a.gn_out_sums + (((int64_t)(mt0 / a.gn_out_rows_per_scene) * a.gn_out_ngroups + grp) * a.gn_slots + slot) * 2;
                 if (own) {
                     typedef double f64x2 __attribute__((ext_vector_type(2)));
                     *reinterpret_cast<f64x2*>(dst) = f64x2{gs, gq};
@@ -1476,13 +1472,15 @@ hipError_t go_h3(const LinearArgs& a0, int groups, hipStream_t s) {
     a.tile_map = 0;
     // 32-row tiles (every W fragment feeds two row halves) while their grid still has a workgroup per CU
     static const int min_wg32 = [] { const char* e = dev_env("PARQ_CHAIN_H3_ROWS32"); return e ? atoi(e) : 256; }();   // 0: never
-    const int64_t wg32 = (int64_t)((a.N / 16 + NT - 1) / NT) * (a.M / 32) * groups;
+    const int gm = a.geom_M > 0 ? a.geom_M : a.M;      // batch-invariant inference: ONE scene's rows decide, so that the scene meets the
+    // same row-tile form alone and in a batch
+    const int64_t wg32 = (int64_t)((a.N / 16 + NT - 1) / NT) * (gm / 32) * groups;
     constexpr bool fits32 = true;
     // measured per launch at the shipped width (profiles/r06_chain_fp16x3_rows32_threshold.txt): 32-row tiles win wherever their grid has a
     // workgroup per CU, except the launch with a plain addend (self in-projection: A and the addend for two row halves) below two full rounds
     static const int add_factor = [] { const char* e = dev_env("PARQ_CHAIN_H3_ROWS32_ADD"); return e ? atoi(e) : 2; }();
     const int64_t need32 = (PRO == kProNone && ADD2 != 0) ? add_factor * (int64_t)min_wg32 : min_wg32;
-    const bool rows32 = fits32 && min_wg32 > 0 && a.M % 32 == 0 && wg32 >= need32 && (!a.gn_sums || a.gn_rows_per_scene % 32 == 0) &&
+    const bool rows32 = fits32 && min_wg32 > 0 && gm % 32 == 0 && a.M % 32 == 0 && wg32 >= need32 && (!a.gn_sums || a.gn_rows_per_scene % 32 == 0) &&
                         (!a.gn_out_sums || a.gn_out_rows_per_scene % 32 == 0);
     if (rows32) {
         constexpr int R2 = fits32 ? 2 : 1;
@@ -1523,11 +1521,16 @@ hipError_t launch_chain_linear(const LinearArgs& a_in, int groups, hipStream_t s
     static const bool wp_off = [] { const char* e = dev_env("PARQ_CHAIN_WPACK"); return e && e[0] == '0'; }();
     // the latency-bound regime (one or a few scenes); above it the generic kernel's 32 x 32 tiles fill the chip
     static const int chain_max_m = [] { const char* e = dev_env("PARQ_CHAIN_MAX_M"); return e ? atoi(e) : 4096; }();   // 0: generic kernel only (measured at 8 scenes, M = 2048: 1.64 -> 1.37 ms of linears)
-    if (a_in.M > chain_max_m) return hipErrorNotSupported;
+    // batch-invariant inference (LinearArgs::geom_M): every choice below — this kernel family or the generic one, sub-tiles per
+    // workgroup, 16- or 32-row tiles — is made from ONE scene's rows; the batch only multiplies the grid
+    const int gm = a_in.geom_M > 0 ? a_in.geom_M : a_in.M;
+    if (gm > chain_max_m) return hipErrorNotSupported;
     LinearArgs a = a_in;
+    if (a.gn_slots <= 0) a.gn_slots = kGnSlots;
+    if (a.gn_slots % 64 != 0) return hipErrorInvalidValue;
     if (wp_off || (a.Wp && (!al16(a.Wp) || a.ldw != a.K))) a.Wp = nullptr;     // the tile-ordered copy mirrors a dense [N][K] matrix
     // shape / layout conditions of the specialised kernel
-    if (a.M % 16 != 0 || a.N % 16 != 0) return hipErrorNotSupported;
+    if (gm % 16 != 0 || a.M % 16 != 0 || a.N % 16 != 0) return hipErrorNotSupported;
     if (a.relu_mask || a.drop_p > 0.f || a.rows_per_batch != a.M || a.col_blk != a.N) return hipErrorNotSupported;
     if ((a.ldx | a.ldw | a.y_row) % 4 != 0 || !al16(a.X) || !al16(a.W) || !al16(a.Y)) return hipErrorNotSupported;
     if ((a.gX | a.gW | a.gY | a.gBias | a.gGamma) % 4 != 0) return hipErrorNotSupported;
@@ -1554,7 +1557,7 @@ hipError_t launch_chain_linear(const LinearArgs& a_in, int groups, hipStream_t s
         /* a ragged sub-tile count (head layer 1: 129) takes full-width tiles with a partial last one instead of narrower tiles */ \
         /* where the grid is four rounds and more (head layer 1 at one / two / four / eight scenes: 23.0 | 24.2, 35.4 | 36.8, 66.0 | 60.5 us, -0.75 % per forward at eight) */ \
         if (nt < nt_h3 && nt_h3 == 4 && a.N >= 1024 && (!a.X2 || a.x2_ncols >= a.N) && h3_partial &&             \
-            (int64_t)((a.N / 16 + 3) / 4) * (a.M / 32) * groups >= 1024) nt = 4;                                 \
+            (int64_t)((a.N / 16 + 3) / 4) * (gm / 32) * groups >= 1024) nt = 4;                                 \
         const hipError_t e = nt == 4   ? go_h3<KK, 4, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s)          \
                              : nt == 3 ? go_h3<KK, 3, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s)          \
                              : nt == 2 ? go_h3<KK, 2, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s)          \
@@ -1622,13 +1625,13 @@ hipError_t launch_chain_linear(const LinearArgs& a_in, int groups, hipStream_t s
     // one scene: head layer 1 34.9 -> 32.5 us, head layer 2 23.3 -> 18.5, self in-projection 30.8 -> 31.6, the N = 1024 launches
     // (128 workgroups: below the threshold) 10.8 -> 20; forward 2.380 -> 2.333 ms at one scene, 7.51 -> 6.82 ms at four
     static const int min_wg32 = [] { const char* e = dev_env("PARQ_CHAIN_K1024_ROWS32"); return e ? atoi(e) : 256; }();   // 0: never
-    const bool rows32_ok = min_wg32 > 0 && a.M % 32 == 0 && (!a.gn_sums || a.gn_rows_per_scene % 32 == 0) &&
+    const bool rows32_ok = min_wg32 > 0 && gm % 32 == 0 && a.M % 32 == 0 && (!a.gn_sums || a.gn_rows_per_scene % 32 == 0) &&
                            (!a.gn_out_sums || a.gn_out_rows_per_scene % 32 == 0);
 #define PARQ_STREAM(PRO, ADD2, BIAS, RELU, RES, GNOUT)                                                          \
     {                                                                                                           \
         if (rows32_ok) {                                                                                        \
             const int nt = pick_nt(a, nt_big);                                                                  \
-            if ((int64_t)(a.N / (16 * nt)) * (a.M / 32) * groups >= min_wg32) {                                 \
+            if ((int64_t)(a.N / (16 * nt)) * (gm / 32) * groups >= min_wg32) {                                 \
                 if (nt == 4) return go_stream32<1024, 4, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);      \
                 if (nt == 3) return go_stream32<1024, 3, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);      \
                 if (nt == 2) return go_stream32<1024, 2, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);      \

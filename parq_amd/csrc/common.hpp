@@ -99,6 +99,30 @@ constexpr int kWave = 64;
 // order that does not depend on arrival) or add into slot (tile % kGnSlots) with fp64 atomics (generic kernel; slots zeroed by the
 // iteration's first kernel).  Consumers sum all slots: 4 per lane and one shuffle tree.
 constexpr int kGnSlots = 256;
+// a consumer lane's share of the slots of one (scene, group): slots lane, lane + 64, ... in that order (src points at slot `lane`).
+// Batch-invariant inference sizes the slots per launch (LinearArgs::gn_slots); the default count keeps its unrolled form.
+__device__ __forceinline__ void gn_lane_sums(const double* __restrict__ src, int slots, double& sm, double& sq) {
+    if (slots == kGnSlots) {
+#pragma unroll
+        for (int i = 0; i < kGnSlots / 64; ++i) { sm += src[i * 128]; sq += src[i * 128 + 1]; }
+    } else {
+        // four slots' loads in flight at a time; the additions keep the slot order
+        const int n = slots / 64;
+        int i = 0;
+        for (; i + 4 <= n; i += 4) {
+            double m[4], q[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { m[j] = src[(i + j) * 128]; q[j] = src[(i + j) * 128 + 1]; }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { sm += m[j]; sq += q[j]; }
+        }
+        for (; i < n; ++i) { sm += src[i * 128]; sq += src[i * 128 + 1]; }
+    }
+}
+// the shared slot of a producer without a slot of its own (default geometry only): index mod slots, the default count as a constant
+__device__ __forceinline__ int gn_shared_slot(unsigned idx, int slots) {
+    return slots == kGnSlots ? (int)(idx % (unsigned)kGnSlots) : (int)(idx % (unsigned)slots);
+}
 
 // LDS-DMA (global_load_lds, 16 bytes per lane, wave-uniform LDS base + lane * 16) issued through inline asm.  hipcc knows that the
 // builtin writes LDS asynchronously and answers with s_waitcnt vmcnt(0) in front of later C++ reads of LDS it cannot prove
@@ -394,7 +418,7 @@ struct LinearArgs {
     const double* gn_sums; const float* gn_gamma; const float* gn_beta;
     int gn_rows_per_scene; int gn_ngroups;
     // moments of the OUTPUT (columns < gn_out_ncols) accumulated with fp64 atomics into
-    // gn_out_sums[scene][(n + g*N) / gn_out_group_cols][kGnSlots][2] (zeroed by an earlier kernel)
+    // gn_out_sums[scene][(n + g*N) / gn_out_group_cols][gn_slots][2] (zeroed by an earlier kernel)
     double* gn_out_sums; int gn_out_ncols; int gn_out_group_cols; int gn_out_rows_per_scene; int gn_out_ngroups;
     // grouped launch: blockIdx.y = g adds these element offsets
     int64_t gX, gW, gBias, gY, gGamma;
@@ -424,6 +448,15 @@ struct LinearArgs {
     // call's prologue launch) into the host-visible progress word, so that a host that only needs to know WHETHER the forward has to
     // be re-run can stop waiting one chain tail (~36 us at BASELINE cfg 3) before the forward ends.  nullptr: nothing to publish.
     const int* pub_flags; int* pub_mirror; int* pub_word; const int* pub_epoch; int pub_mask; int pub_peaky;
+    // Batch-invariant inference (parq_set_batch_invariant): the launchers choose kernel, tile shape and sub-tile count from geom_M rows
+    // — ONE scene's — instead of M (0: from M), so that a scene's rows meet the same kernel whatever shares the call.
+    int geom_M;
+    // slots per (scene, group) of gn_sums / gn_out_sums (a multiple of 64; launch_linear reads 0 as kGnSlots).  The mode sizes them so
+    // that every 16 x 16 sub-tile of a (scene, group) block owns one: plain stores, summed by the consumers in slot order.
+    int gn_slots;
+    // generic kernel (linear.hip) only: 1 = a tile stores its moments into the slot of its own coordinates inside the scene's block
+    // instead of adding into slot (tile index % slots) with atomics (the caller sized gn_slots for it and the tiles lie inside scenes)
+    int gn_own;
 };
 __device__ __forceinline__ void publish_progress(const LinearArgs& a) {
     if (a.pub_word != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
@@ -497,6 +530,7 @@ struct FlashArgs {
     // nh > 0: grid index z = b * nh + i covers head (hmap >> 4 i) & 15; partials are indexed by z, everything else by b * H + head.
     int nh; unsigned long long hmap;
     int64_t cache_head_bytes;   // bytes between the cache regions of two (scene, head) pairs; 0 = the kernel's own packed layout
+    int geom_B;                 // batch-invariant inference: the scene count the launchers choose waves / merge width from (0: B)
 };
 struct FlashHead { int b, h, bh; };
 // grid index z of a partial-producing / merging launch -> (scene, head, b * H + head)
@@ -775,7 +809,7 @@ hipError_t launch_gn_stats(const float* X, int64_t ldx, int col0, int ncols, int
 struct BoxDecodeArgs {
     const float* h1; int64_t ld1;      // [M][..]: logits at cols [0,ncls), size_raw at [ncls, ncls+3)
     const float* h2; int64_t ld2;      // [M][2C]: centre hidden | rotation hidden (pre-GroupNorm)
-    const double* gn_sums;             // [B][2][kGnSlots][2] moments of h2 per scene and head
+    const double* gn_sums;             // [B][2][gn_slots][2] moments of h2 per scene and head
     const float* gn_gamma; const float* gn_beta;       // [2][C]
     const float* w3; const float* b3;  // [2][6][C] (centre rows 0..2 of group 0), [2][6]
     int C; int rows_per_scene; float eps;
@@ -797,6 +831,8 @@ struct BoxDecodeArgs {
     int poison_mask;                   // the bits of *poison that count (all of them in the fp16-operand cache modes, else only bit 2)
     const void* const* ind;            // optional CallPtrs block: the five output pointers are ind[1..5] + out_row0 rows (a captured forward)
     int64_t out_row0;
+    int gn_slots;                      // slots per (scene, head) of gn_sums (a multiple of 64; 0 is read as kGnSlots)
+    int geom_M;                        // batch-invariant inference: rows per workgroup are chosen from this many rows (0: from M)
 };
 hipError_t launch_box_decode(const BoxDecodeArgs& a, hipStream_t s);
 // weight packing helpers

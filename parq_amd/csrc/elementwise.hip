@@ -285,11 +285,10 @@ __global__ __launch_bounds__(256) void box_decode_kernel(BoxDecodeArgs a) {
     double sums[4];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-        const double* src = a.gn_sums + ((int64_t)(scene * 2 + g) * kGnSlots + lane) * 2;
+        const double* src = a.gn_sums + ((int64_t)(scene * 2 + g) * a.gn_slots + lane) * 2;
         sums[2 * g] = 0.0;
         sums[2 * g + 1] = 0.0;
-#pragma unroll
-        for (int i = 0; i < kGnSlots / 64; ++i) { sums[2 * g] += src[i * 128]; sums[2 * g + 1] += src[i * 128 + 1]; }
+        gn_lane_sums(src, a.gn_slots, sums[2 * g], sums[2 * g + 1]);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -417,11 +416,10 @@ __global__ __launch_bounds__(256) void box_decode256_kernel(BoxDecodeArgs a) {
     double sums[4];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-        const double* src = a.gn_sums + ((int64_t)(scene * 2 + g) * kGnSlots + lane) * 2;
+        const double* src = a.gn_sums + ((int64_t)(scene * 2 + g) * a.gn_slots + lane) * 2;
         sums[2 * g] = 0.0;
         sums[2 * g + 1] = 0.0;
-#pragma unroll
-        for (int i = 0; i < kGnSlots / 64; ++i) { sums[2 * g] += src[i * 128]; sums[2 * g + 1] += src[i * 128 + 1]; }
+        gn_lane_sums(src, a.gn_slots, sums[2 * g], sums[2 * g + 1]);
     }
     const f32x4v x0 = *reinterpret_cast<const f32x4v*>(h2 + 4 * lane);
     const f32x4v x1 = *reinterpret_cast<const f32x4v*>(h2 + C + 4 * lane);
@@ -728,11 +726,15 @@ hipError_t launch_gn_stats(const float* X, int64_t ldx, int col0, int ncols, int
     return hipGetLastError();
 }
 
-hipError_t launch_box_decode(const BoxDecodeArgs& a, hipStream_t s) {
+hipError_t launch_box_decode(const BoxDecodeArgs& a_in, hipStream_t s) {
+    BoxDecodeArgs a = a_in;
     if (a.ncls > kMaxCls || a.ncls < 1) return hipErrorInvalidValue;
+    if (a.gn_slots <= 0) a.gn_slots = kGnSlots;
+    if (a.gn_slots % 64 != 0) return hipErrorInvalidValue;
+    const int gm = a.geom_M > 0 ? a.geom_M : a.M;      // batch-invariant inference: one scene's rows
     // one row per wave; rows per workgroup: 1 while that still leaves CUs idle (pure latency: spread the rows over the chip), else 4
     static const int rows_env = [] { const char* e = dev_env("PARQ_DECODE_ROWS"); return e ? atoi(e) : 0; }();
-    const int rows = (rows_env >= 1 && rows_env <= 4) ? rows_env : (a.M <= 2 * device_num_cus() ? 1 : 4);
+    const int rows = (rows_env >= 1 && rows_env <= 4) ? rows_env : (gm <= 2 * device_num_cus() ? 1 : 4);
     static const bool fast_off = [] { const char* e = dev_env("PARQ_DECODE_FAST"); return e && e[0] == '0'; }();
     const bool al = ((reinterpret_cast<uintptr_t>(a.h2) | reinterpret_cast<uintptr_t>(a.gn_gamma) | reinterpret_cast<uintptr_t>(a.gn_beta) |
                       reinterpret_cast<uintptr_t>(a.w3)) & 15u) == 0 && a.ld2 % 4 == 0;

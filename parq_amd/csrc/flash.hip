@@ -734,7 +734,8 @@ hipError_t merge_dh(const FlashArgs& a, hipStream_t s) {
     const size_t lds = ((size_t)a.nsplit * 32 + 8 * 32 + (size_t)2 * 16 * 32) * sizeof(float);
     static const int dg_env = [] { const char* e = dev_env("PARQ_MERGE_DG"); return e ? atoi(e) : 0; }();
     // 8 dims per workgroup while that is what it takes to cover the chip (one scene), else 16
-    const int64_t wg16 = (int64_t)ceil_div(a.Lq, 32) * a.B * flash_launch_heads(a) * (DH / 16);
+    // (batch-invariant inference, FlashArgs::geom_B: the width is chosen as for that many scenes)
+    const int64_t wg16 = (int64_t)ceil_div(a.Lq, 32) * (a.geom_B > 0 ? a.geom_B : a.B) * flash_launch_heads(a) * (DH / 16);
     const int dg = dg_env == 8 || dg_env == 16 ? dg_env : (wg16 < device_num_cus() ? 8 : 16);
     static const bool fixed_off = [] { const char* e = dev_env("PARQ_MERGE_FIXED"); return e && e[0] == '0'; }();
     if constexpr (DH == 64) {
@@ -845,7 +846,7 @@ static bool dh_ok(int dh) { return dh == 32 || dh == 64 || dh == 128 || dh == 25
 hipError_t launch_flash(const FlashArgs& a, hipStream_t s) {
     if (!dh_ok(a.dh) || a.nsplit < 1 || a.nsplit > 256) return hipErrorInvalidValue;
     if (a.nsplit > ceil_div(a.Lk, flash_key_tile(a.dh))) return hipErrorInvalidValue;
-    const int nw = flash_pick_nw(a.B, a.H, a.Lq, a.Lk, a.dh, device_num_cus());
+    const int nw = flash_pick_nw(a.geom_B > 0 ? a.geom_B : a.B, a.H, a.Lq, a.Lk, a.dh, device_num_cus());
     switch (a.dh) {
         case 32: return launch_dh<32>(a, nw, s);
         case 64: return launch_dh<64>(a, nw, s);

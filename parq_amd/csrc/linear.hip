@@ -151,12 +151,12 @@ __global__ __launch_bounds__(kWaves * kWave) void linear_f32_kernel(LinearArgs a
         const double cnt = (double)a.gn_rows_per_scene * (double)a.K;
         const int sc_lo = m0 / a.gn_rows_per_scene;
         const int sc_hi = (m0 + T - 1 < a.M ? m0 + T - 1 : a.M - 1) / a.gn_rows_per_scene;
-        if (sc_lo == sc_hi) {
-            // the producer left its moments in kGnSlots slots per (scene, group): kGnSlots / 64 per lane, then one shuffle tree
-            const double* src = a.gn_sums + ((int64_t)(sc_lo * a.gn_ngroups + g) * kGnSlots + lane) * 2;
+        // (batch-invariant mode, geom_M: the form is chosen from the scene's rows alone — never from where the tile lies in the batch)
+        if (a.geom_M > 0 ? a.gn_rows_per_scene % T == 0 : sc_lo == sc_hi) {
+            // the producer left its moments in gn_slots slots per (scene, group): gn_slots / 64 per lane, then one shuffle tree
+            const double* src = a.gn_sums + ((int64_t)(sc_lo * a.gn_ngroups + g) * a.gn_slots + lane) * 2;
             double Sm = 0.0, Qs = 0.0;
-#pragma unroll
-            for (int i = 0; i < kGnSlots / 64; ++i) { Sm += src[i * 128]; Qs += src[i * 128 + 1]; }
+            gn_lane_sums(src, a.gn_slots, Sm, Qs);
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) {
                 Sm += __shfl_xor(Sm, o);
@@ -176,9 +176,9 @@ __global__ __launch_bounds__(kWaves * kWave) void linear_f32_kernel(LinearArgs a
                 const int m = m0 + s * 16 + li;
                 const int scene = (m_ok[s] ? m : 0) / a.gn_rows_per_scene;
                 double Sm = 0.0, Qs = 0.0;
-                for (int sl = 0; sl < kGnSlots; ++sl) {
-                    Sm += a.gn_sums[((int64_t)(scene * a.gn_ngroups + g) * kGnSlots + sl) * 2 + 0];
-                    Qs += a.gn_sums[((int64_t)(scene * a.gn_ngroups + g) * kGnSlots + sl) * 2 + 1];
+                for (int sl = 0; sl < a.gn_slots; ++sl) {
+                    Sm += a.gn_sums[((int64_t)(scene * a.gn_ngroups + g) * a.gn_slots + sl) * 2 + 0];
+                    Qs += a.gn_sums[((int64_t)(scene * a.gn_ngroups + g) * a.gn_slots + sl) * 2 + 1];
                 }
                 gn_mean_rstd(Sm, Qs, 1.0 / cnt, a.norm_eps, gn_mean[s], gn_rstd[s]);
             }
@@ -384,15 +384,25 @@ __global__ __launch_bounds__(kWaves * kWave) void linear_f32_kernel(LinearArgs a
                     S += dred[w * 2 + 0];
                     Q2 += dred[w * 2 + 1];
                 }
-                // slot = tile index mod kGnSlots: a handful of workgroups contend on one address
-                const int slot = (int)(blockIdx.x % kGnSlots);
-                double* dst = a.gn_out_sums + (((int64_t)sc_first * a.gn_out_ngroups + grp) * kGnSlots + slot) * 2;
-                atomicAdd(dst, S);
-                atomicAdd(dst + 1, Q2);
+                if (a.gn_own) {
+                    // batch-invariant mode: the slot of this tile's coordinates inside the scene's block, a plain store (launch_linear
+                    // checked that the tiles lie inside scenes and groups and that every one has a slot)
+                    const int cbs = (a.gn_out_group_cols + T - 1) / T;
+                    const int slot = ((m0 % a.gn_out_rows_per_scene) / T) * cbs + ((n0 + g * a.N) % a.gn_out_group_cols) / T;
+                    double* dst = a.gn_out_sums + (((int64_t)sc_first * a.gn_out_ngroups + grp) * a.gn_slots + slot) * 2;
+                    dst[0] = S;
+                    dst[1] = Q2;
+                } else {
+                    // slot = tile index mod gn_slots: a handful of workgroups contend on one address
+                    const int slot = gn_shared_slot(blockIdx.x, a.gn_slots);
+                    double* dst = a.gn_out_sums + (((int64_t)sc_first * a.gn_out_ngroups + grp) * a.gn_slots + slot) * 2;
+                    atomicAdd(dst, S);
+                    atomicAdd(dst + 1, Q2);
+                }
             }
         } else if (row_ok) {
-            const int slot = (int)(blockIdx.x % kGnSlots);
-            double* dst = a.gn_out_sums + (((int64_t)(om / a.gn_out_rows_per_scene) * a.gn_out_ngroups + grp) * kGnSlots + slot) * 2;
+            const int slot = gn_shared_slot(blockIdx.x, a.gn_slots);
+            double* dst = a.gn_out_sums + (((int64_t)(om / a.gn_out_rows_per_scene) * a.gn_out_ngroups + grp) * a.gn_slots + slot) * 2;
             atomicAdd(dst, gs);
             atomicAdd(dst + 1, gq);
         }
@@ -415,16 +425,34 @@ static int pick_tile(int64_t tiles32) {
     return tiles32 < (below > 0 ? below : device_num_cus()) ? 16 : 32;
 }
 
-hipError_t launch_linear(const LinearArgs& a, int groups, hipStream_t s) {
-    if (a.K % 16 != 0 || a.M <= 0 || a.N <= 0) return hipErrorInvalidValue;
+// gn_own (batch-invariant inference) asks that no moment of the output is added with atomics: possible where every T x T tile lies
+// inside one scene and one group and has a slot of its own
+static bool gn_own_ok(const LinearArgs& a, int T) {
+    if (!a.gn_out_sums) return true;
+    const int cbs = ceil_div(a.gn_out_group_cols, T);
+    return a.gn_out_rows_per_scene % T == 0 && a.gn_out_group_cols % T == 0 && a.gn_out_ncols % T == 0 &&
+           (int64_t)(a.gn_out_rows_per_scene / T) * cbs <= a.gn_slots;
+}
+
+hipError_t launch_linear(const LinearArgs& a_in, int groups, hipStream_t s) {
+    if (a_in.K % 16 != 0 || a_in.M <= 0 || a_in.N <= 0) return hipErrorInvalidValue;
+    LinearArgs a = a_in;
+    if (a.gn_slots <= 0) a.gn_slots = kGnSlots;
+    if (a.gn_slots % 64 != 0) return hipErrorInvalidValue;
     // the latency-bound regime (one or a few scenes): compile-time specialised kernels of the decoder chain (chain.hip)
     {
         const hipError_t e = launch_chain_linear(a, groups, s);
         if (e != hipErrorNotSupported) return e;
     }
     if (a.W2) return hipErrorInvalidValue;          // a second operand pair exists in chain.hip only (callers test chain_linear_supported)
-    const int64_t tiles32 = (int64_t)ceil_div(a.N, 32) * ceil_div(a.M, 32) * groups;
-    const int T = pick_tile(tiles32);
+    // batch-invariant inference: the tile edge follows from ONE scene's rows (geom_M); 16 where a 32-row tile would straddle scenes
+    const int gm = a.geom_M > 0 ? a.geom_M : a.M;
+    const int64_t tiles32 = (int64_t)ceil_div(a.N, 32) * ceil_div(gm, 32) * groups;
+    int T = pick_tile(tiles32);
+    if (a.gn_own) {
+        if (T == 32 && ((a.gn_sums && a.gn_rows_per_scene % 32 != 0) || !gn_own_ok(a, 32))) T = 16;
+        if (!gn_own_ok(a, T)) return hipErrorInvalidValue;      // (api.hip asks for own slots only where they exist)
+    }
     const int64_t tiles = (int64_t)ceil_div(a.N, T) * ceil_div(a.M, T);
     if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
     dim3 grid((unsigned)tiles, groups, 1);

@@ -227,7 +227,7 @@ class _WsEntry:
 
 class _Run:
     """One enqueued inference forward as its range check must see it: the workspace, mirror slot and epoch it ran with and the
-    arithmetic settings (attention mode, head tiers, seam fusion) it was enqueued under.  A deferred check (InFlight) runs after
+    arithmetic settings (attention mode, head tiers, seam fusion, batch invariance) it was enqueued under.  A deferred check (InFlight) runs after
     other forwards may have re-used the workspace's fields or switched the module to safer arithmetic: it reads this, not them."""
     __slots__ = ("entry", "slot", "epoch", "settings")
 
@@ -443,6 +443,17 @@ class PARQDecoder(_Tracked, nn.Module):
         # back to one launch per dependent stage for good.
         self.fuse_seams = False
         self._seams_set = None
+        # Batch-invariant inference (include/parq_hip.h parq_set_batch_invariant).  By default the launch geometry follows the call
+        # (key-split counts, row tiles, GroupNorm moment slots are chosen from the number of scenes), so a scene's outputs differ in the
+        # last bits with the number of scenes that share its forward.  True: every such choice is made as for ONE scene and the batch only
+        # multiplies the grid — scene i of a B-scene call returns the bits of the same scene passed alone (to a module in the same state:
+        # weights, attention_mode, safe_heads, fuse_seams, token dtype; no range / too-peaked flag raised), wherever it stands and whatever
+        # the others hold, with the same number of launches at every B.  Honoured by forward (captured or not), InFlight, prepare /
+        # iterate, cross_attention_map and cross_attention_view_mass; forward_view_sharded, forward_train and the autograd path keep
+        # the default geometry.  Costs throughput at B > 1 (profiles/batch_invariant_ab.json); changing it drops the cached workspaces
+        # (they are sized differently) and re-captures the forward.
+        self.batch_invariant = False
+        self._inv_set = None
         # range_check = "sync" only (there a wrong guess costs a re-run, never a NaN forward): a head on the fp16 x 3 tier returns to the
         # fast tier after this many CONSECUTIVE forwards in which all of its rows kept a probability sum of at least tier_return_margin x
         # the guard threshold.  0 (default) = heads never return by themselves.
@@ -540,9 +551,9 @@ class PARQDecoder(_Tracked, nn.Module):
             self._peaky_fallback(v >> 8, "detected after an earlier forward, whose outputs are NaN from that iteration on")
 
     def _settings(self):
-        """(attention mode, head tiers, seam fusion) as the next forward's _handle() will set them."""
+        """(attention mode, head tiers, seam fusion, batch invariance) as the next forward's _handle() will set them."""
         return (self.attention_mode, (int(self.safe_heads) if self.num_heads <= 16 else 0, 0 if self.range_check == "off" else 1),
-                bool(self.fuse_seams))
+                bool(self.fuse_seams), bool(self.batch_invariant))
 
     def _range_after_forward(self, run, sc, dev):
         """"sync" policy: wait for the forward `run` (a _Run) and read what it raised; True = re-run it (with the fp32 kernels after a
@@ -552,7 +563,7 @@ class PARQDecoder(_Tracked, nn.Module):
         first call on.  What the forward could raise is decided by the settings it was ENQUEUED under: a deferred check (InFlight) may
         find the module already switched by another forward's check — then the fallback has nothing left to change, and the forward
         is re-run all the same because it ran under the old settings."""
-        mode, (_, poison), seams = run.settings
+        mode, (_, poison), seams, _inv = run.settings
         first = mode == "split8" and not self._peaky_checked and self.range_check != "off"
         if not first and (self.range_check != "sync" or mode not in ("split", "split8", "fp16")):
             return False
@@ -636,6 +647,7 @@ class PARQDecoder(_Tracked, nn.Module):
             self._train_tok_set = 0          # and the one its training entry points accept
             self._tiers_set = None
             self._seams_set = None
+            self._inv_set = None
             self._bwd_batched_set = None
             self._bwd_streams_set = None
             self._train_ws = None
@@ -668,6 +680,11 @@ class PARQDecoder(_Tracked, nn.Module):
         if self._seams_set != bool(self.fuse_seams):
             _lib.check(_lib.load().parq_set_seam_fusion(self._h, int(bool(self.fuse_seams))), "parq_set_seam_fusion")
             self._seams_set = bool(self.fuse_seams)
+        if self._inv_set != bool(self.batch_invariant):
+            _lib.check(_lib.load().parq_set_batch_invariant(self._h, int(bool(self.batch_invariant))), "parq_set_batch_invariant")
+            if self._inv_set is not None or self.batch_invariant:
+                self._ws.clear()                       # inference workspaces are sized differently (key-split partials, moment slots)
+            self._inv_set = bool(self.batch_invariant)
         if apply_mode and self._mode_set != self.attention_mode:
             if self.attention_mode not in ATTENTION_MODES:
                 raise ValueError(f"attention_mode must be one of {sorted(ATTENTION_MODES)}")
@@ -1056,13 +1073,13 @@ class PARQDecoder(_Tracked, nn.Module):
         self._set_mirror(entry.slot)
         self._epoch = (self._epoch % 0x7ffffff0) + 1
         entry.epoch = self._epoch                           # (the device stores it into the slot's progress word)
-        run = _Run(entry, entry.slot, self._epoch, (self._mode_set, self._tiers_set, self._seams_set))
+        run = _Run(entry, entry.slot, self._epoch, (self._mode_set, self._tiers_set, self._seams_set, self._inv_set))
         _lib.check(lib.parq_set_progress(h, C.c_void_p(self._progress_ptr(entry.slot)), self._epoch), "parq_set_progress")
         stream = C.c_void_p(entry.stream.cuda_stream)
         po = self._out_pointers(flat.data_ptr(), self.num_layers * sc.B * self.num_queries)
         graph = None
         if self.use_graph and not self._profiling:
-            key = (self._arena_gen, self._mode_set, self._tiers_set, self._seams_set, tt)
+            key = (self._arena_gen, self._mode_set, self._tiers_set, self._seams_set, self._inv_set, tt)
             graph = entry.graphs.get(key)
             if graph is None and entry.last_key == key:
                 graph = self._capture(entry, key, sc, stream)

@@ -48,6 +48,16 @@ class PARQ(_Base):
         self.token_dtype = None
         self.synced_metrics = {}          # validation metrics averaged over the ranks (what the reference logs with sync_dist=True)
 
+    @property
+    def batch_invariant(self):
+        """Batch-invariant inference of the decoder (``PARQDecoder.batch_invariant``): a scene's outputs — hence its detections —
+        do not depend on how many scenes share the call.  The ray-PE tokenisation and ``parse_pred`` work scene by scene as they are."""
+        return self.box3d_decoder.batch_invariant
+
+    @batch_invariant.setter
+    def batch_invariant(self, on):
+        self.box3d_decoder.batch_invariant = bool(on)
+
     def set_data_parallel(self, on=True):
         """One process per GPU, scenes sharded (train.py:103-108 runs DDP): with ``on`` every trainable tensor of the module —
         the decoder's flat gradient arena and the ray-PE encoder's four tensors — is averaged over the default process group
