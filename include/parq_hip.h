@@ -256,6 +256,43 @@ int parq_forward_replay(parq_handle h, parq_graph_t g, const parq_scene *scene, 
 int64_t parq_graph_nodes(parq_graph_t g);
 int parq_graph_destroy(parq_graph_t g);
 
+/* A forward that re-projects only the views that changed (a streaming window of V key frames in which a few are replaced per step).
+ * parq_forward (`graph` NULL: launch by launch) or parq_forward_replay (`graph` from parq_forward_capture, checked as there) with the
+ * hoisted K/V projection restricted to the view slots listed in `views` (n_views distinct indices in [0, V), any order); the K / V
+ * rows of every other view are read from the cache as an earlier forward in this workspace left them.  The prologue, the call's
+ * pointer block and all iterations run as always: poses, cameras and T_world_local of ALL views are read from `scene` every call.
+ *   n_views == V      every view: the launches and the bits of parq_forward / parq_forward_replay.
+ *   n_views == 0      valid (only poses or cameras changed): nothing is projected.
+ *   otherwise         adjacent listed slots are merged into runs; every run is ONE projection launch per distinct layer over the token
+ *                     rows [v0 * h * w, (v1 + 1) * h * w), widened outward to the granularity of the kernel that runs it — 64 rows
+ *                     (the persistent kernel's tile = one 64-key stage of the mode-4 cache; dims 128 / 256), 128 rows (the tiled
+ *                     kernel) or one 32-key cache block (dims above 256) — and clamped to V * h * w; runs that touch after widening
+ *                     are merged.  h * w needs no alignment: re-projecting a few rows of a clean neighbour writes the bits that are
+ *                     there (a cache row depends on its own token row and the weights only).  Attention mode 0 keeps no cache layout
+ *                     addressed by key: it projects all rows (or none when n_views == 0) and says so in rows_projected.
+ * rows_projected (may be NULL): the token rows PER SCENE that were projected, after widening.
+ * The caller's side of the contract: `scene->tokens` holds, in the rows of every view that is NOT listed, exactly what it held when
+ * those rows were last projected into this workspace, and the tokens of all views were made for the scene's present T_world_local
+ * (the ray points of the positional encoding are expressed in the local frame: a new local frame means new tokens for every view).
+ * Validity: the library keeps, per workspace address, a note of what the cache there was last built with by a whole inference
+ * forward — shape, attention mode, head-tier mask, token type, the packed arena and its pack count, the batch-invariant flag.  A call
+ * that lists fewer than V views against a workspace whose note is missing or differs returns PARQ_ERR_STATE naming the field, and
+ * enqueues nothing.  parq_prepare, parq_forward_train, parq_iterate_sharded and parq_pack_weights drop the note.  The range mirror
+ * word (parq_set_range_mirror) is part of the note: a subset call under another word than the one the cache was built under is
+ * PARQ_ERR_STATE too (only the handle's present word is ever read).
+ * Flags.  The range flag comes from the projection, so it would be lost with the rows a subset call skips.  Two things keep it:
+ * (1) on the device, a subset call does not clear the workspace's range flag word in its prologue — a flag raised by the forward
+ * that projected the skipped rows, even one still in flight, poisons the subset forward's outputs as well and is raised in the
+ * mirror word again, in stream order; only a call that lists all views clears it.  (2) on the host, a subset call that finds a
+ * range or too-peaked bit raised in the handle's mirror word returns PARQ_ERR_STATE for as long as the word is raised; a caller
+ * who takes the word (parq_mirror_take) and finds it raised lists all views next.  With NO mirror word set (NULL) the host check
+ * (2) does not exist: such a caller reads the workspace's flag word itself ("flags", parq_workspace_lookup) or lives with (1) —
+ * NaN outputs from every subset call until one lists all views.
+ * A view index outside [0, V), a duplicate, n_views outside [0, V] or a NULL list with n_views > 0 is PARQ_ERR_ARG.
+ * (Parenthesised name: see parq_set_batch_invariant; typed in _lib.EXTRA_SYMBOLS.) */
+int (parq_forward_views)(parq_handle h, parq_graph_t graph, const parq_scene *scene, void *workspace, size_t workspace_bytes,
+                         const parq_outputs *outs, const int32_t *views, int32_t n_views, int64_t *rows_projected, parq_stream stream);
+
 /* Stepping interface (teacher-forced parity tests, custom drivers):
  *   parq_prepare  : T_camera_local and the hoisted K/V cache (transformer_parq.py:298-305)
  *   parq_iterate  : one loop body (:310-335).  ref_in (B,Q,3) normalised reference points,

@@ -5,6 +5,7 @@ Public surface mirrors the reference (ymingxie/PARQ):
     AddRayPE     (model/ray_positional_encoding.py:29)  ray-point PE (+ fused tokenisation)
     Pose, Camera (utils/wrappers.py:194,441)     tensor wrappers drivers pass in
     InFlight     (no counterpart: the reference calls its model once per batch, eval.py:46)  several forwards of one module in flight
+    ViewWindow   (no counterpart: the reference re-projects every view of every snippet)  a streaming window of view slots
     ResnetFPN    (model/resnet_fpn.py:16)        wrapper of a user-supplied ResNet-FPN; its neck is fused into the tokenisation
 The compute lives in ``parq_amd/_C/libparq_hip.so`` (C ABI: include/parq_hip.h).
 """
@@ -28,4 +29,7 @@ def __getattr__(name):
     if name == "InFlight":
         from .inflight import InFlight
         return InFlight
+    if name == "ViewWindow":
+        from .view_window import ViewWindow
+        return ViewWindow
     raise AttributeError(name)

@@ -134,6 +134,8 @@ SYMBOLS = {
 # entry points added since: typed by load() like the table above (whose size tests/test_train_token16_cpu.py pins)
 EXTRA_SYMBOLS = {
     "parq_set_batch_invariant": (C.c_int, [_vp, _i32]),
+    "parq_forward_views": (C.c_int, [_vp, _vp, C.POINTER(ParqScene), _vp, _sz, C.POINTER(ParqOutputs), C.POINTER(_i32), _i32,
+                                     C.POINTER(_i64), _vp]),
 }
 
 _lib = None

@@ -4,12 +4,14 @@
 #include "../../include/parq_hip.h"
 #include "common.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 using namespace parq;
@@ -117,6 +119,18 @@ struct MapRec {
 };
 constexpr size_t kMapRecs = 256;
 
+// what the K/V cache of a workspace was last built with, whole, by an inference forward (host-side note keyed by the workspace address,
+// as MapRec): parq_forward_views projects a subset of the views only into a cache whose note equals the handle's present state.
+// Dropped on entry by every call that rewrites the cache or the token copies next to it, written once a forward is enqueued whole.
+struct CacheRec {
+    int B, V, h, w, mode, tok, inv;
+    uint32_t safe;
+    const void* arena; uint64_t pack_gen;
+    const int* mirror;                        // the range mirror word of that forward (NULL: none)
+    uint64_t seq;
+};
+typedef std::vector<std::pair<int, int>> RowRuns;      // token-row ranges [first, second) of every scene, ascending and disjoint
+
 }  // namespace
 
 struct parq_ctx {
@@ -192,6 +206,17 @@ struct parq_ctx {
         map_recs[wsp] = MapRec{sc->B, sc->V, sc->h, sc->w, cfg.share_weights ? 0 : layer_num, attn_mode, tok_type, state, safe_heads(), ++map_seq};
     }
     uint64_t map_seq = 0;
+    std::map<const void*, CacheRec> cache_recs;   // parq_forward_views: what the cache of a workspace was built with
+    uint64_t pack_gen = 0;                        // counts parq_pack_weights calls
+    void note_cache(const void* wsp, const parq_scene* sc) {
+        if (!cache_recs.count(wsp) && cache_recs.size() >= kMapRecs) {
+            auto oldest = cache_recs.begin();
+            for (auto it = cache_recs.begin(); it != cache_recs.end(); ++it)
+                if (it->second.seq < oldest->second.seq) oldest = it;
+            cache_recs.erase(oldest);
+        }
+        cache_recs[wsp] = CacheRec{sc->B, sc->V, sc->h, sc->w, attn_mode, tok_type, batch_invariant ? 1 : 0, safe_heads(), arena, pack_gen, range_mirror, ++map_seq};
+    }
 };
 
 namespace {
@@ -469,8 +494,14 @@ int settle_weight_state(parq_ctx* c, hipStream_t s) {
     return PARQ_OK;
 }
 
+// which kernel projects K / V in cache mode, hence what a row range is aligned to (kvproj_big.hip: a 32-key cache block)
+bool kvproj_uses_big(const parq_ctx* c, int B, int64_t N) { return kvproj_big_on() && kvproj_big_scratch_floats(B, (int)N, c->C) > 0; }
+int kvproj_granule(const parq_ctx* c, int B, int64_t N) { return kvproj_uses_big(c, B, N) ? 32 : kvproj_split_granule(c->C); }
+
+// runs (parq_forward_views): the token rows of every scene whose K / V are projected, nullptr = all of them.  Cache modes only: one
+// launch per layer and run; attention mode 0 (no cache) projects everything unless the list is empty.
 int do_prepare(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& ws, hipStream_t s, bool train = false,
-               const parq_outputs* call_outs = nullptr, bool forward_call = false) {
+               const parq_outputs* call_outs = nullptr, bool forward_call = false, const RowRuns* runs = nullptr) {
     const float* A = c->arena;
     const int B = sc->B, V = sc->V;
     const int64_t N = (int64_t)V * sc->h * sc->w;
@@ -494,28 +525,37 @@ int do_prepare(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
             pc.ptrs.p[3] = call_outs->size_unnormalized; pc.ptrs.p[4] = call_outs->ortho6d; pc.ptrs.p[5] = call_outs->sem_cls_prob;
             pc.ptrs.p[6] = call_outs->coord_pos;
         }
+        // a forward that skips rows of the projection (parq_forward_views with a subset) keeps flag word 0 as the forward before it left
+        // it: the range flag comes from the projection, so one raised by the forward that projected the skipped rows — possibly still
+        // in flight, its mirror word not yet raised for the host to see — poisons this forward too and is published again, in stream order
+        const int keep0 = runs ? 1 : 0;
         HIPCHK(launch_forward_prologue(sc->T_camera_pseudoCam, sc->T_world_pseudoCam, sc->T_world_local, B, V,
                                        reinterpret_cast<double*>(wsp + ws.T_cl), A + c->ar.refpoint, c->Q, wsp + ws.ref, A + c->ar.dim_t,
-                                       wsp + ws.emb, wsp + ws.flags, (int)(ws.lnp1 - ws.flags), s,      // the 64 flag words and the seam flags behind them
+                                       wsp + ws.emb, wsp + ws.flags + keep0, (int)(ws.lnp1 - ws.flags) - keep0, s,      // the 64 flag words and the seam flags behind them
                                        pc.ind ? &pc : nullptr));
     }
     // hoisted K/V in-projection of the memory tokens: one GEMM per distinct layer,
     // written head-major [b][{K heads, V heads}][N][dh] so the attention kernel streams contiguous panels
     if ((int64_t)B * N > (int64_t)INT32_MAX) return fail(PARQ_ERR_ARG, "B*N too large");
     { const int rc = settle_weight_state(c, s); if (rc) return rc; }
-    for (int li = 0; li < c->nl; ++li) {
+    const RowRuns whole(1, std::make_pair(0, (int)N));
+    const RowRuns& rr = runs ? *runs : whole;
+    for (int li = 0; li < c->nl && !rr.empty(); ++li) {
         Prof p(c, s, PARQ_PROF_KV_PROJ);
         const LayerW& L = c->ar.layers[li];
         if (c->cache_mode()) {
             char* cache = reinterpret_cast<char*>(wsp + ws.kvc) + (size_t)li * kvsplit_cache_bytes(B, c->vheads(), (int)N, c->terms());
-            if (kvproj_big_on() && kvproj_big_scratch_floats(B, (int)N, C) > 0)
-                HIPCHK(launch_kvproj_big(sc->tokens, A + L.kv_whi, A + L.kv_wlo, A + L.cross_in_b + C, B, (int)N, C, cache,
-                                         reinterpret_cast<int*>(wsp + ws.flags), wsp + ws.xsplit, s, c->terms(), c->kind(), c->tok_type));
-            else
-                HIPCHK(launch_kvproj_split(sc->tokens, A + L.kv_whi, A + L.kv_wlo, A + L.cross_in_b + C, B, (int)N, C, c->vheads(),
-                                           cache, reinterpret_cast<int*>(wsp + ws.flags), s,
-                                           c->mixed_tiers(N, train, train && bwd_reads_cache(c, ws)) ? 11 : c->terms_for(N, train, train && bwd_reads_cache(c, ws)),
-                                           c->kind(), c->safe_heads(), c->tok_type));
+            for (const auto& r : rr) {
+                if (kvproj_uses_big(c, B, N))
+                    HIPCHK(launch_kvproj_big(sc->tokens, A + L.kv_whi, A + L.kv_wlo, A + L.cross_in_b + C, B, (int)N, C, cache,
+                                             reinterpret_cast<int*>(wsp + ws.flags), wsp + ws.xsplit, s, c->terms(), c->kind(), c->tok_type,
+                                             r.first, r.second));
+                else
+                    HIPCHK(launch_kvproj_split(sc->tokens, A + L.kv_whi, A + L.kv_wlo, A + L.cross_in_b + C, B, (int)N, C, c->vheads(),
+                                               cache, reinterpret_cast<int*>(wsp + ws.flags), s,
+                                               c->mixed_tiers(N, train, train && bwd_reads_cache(c, ws)) ? 11 : c->terms_for(N, train, train && bwd_reads_cache(c, ws)),
+                                               c->kind(), c->safe_heads(), c->tok_type, r.first, r.second));
+            }
         } else {
             // 16-bit tokens: the fp32 GEMM reads their exact widening (once per forward, in front of the first layer)
             const float* X = sc->tokens;
@@ -1431,6 +1471,8 @@ int parq_pack_weights(parq_handle h, void* arena_v, size_t arena_bytes, parq_str
     c->arena = A;
     c->packed = true;
     c->prepared = false;
+    ++c->pack_gen;                     // every K/V cache was projected with the weights of an earlier pack
+    c->cache_recs.clear();
     return PARQ_OK;
 }
 
@@ -1450,6 +1492,7 @@ int parq_prepare(parq_handle h, const parq_scene* scene, void* workspace, size_t
     carve_workspace(h, scene->B, scene->V, scene->h, scene->w, &ws, h->batch_invariant);
     if (workspace_bytes < (size_t)ws.total * sizeof(float)) return fail(PARQ_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, (size_t)ws.total * sizeof(float));
     h->map_recs.erase(workspace);         // the K cache is rewritten: "cross_q" of an earlier iteration no longer belongs to it
+    h->cache_recs.erase(workspace);       // (a stepping driver owns the workspace from here on)
     return do_prepare(h, scene, (float*)workspace, ws, (hipStream_t)stream);
 }
 
@@ -1509,6 +1552,7 @@ int parq_iterate_sharded(parq_handle h, const parq_scene* scene, void* workspace
     ShardIO sh;
     sh.mask = 1 << phase; sh.in = xchg_in; sh.out = xchg_out; sh.nranks = nranks;
     h->map_recs.erase(workspace);
+    h->cache_recs.erase(workspace);
     rc = do_iterate(h, scene, wsp, ws, layer_num, ref, ref_in == nullptr && h->emb_valid, outs, wsp + ws.ref_next, s, 0, nullptr, false, sh);
     if (rc) return rc;
     if (phase == 2) {
@@ -1565,11 +1609,12 @@ int parq_forward(parq_handle h, const parq_scene* scene, void* workspace, size_t
     Workspace ws;
     int rc = forward_checks(h, scene, workspace, workspace_bytes, outs, &ws);
     if (rc) return rc;
-    h->map_recs.erase(workspace);         // the cache and "cross_q" are rewritten: the note returns once the forward is enqueued whole
+    h->map_recs.erase(workspace);         // the cache and "cross_q" are rewritten: the notes return once the forward is enqueued whole
+    h->cache_recs.erase(workspace);
     rc = do_prepare(h, scene, (float*)workspace, ws, (hipStream_t)stream, false, nullptr, true);
     if (rc) return rc;
     rc = forward_iterations(h, scene, (float*)workspace, ws, outs, (hipStream_t)stream, false);
-    if (rc == PARQ_OK) h->note_iteration(workspace, scene, h->I - 1, 1);
+    if (rc == PARQ_OK) { h->note_iteration(workspace, scene, h->I - 1, 1); h->note_cache(workspace, scene); }
     return rc;
 }
 
@@ -1647,6 +1692,7 @@ int parq_forward_replay(parq_handle h, parq_graph_t g, const parq_scene* scene, 
                                     "other attention settings (mode, head tiers, seam fusion, batch invariance) or token type: capture again");
     hipStream_t s = (hipStream_t)stream;
     h->map_recs.erase(workspace);
+    h->cache_recs.erase(workspace);
     // launched directly with THIS call's pointers: prologue (which also leaves them in the workspace for the recorded part) + K/V projection
     rc = do_prepare(h, scene, (float*)workspace, ws, s, false, outs, true);
     if (rc) return rc;
@@ -1654,6 +1700,98 @@ int parq_forward_replay(parq_handle h, parq_graph_t g, const parq_scene* scene, 
     h->ref_state = 0;
     h->prepared = false;
     h->note_iteration(workspace, scene, h->I - 1, 1);
+    h->note_cache(workspace, scene);
+    return PARQ_OK;
+}
+
+/* ---- a forward that re-projects the listed views only (include/parq_hip.h) ---------------------------------------------------------- */
+// view slots -> maximal runs of adjacent slots -> token rows, widened outward to `gran` rows and clamped to N; runs that touch
+// after widening are merged (parq_amd/view_window.py row_ranges is the same function, for callers that plan ahead)
+static RowRuns view_row_runs(std::vector<int> views, int hw, int64_t N, int gran) {
+    std::sort(views.begin(), views.end());
+    RowRuns out;
+    for (int v : views) {
+        const int64_t r0 = (int64_t)v * hw / gran * gran;
+        int64_t r1 = ((int64_t)(v + 1) * hw + gran - 1) / gran * gran;
+        if (r1 > N) r1 = N;
+        if (!out.empty() && r0 <= out.back().second) { if (r1 > out.back().second) out.back().second = (int)r1; }
+        else out.emplace_back((int)r0, (int)r1);
+    }
+    return out;
+}
+
+int (parq_forward_views)(parq_handle h, parq_graph_t g, const parq_scene* scene, void* workspace, size_t workspace_bytes,
+                         const parq_outputs* outs, const int32_t* views, int32_t n_views, int64_t* rows_projected, parq_stream stream) {
+    if (g && !g->exec) return fail(PARQ_ERR_ARG, "NULL graph");
+    Workspace ws;
+    int rc = forward_checks(h, scene, workspace, workspace_bytes, outs, &ws);
+    if (rc) return rc;
+    const int V = scene->V, hw = scene->h * scene->w;
+    const int64_t N = (int64_t)V * hw;
+    if (n_views < 0 || n_views > V || (n_views > 0 && !views)) return fail(PARQ_ERR_ARG, "parq_forward_views: n_views = %d for %d views (or a NULL list)", n_views, V);
+    if ((int64_t)scene->B * N > (int64_t)INT32_MAX) return fail(PARQ_ERR_ARG, "B*N too large");
+    std::vector<int> list(views, views + n_views);
+    {
+        std::vector<char> seen((size_t)V, 0);
+        for (int v : list) {
+            if (v < 0 || v >= V) return fail(PARQ_ERR_ARG, "parq_forward_views: view index %d outside [0, %d)", v, V);
+            if (seen[(size_t)v]) return fail(PARQ_ERR_ARG, "parq_forward_views: view index %d listed twice", v);
+            seen[(size_t)v] = 1;
+        }
+    }
+    if (g && (!(g->key == graph_key(h, scene->B, scene->V, scene->h, scene->w, workspace)) || !h->derived_valid))
+        return fail(PARQ_ERR_STATE, "parq_forward_views: the graph was recorded for another shape / workspace / weight arena / range mirror or under "
+                                    "other attention settings (mode, head tiers, seam fusion, batch invariance) or token type: capture again");
+    const bool all = n_views == V;
+    if (!all) {
+        // the views that are not listed are read from the cache as it stands: it must have been built whole in the handle's present state
+        const auto it = h->cache_recs.find(workspace);
+        if (it == h->cache_recs.end())
+            return fail(PARQ_ERR_STATE, "parq_forward_views: no record of a whole K/V cache in this workspace (never filled, or rewritten by parq_prepare / "
+                                        "parq_forward_train / a view-sharded iteration / a re-pack since): list all %d views", V);
+        const CacheRec& r = it->second;
+        const char* what = nullptr;
+        if (r.B != scene->B || r.V != scene->V || r.h != scene->h || r.w != scene->w) what = "shape";
+        else if (r.mode != h->attn_mode) what = "attention mode";
+        else if (r.safe != h->safe_heads()) what = "head-tier mask";
+        else if (r.tok != h->tok_type) what = "token type";
+        else if (r.arena != h->arena || r.pack_gen != h->pack_gen) what = "packed weight arena";
+        else if (r.inv != (h->batch_invariant ? 1 : 0)) what = "batch-invariant flag";
+        else if (r.mirror != h->range_mirror) what = "range mirror word";      // (only the handle's present word is ever read below)
+        if (what) return fail(PARQ_ERR_STATE, "parq_forward_views: the K/V cache in this workspace was built under another %s: list all %d views", what, V);
+        if (h->range_mirror && __atomic_load_n(h->range_mirror, __ATOMIC_ACQUIRE) != 0)
+            return fail(PARQ_ERR_STATE, "parq_forward_views: a range / too-peaked flag is raised in the mirror word of the forward that built this cache: "
+                                        "list all %d views, so that the flag is raised again rather than lost with the rows that are skipped", V);
+    }
+    RowRuns runs;
+    int64_t rows = N;
+    if (!all) {
+        if (h->cache_mode()) {
+            runs = view_row_runs(list, hw, N, kvproj_granule(h, scene->B, N));
+            rows = 0;
+            for (const auto& r : runs) rows += r.second - r.first;
+        } else {
+            // attention mode 0 has no cache layout to address by key: one fp32 GEMM over all rows, or none
+            if (n_views > 0) runs.emplace_back(0, (int)N);
+            rows = n_views > 0 ? N : 0;
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    h->map_recs.erase(workspace);
+    h->cache_recs.erase(workspace);
+    rc = do_prepare(h, scene, (float*)workspace, ws, s, false, g ? outs : nullptr, true, all ? nullptr : &runs);
+    if (rc) return rc;
+    if (g) {
+        HIPCHK(hipGraphLaunch(g->exec, s));
+        h->ref_state = 0;
+        h->prepared = false;
+    } else {
+        rc = forward_iterations(h, scene, (float*)workspace, ws, outs, s, false);
+        if (rc) return rc;
+    }
+    h->note_iteration(workspace, scene, h->I - 1, 1);
+    h->note_cache(workspace, scene);
+    if (rows_projected) *rows_projected = rows;
     return PARQ_OK;
 }
 
@@ -1860,6 +1998,7 @@ int parq_forward_train(parq_handle h, const parq_scene* scene, void* workspace, 
     float* wsp = (float*)workspace;
     hipStream_t s = (hipStream_t)stream;
     h->note_iteration(workspace, scene, h->I - 1, 2);     // (before anything is enqueued: whatever an inference forward left here is gone)
+    h->cache_recs.erase(workspace);
     rc = do_prepare(h, scene, wsp, ws, s, true);
     if (rc) return rc;
     const int64_t M = (int64_t)scene->B * h->Q;

@@ -560,7 +560,8 @@ int flash_split_pick_splits(int B, int H, int Lq, int Lk, int num_cus);
 size_t kvproj_big_scratch_floats(int B, int N, int C);
 hipError_t launch_kvproj_big(const void* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N, int C,
                              void* cache, int* overflow, float* scratch, hipStream_t s, int terms = 3, int kind = kF16,
-                             int tok_type = kTokF32);      // tok_type: element type of `tokens` (kTokF32 / kTokF16 / kTokBF16)
+                             int tok_type = kTokF32,       // tok_type: element type of `tokens` (kTokF32 / kTokF16 / kTokBF16)
+                             int row0 = 0, int row_end = -1);   // token rows [row0, row_end) of every scene (row_end < 0: all); multiples of 32 or N
 // flash_split256.hip: the same for head dim 256 (a head = 4 virtual heads of 64 in the cache; wave pairs split the head dim)
 int flash_split256_pick_splits(int B, int H, int Lq, int Lk, int num_cus);
 hipError_t launch_flash_split256(const FlashArgs& a, const void* cache, hipStream_t s, int terms = 3, int kind = kF16);
@@ -618,7 +619,8 @@ inline int64_t setloss_part_floats(int64_t P, int64_t rows) { return 3 * ((P + 2
 // every (scene, head) region of the cache then spans ceil(N / 32) * 16 KB (the split layout's size)
 hipError_t launch_kvproj_split(const void* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N,
                                int C, int H, void* cache, int* overflow, hipStream_t s, int terms = 3, int kind = kF16, unsigned safe_mask = 0,
-                               int tok_type = kTokF32);
+                               int tok_type = kTokF32, int row0 = 0, int row_end = -1);      // rows [row0, row_end) of every scene (row_end < 0: all)
+int kvproj_split_granule(int C);      // what row0 / row_end of launch_kvproj_split are multiples of (row_end may also be N)
 // fp32 -> 16-bit (round to nearest) weights of the single-term modes
 hipError_t launch_cvt16(const float* src, void* dst, int64_t n, int kind, hipStream_t s);
 // 16-bit tokens (tok_type kTokF16 / kTokBF16) -> fp32, exact: the fp32 K/V projection of attention mode 0 reads the widened copy

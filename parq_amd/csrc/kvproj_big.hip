@@ -32,14 +32,17 @@ struct BigArgs {
     _Float16* cache;                                // [B][C/64 heads][nblk][16 KB]
     int* overflow;
     int N, C, VH;                                   // VH = C / 64 virtual heads
+    int row0, row_end;                              // token rows of every scene this launch projects: [row0, row_end), row0 a multiple of 32 (a cache block)
 };
 
 // 8 tokens -> hi/lo fp16, streaming (the pre-pass); TT: element type of the tokens, 16-bit ones widened to fp32 first (exact)
 template <int TT>
 __global__ __launch_bounds__(256) void split_tokens_kernel(const void* __restrict__ x, _Float16* __restrict__ hi, _Float16* __restrict__ lo,
-                                                           int64_t n8, int* __restrict__ overflow) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+                                                           int64_t n8, int* __restrict__ overflow, int64_t scene8, int64_t off8) {
+    // blockIdx.y = scene of a row-range launch: its pieces start at scene8 * y + off8 (the whole batch: one y, both 0)
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n8) return;
+    i += (int64_t)blockIdx.y * scene8 + off8;
     float v[8];
     if constexpr (TT == kTokF32) {
         const float4 a = reinterpret_cast<const float4*>(x)[2 * i], b = reinterpret_cast<const float4*>(x)[2 * i + 1];
@@ -75,7 +78,7 @@ __global__ __launch_bounds__(512) void kvproj_big_kernel(BigArgs a) {
     const int wr = wave >> 1, wc = wave & 1;
     const int C = a.C;
     const int nct = 2 * C / kTN;
-    const int nrt = (a.N + kTM - 1) / kTM;
+    const int nrt = (a.row_end - a.row0 + kTM - 1) / kTM;       // row tiles per scene (of the launch's row range)
     const int b = blockIdx.y;
     int rtile, ctile;
     {   // the column tiles of one token tile get workgroup ids that are equal mod 8 (same XCD: tokens re-read from its L2)
@@ -85,7 +88,7 @@ __global__ __launch_bounds__(512) void kvproj_big_kernel(BigArgs a) {
         ctile = r >> 3;
     }
     if (rtile >= nrt) return;
-    const int m0 = rtile * kTM, n0 = ctile * kTN;
+    const int m0 = a.row0 + rtile * kTM, n0 = ctile * kTN;
     const int nk = C / kTK;
 
     // ---- LDS-DMA of one k-step: 8 instructions per thread, piece p = i * 512 + tid of the 4096 16-byte pieces of the stage
@@ -101,7 +104,8 @@ __global__ __launch_bounds__(512) void kvproj_big_kernel(BigArgs a) {
         const bool lo = TERMS == 3 && (img & 1);
         if (isA) {
             int tok = m0 + row;
-            tok = tok < a.N ? tok : a.N - 1;                    // rows past the scene: any finite data (their cache entries are masked keys)
+            tok = tok < a.row_end ? tok : a.row_end - 1;        // rows past the range (the scene's end, or a clean neighbour's rows, which are not
+                                                                // stored): any finite data of this launch's own pre-pass
             srcs[i] = (lo ? a.Xlo : a.Xhi) + ((int64_t)b * a.N + tok) * C + chunk * 8;
         } else {
             srcs[i] = (lo ? a.Wlo : a.Whi) + (int64_t)(n0 + row) * C + chunk * 8;
@@ -240,7 +244,7 @@ __global__ __launch_bounds__(512) void kvproj_big_kernel(BigArgs a) {
             __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0): same-wave LDS round trip
             __builtin_amdgcn_wave_barrier();
             const int blk = (m0 + wr * 64 + t * 32) >> 5;
-            if (blk < nblk) {                                   // wave-uniform
+            if (blk < nblk && blk * 32 < a.row_end) {           // wave-uniform (blocks behind the range: a clean neighbour's, left alone)
                 const int hv = isK ? headcol : headcol - a.VH;
                 _Float16* gout = a.cache + (((int64_t)b * a.VH + hv) * nblk + blk) * kBlkH + (isK ? 0 : kBlkH / 2);
                 const uint4* src = reinterpret_cast<const uint4*>(wl);
@@ -268,7 +272,7 @@ static hipError_t launch_big_t(const BigArgs& a, int B, hipStream_t s) {
     static DynLdsOnce once;
     const size_t ldsb = (size_t)2 * (TERMS == 3 ? 4 : 2) * kImg * sizeof(_Float16);              // 128 KB (64 KB single-term); >= the 64 KB of epilogue scratch
     if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&kvproj_big_kernel<TERMS, KIND>), ldsb); e != hipSuccess) return e;
-    const int nct = 2 * a.C / kTN, nrt = ceil_div(a.N, kTM);
+    const int nct = 2 * a.C / kTN, nrt = ceil_div(a.row_end - a.row0, kTM);
     dim3 grid(ceil_div(nrt, 8) * 8 * nct, B, 1);
     hipLaunchKernelGGL((kvproj_big_kernel<TERMS, KIND>), grid, dim3(512), ldsb, s, a);
     return hipGetLastError();
@@ -276,8 +280,12 @@ static hipError_t launch_big_t(const BigArgs& a, int B, hipStream_t s) {
 
 // terms = 3: Whi / Wlo are the hi / lo planes of W_kv; terms = 1: Whi holds W_kv rounded to `kind`, Wlo is unused
 hipError_t launch_kvproj_big(const void* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N, int C,
-                             void* cache, int* overflow, float* scratch, hipStream_t s, int terms, int kind, int tok_type) {
+                             void* cache, int* overflow, float* scratch, hipStream_t s, int terms, int kind, int tok_type,
+                             int row0, int row_end) {
     if (!kvproj_big_scratch_floats(B, N, C) || !scratch || B > 65535) return hipErrorInvalidValue;
+    if (row_end < 0) row_end = N;
+    if (row0 < 0 || row0 >= row_end || row_end > N || row0 % 32 != 0 || (row_end % 32 != 0 && row_end != N)) return hipErrorInvalidValue;
+    const bool part = row0 != 0 || row_end != N;     // a row range: the pre-pass converts those rows of every scene only
     if (tok_type != kTokF32 && tok_type != kTokF16 && tok_type != kTokBF16) return hipErrorInvalidValue;
     const int64_t n = (int64_t)B * N * C;
     _Float16* xhi = reinterpret_cast<_Float16*>(scratch);
@@ -285,12 +293,28 @@ hipError_t launch_kvproj_big(const void* tokens, const void* Whi, const void* Wl
     BigArgs a;
     a.Xhi = xhi; a.Xlo = xlo; a.Whi = reinterpret_cast<const _Float16*>(Whi); a.Wlo = reinterpret_cast<const _Float16*>(Wlo);
     a.bias = bias; a.cache = reinterpret_cast<_Float16*>(cache); a.overflow = overflow; a.N = N; a.C = C; a.VH = C / 64;
+    a.row0 = row0; a.row_end = row_end;
+    const int64_t scene8 = (int64_t)N * C / 8, off8 = (int64_t)row0 * C / 8, part8 = (int64_t)(row_end - row0) * C / 8;      // C % 128 == 0
     if (terms == 3) {
-        const dim3 grid((unsigned)ceil_div64(n / 8, 256));
-        if (tok_type == kTokF16) hipLaunchKernelGGL(split_tokens_kernel<kTokF16>, grid, dim3(256), 0, s, tokens, xhi, xlo, n / 8, overflow);
-        else if (tok_type == kTokBF16) hipLaunchKernelGGL(split_tokens_kernel<kTokBF16>, grid, dim3(256), 0, s, tokens, xhi, xlo, n / 8, overflow);
-        else hipLaunchKernelGGL(split_tokens_kernel<kTokF32>, grid, dim3(256), 0, s, tokens, xhi, xlo, n / 8, overflow);
+        const int64_t n8 = part ? part8 : n / 8;
+        const dim3 grid((unsigned)ceil_div64(n8, 256), part ? B : 1, 1);
+        const int64_t sc8 = part ? scene8 : 0, o8 = part ? off8 : 0;
+        if (tok_type == kTokF16) hipLaunchKernelGGL(split_tokens_kernel<kTokF16>, grid, dim3(256), 0, s, tokens, xhi, xlo, n8, overflow, sc8, o8);
+        else if (tok_type == kTokBF16) hipLaunchKernelGGL(split_tokens_kernel<kTokBF16>, grid, dim3(256), 0, s, tokens, xhi, xlo, n8, overflow, sc8, o8);
+        else hipLaunchKernelGGL(split_tokens_kernel<kTokF32>, grid, dim3(256), 0, s, tokens, xhi, xlo, n8, overflow, sc8, o8);
         return launch_big_t<3, kF16>(a, B, s);
+    }
+    if (part) {          // the single-term modes' rounding pass is a flat one: one launch per scene for its rows
+        const int64_t tb = tok_type == kTokF32 ? 4 : 2;
+        for (int b = 0; b < B; ++b) {
+            const int64_t o = ((int64_t)b * N + row0) * C, cnt = (int64_t)(row_end - row0) * C;
+            const char* src = reinterpret_cast<const char*>(tokens) + o * tb;
+            if (hipError_t e = tok_type == kTokF32 ? launch_cvt16(reinterpret_cast<const float*>(src), xhi + o, cnt, kind, s)
+                                                   : launch_cvt16_tokens(src, xhi + o, cnt, kind, tok_type, s);
+                e != hipSuccess)
+                return e;
+        }
+        return kind == kF16 ? launch_big_t<1, kF16>(a, B, s) : launch_big_t<1, kBF16>(a, B, s);
     }
     if (hipError_t e = tok_type == kTokF32 ? launch_cvt16(reinterpret_cast<const float*>(tokens), xhi, n, kind, s)
                                            : launch_cvt16_tokens(tokens, xhi, n, kind, tok_type, s);

@@ -35,8 +35,11 @@ struct KvProjArgs {
     int* overflow;
     int N, C, H;
     // TERMS == 11 (attention mode 4 with per-head tiers): bit h set = head h is written in the split layout (fp16 x 3 kernel), clear =
-    // as mode-4 stages; every (scene, head) region then spans head_bytes (the split layout's size)
-    unsigned safe_mask; int64_t head_bytes;
+    // as mode-4 stages; every (scene, head) region then spans the split layout's size, ceil(N / 32) blocks of 16 KB
+    unsigned safe_mask;
+    // the token rows of every scene this launch projects: [row0, row_end), row0 a multiple of the kernel's row tile (and of the 64-key
+    // stage where the cache has stages), row_end <= N.  [0, N) = everything; N stays the scene's N for clamps and cache addressing
+    int row0, row_end;
 };
 
 template <int TT>
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(kThreads) void kvproj_split_kernel(KvProjArgs a) {
     // nct column tiles that share one 128-token A tile get ids that are equal mod 8 and at most 8*nct apart,
     // so the A tile is fetched from HBM once and re-read from that XCD's L2.
     const int nct = 2 * a.C / kBN;                 // column tiles
-    const int nrt = (a.N + kBM - 1) / kBM;         // row tiles per scene
+    const int nrt = (a.row_end - a.row0 + kBM - 1) / kBM;      // row tiles per scene (of the launch's row range)
     const int b = blockIdx.y;
     int rtile, ctile;
     {
@@ -66,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void kvproj_split_kernel(KvProjArgs a) {
         ctile = r >> 3;
     }
     if (rtile >= nrt) return;                      // padding of the last group (uniform per workgroup)
-    const int m0 = rtile * kBM;                    // first token of the tile within scene b
+    const int m0 = a.row0 + rtile * kBM;           // first token of the tile within scene b
     const int n0 = ctile * kBN;                    // first output column
     const int C = a.C;
     const int nk = C / kBK;
@@ -312,7 +315,7 @@ constexpr int kKvStampSteps = 96, kKvStampPts = 8, kKvStampBytes = 2 * kKvStampS
 // every request is still a whole kilobyte and every row piece a whole 128-byte line — and are widened to fp32 (exactly) at the
 // conversion; from there on the arithmetic is the fp32-token kernel's.
 template <int TM, int TERMS, int KIND, int NK, int D, int PROBE = 0, int TT = kTokF32>
-__global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int total_rt, int nrt, int P) {
+__global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int total_rt, int nrt, int P, int rt0) {      // rt0: first row tile of the launch's row range
     PARQ_TL_KERNEL(kTlKvProj);
     constexpr int NWV = 8;
     constexpr bool SPLIT = TERMS != 1;         // three-term products (TERMS = 3, and 8: the same GEMM with the mode-4 epilogue;
@@ -373,7 +376,7 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
     auto dma = [&](int q) {
         const int qq = q < last_step ? q : last_step;
         const int tile = p + (qq / NK) * P, ks = qq % NK;
-        const int b = tile / nrt, m0 = (tile - b * nrt) * TM;
+        const int b = tile / nrt, m0 = (tile - b * nrt + rt0) * TM;
         const char* Xb = reinterpret_cast<const char*>(a.X) + (((int64_t)b * a.N) * C + ks * kBK) * kTB;
         lds_byte* dst = (lds_byte*)(ldsb) + (q % D) * kRawBytes;
         if constexpr (PROBE & 8) return;
@@ -440,10 +443,9 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
             }
         }
     };
-    auto tile_m0 = [&](int tile) {
-        const int t = tile < total_rt ? tile : total_rt - 1;
+    auto tile_m0 = [&](int t) {
         const int b = t / nrt;
-        return (t - b * nrt) * TM;
+        return (t - b * nrt + rt0) * TM;
     };
 
     auto run = [&](auto isk_tag, auto f8_tag) __attribute__((always_inline)) {
@@ -478,9 +480,9 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
         convert(0, tile_m0(p));
         int step = 0;
         bool first = true;
-        for (int tile = p; tile < total_rt; tile += P) {
-            const int b = tile / nrt, m0 = (tile - b * nrt) * TM;
-            const int m0_next = tile_m0(tile + P);
+        for (int tile = p; step <= last_step; tile += P) {      // (total_rt is not needed past my_tiles: one scalar register less to keep)
+            const int b = tile / nrt, m0 = (tile - b * nrt + rt0) * TM;
+            const int m0_next = step + NK <= last_step ? tile_m0(tile + P) : m0;      // behind the last tile: converted, never multiplied
             f32x16 acc[RT];
 #pragma unroll
             for (int i = 0; i < RT; ++i)
@@ -561,7 +563,7 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
                     // mode-4 stage image (flash_split8.hip): this block's fp16 plane at t * 4 KB of the K / V 16-bit region; K lanes also
                     // store their 16 accumulator registers as ONE 16-byte piece of the hi8 plane and one of the lo8 plane
                     unsigned char* stage = reinterpret_cast<unsigned char*>(a.cache) +
-                                           (MIX ? ((int64_t)b * a.H + h) * a.head_bytes + (int64_t)(m0 >> 6) * kStage8Bytes
+                                           (MIX ? ((int64_t)b * a.H + h) * ((int64_t)nblk * (2 * kBlkHalfs)) + (int64_t)(m0 >> 6) * kStage8Bytes
                                                 : (((int64_t)b * a.H + h) * (nblk >> 1) + (m0 >> 6)) * kStage8Bytes);
                     out = reinterpret_cast<_Float16*>(stage + (ISK ? kS8Kh16 : kS8Vh16 - 2 * kVoff) + t * 4096);
                     if constexpr (ISK) {
@@ -698,13 +700,13 @@ static hipError_t launch_dma_nk(const KvProjArgs& a, int B, hipStream_t s) {
     const size_t lds = (size_t)D * TM * kBK * tok_bytes<TT>() + (size_t)2 * 2 * TM * kBK * sizeof(_Float16) + 8 * 2048;
 #endif
     if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&kvproj_dma_kernel<TM, TERMS, KIND, NK, D, PROBE, TT>), lds); e != hipSuccess) return e;
-    const int nslice = 2 * a.C / 256, nrt = ceil_div(a.N, TM);
+    const int nslice = 2 * a.C / 256, nrt = ceil_div(a.row_end - a.row0, TM);
     const int total_rt = B * nrt;
     int P = device_num_cus() / nslice;
     if (P < 1) P = 1;
     if (P > total_rt) P = total_rt;
     dim3 grid(ceil_div(P, 8) * 8 * nslice, 1, 1);
-    hipLaunchKernelGGL((kvproj_dma_kernel<TM, TERMS, KIND, NK, D, PROBE, TT>), grid, dim3(512), lds, s, a, total_rt, nrt, P);
+    hipLaunchKernelGGL((kvproj_dma_kernel<TM, TERMS, KIND, NK, D, PROBE, TT>), grid, dim3(512), lds, s, a, total_rt, nrt, P, a.row0 / TM);
     return hipGetLastError();
 }
 
@@ -792,17 +794,28 @@ hipError_t launch_split_f32(const float* src, void* hi, void* lo, int64_t n, hip
     return hipGetLastError();
 }
 
+// rows a row range of launch_kvproj_split is aligned to: the row tile of the kernel that runs dim C (64: the persistent kernel, whose
+// tile is also one stage of the mode-4 cache; 128: the tiled kernel)
+int kvproj_split_granule(int C) { return (C <= 4 * kBK && C % (2 * kBK) == 0) ? 64 : kBM; }
+
 // tokens [B][N][C] -> split cache; Whi/Wlo [2C][C] fp16, bias [2C] fp32.  Needs C % 64 == 0, head dim 64.
+// [row0, row_end): the token rows of every scene to project (row_end < 0: all N), aligned as kvproj_split_granule says; a row's cache
+// image does not depend on the range it is projected in (a tile's rows are independent dot products over the same k order).
 hipError_t launch_kvproj_split(const void* tokens, const void* Whi, const void* Wlo, const float* bias, int B, int N,
-                               int C, int H, void* cache, int* overflow, hipStream_t s, int terms, int kind, unsigned safe_mask, int tok_type) {
+                               int C, int H, void* cache, int* overflow, hipStream_t s, int terms, int kind, unsigned safe_mask, int tok_type,
+                               int row0, int row_end) {
+    if (row_end < 0) row_end = N;
+    const int gran = kvproj_split_granule(C);
+    if (row0 < 0 || row0 >= row_end || row_end > N || row0 % gran != 0 || (row_end % gran != 0 && row_end != N)) return hipErrorInvalidValue;
     if (C % kBK != 0 || C != H * 64 || (2 * C) % kBN != 0) return hipErrorInvalidValue;
     if (tok_type != kTokF32 && tok_type != kTokF16 && tok_type != kTokBF16) return hipErrorInvalidValue;
     const size_t ldsb = (size_t)(2 * kBM * kBK + 2 * kBN * kBK) * sizeof(_Float16);      // 64 KB
     KvProjArgs a;
     a.X = tokens; a.Whi = reinterpret_cast<const _Float16*>(Whi); a.Wlo = reinterpret_cast<const _Float16*>(Wlo);
     a.bias = bias; a.cache = reinterpret_cast<_Float16*>(cache); a.overflow = overflow; a.N = N; a.C = C; a.H = H;
-    a.safe_mask = safe_mask; a.head_bytes = (int64_t)ceil_div(N, 32) * 16384;
-    const int nct = 2 * C / kBN, nrt = ceil_div(N, kBM);
+    a.safe_mask = safe_mask;
+    a.row0 = row0; a.row_end = row_end;
+    const int nct = 2 * C / kBN, nrt = ceil_div(row_end - row0, kBM);
     if (C <= 4 * kBK && C % (2 * kBK) == 0) {
         // W-stationary persistent kernel: one workgroup per CU, the column slices of one slot on one XCD
         if (tok_type == kTokF16) return launch_dma_tok16<kTokF16>(a, B, N, C, terms, kind, s);

@@ -229,10 +229,12 @@ class _Run:
     """One enqueued inference forward as its range check must see it: the workspace, mirror slot and epoch it ran with and the
     arithmetic settings (attention mode, head tiers, seam fusion, batch invariance) it was enqueued under.  A deferred check (InFlight) runs after
     other forwards may have re-used the workspace's fields or switched the module to safer arithmetic: it reads this, not them."""
-    __slots__ = ("entry", "slot", "epoch", "settings")
+    __slots__ = ("entry", "slot", "epoch", "settings", "rows", "views")
 
     def __init__(self, entry, slot, epoch, settings):
         self.entry, self.slot, self.epoch, self.settings = entry, slot, epoch, settings
+        self.rows = None              # a view window's forward: token rows per scene its K/V projection covered (parq_forward_views)
+        self.views = None             # ... and the view slots it listed
 
 
 class _WsCache(dict):
@@ -525,6 +527,7 @@ class PARQDecoder(_Tracked, nn.Module):
 
     def _free_slot(self):
         used = {e.slot for e in self._ws.values()} | set(self._pending)     # (a dropped workspace's forward may still await its check)
+        used |= {w._slot for w in self.__dict__.get("_windows", ())}         # view windows own a word each, outside the workspace cache
         for sl in range(1, self._MIRROR_SLOTS):
             if sl not in used:
                 return sl
@@ -540,7 +543,12 @@ class PARQDecoder(_Tracked, nn.Module):
         v = 0
         for sl in np.nonzero(self._mirror_np[:self._MIRROR_SLOTS])[0].tolist():
             if sl not in self._pending:
-                v |= self._mirror_take(sl)
+                t = self._mirror_take(sl)
+                v |= t
+                if t:                                   # a view window's word: its cache holds the flagged forward's rows, whoever polls
+                    for w in self.__dict__.get("_windows", ()):
+                        if w._slot == sl:
+                            w.invalidate()
         if v == 0 or self.range_check == "off":
             return
         if v & 4:
@@ -975,6 +983,14 @@ class PARQDecoder(_Tracked, nn.Module):
         with torch.no_grad():
             return self._forward_inference(intput_tokens, camera, T_camera_pseudoCam, T_world_pseudoCam, T_world_local, feat_hw)
 
+    def view_window(self, B, V, h, w, T_world_local, dtype=torch.float32):
+        """A streaming window of V view slots for video inference (parq_amd.ViewWindow, INTEGRATION.md "Streaming a window of
+        views"): ``put`` replaces the tokens, camera and poses of some slots, ``forward`` re-projects K / V of those slots only and
+        returns what ``forward`` returns on the assembled inputs, bit for bit.  The window lives in ONE local frame (`T_world_local`:
+        the tokens' ray positional encoding is expressed in it); ``rebase`` starts a new one."""
+        from .view_window import ViewWindow
+        return ViewWindow(self, B, V, h, w, T_world_local, dtype)
+
     def _needs_graph(self, tokens):
         t = raw(tokens)
         return bool(getattr(t, "requires_grad", False)) or any(p.requires_grad for p in self.parameters())
@@ -1060,15 +1076,18 @@ class PARQDecoder(_Tracked, nn.Module):
             off += rows * wd
         return _lib.ParqOutputs(*ptrs)
 
-    def _enqueue_forward(self, sc, keep, flat, dev):
+    def _enqueue_forward(self, sc, keep, flat, dev, entry=None, views=None):
         """One inference forward into `flat` (the six output tensors back to back).  From the second forward of a (workspace, weights,
         attention settings) on, the iterations are replayed from a captured graph behind the directly launched prologue and K/V
-        projection (parq_forward_replay); launch by launch otherwise (parq_forward).  Returns its _Run."""
+        projection (parq_forward_replay); launch by launch otherwise (parq_forward).  Returns its _Run.
+        `entry`, `views` (parq_amd.ViewWindow): run in that workspace entry — one the window owns, outside the ``max_workspaces`` cache —
+        with the K/V projection restricted to those view slots (parq_forward_views, with the graph or without)."""
         lib = _lib.load()
         h = self._handle()
         tt = TOKEN_TYPES[keep[0].dtype]
         self._token_type(h, tt)                             # (before the workspace is sized: mode "fp32" carves a widened copy)
-        entry = self._workspace_entry(sc.B, sc.V, sc.h, sc.w, dev, handle=h, tok=self._ws_token_key(tt))
+        if entry is None:
+            entry = self._workspace_entry(sc.B, sc.V, sc.h, sc.w, dev, handle=h, tok=self._ws_token_key(tt))
         ws = entry.ws
         self._set_mirror(entry.slot)
         self._epoch = (self._epoch % 0x7ffffff0) + 1
@@ -1084,7 +1103,20 @@ class PARQDecoder(_Tracked, nn.Module):
             if graph is None and entry.last_key == key:
                 graph = self._capture(entry, key, sc, stream)
             entry.last_key = key
-        if graph is not None:
+        if views is not None:
+            rows = C.c_int64(0)
+            call = lambda vs: lib.parq_forward_views(h, graph, C.byref(sc), _lib.ptr(ws), ws.numel() * 4, C.byref(po),
+                                                     (C.c_int32 * max(1, len(vs)))(*vs), len(vs), C.byref(rows), stream)
+            rc = call(views)
+            if rc == 3 and len(views) < sc.V:
+                # PARQ_ERR_STATE, nothing enqueued: the library's record of this cache is gone or differs, or the mirror word rose since
+                # the window looked at it (the device raises it when the flagged forward ends) — the same forward with every view listed
+                views = list(range(sc.V))
+                rc = call(views)
+            _lib.check(rc, "parq_forward_views")
+            entry.replays += graph is not None
+            run.rows, run.views = int(rows.value), list(views)
+        elif graph is not None:
             _lib.check(lib.parq_forward_replay(h, graph, C.byref(sc), _lib.ptr(ws), ws.numel() * 4, C.byref(po), stream), "parq_forward_replay")
             entry.replays += 1
         else:
@@ -1430,6 +1462,7 @@ class PARQDecoder(_Tracked, nn.Module):
         last, key = self.__dict__.setdefault("_map_last", {}), (dev.index, _raw_stream(dev))
         last.pop(key, None)
         last[key] = kind                                   # (re-)insert as the most recent
+        self.__dict__["_map_window"] = None                # (a view window's forward sets it behind this note: ViewWindow._enqueue)
         while len(last) > 64:
             last.pop(next(iter(last)))
 
@@ -1441,7 +1474,10 @@ class PARQDecoder(_Tracked, nn.Module):
             raise ValueError("cross-attention maps come as torch.float32 or torch.float16, not %s" % (dtype,))
         hd = self._handle()                                # first: a pending mode change drops the cached workspaces
         found = None
-        for k in reversed(list(self._ws)):                 # most recently used first; the one this stream's forwards ran in
+        mw = self.__dict__.get("_map_window")              # the last inference forward was a view window's: its own workspace entry
+        if mw is not None and _raw_stream(torch.device("cuda", mw[0][4])) == mw[0][5]:
+            found = (mw[0], mw[1], torch.device("cuda", mw[0][4]))
+        for k in reversed(list(self._ws) if found is None else []):      # most recently used first; the one this stream's forwards ran in
             dev = torch.device("cuda", k[4])
             if _raw_stream(dev) == k[5]:
                 found = (k, self._ws[k], dev)

@@ -58,6 +58,13 @@ class PARQ(_Base):
     def batch_invariant(self, on):
         self.box3d_decoder.batch_invariant = bool(on)
 
+    def view_window(self, B, V, h, w, T_world_local):
+        """A streaming window of V view slots (parq_amd.ViewWindow) that also encodes: ``win.put_features(slot, features or
+        (levels, layer), camera, T_camera_pseudoCam, T_world_pseudoCam)`` tokenises the put views only, with the window's
+        ``T_world_local`` and in ``token_dtype``; ``win.forward()`` equals ``forward(batch)[1]`` on the assembled batch."""
+        from .view_window import FeatureViewWindow
+        return FeatureViewWindow(self, B, V, h, w, T_world_local)
+
     def set_data_parallel(self, on=True):
         """One process per GPU, scenes sharded (train.py:103-108 runs DDP): with ``on`` every trainable tensor of the module —
         the decoder's flat gradient arena and the ray-PE encoder's four tensors — is averaged over the default process group
