@@ -535,7 +535,9 @@ int parq_ray_pe_backward_flags(const float *camera, const float *T_camera_pseudo
  * From the LAST iteration's outputs: obbs_out (B,Q,19) = [-s/2, s/2 per axis | R(ortho6d) centre | arg-max class],
  * mask_out (B,Q) bytes = NMS keep mask AND validity window (centre x in (ts[0], ts[1]), z in (ts[4], ts[5]); all valid when
  * for_vis).  NMS on the axis-aligned bounds of the boxes, background class (num_classes - 1) excluded: IoU > 0.1
- * class-agnostic, or IoU > 0.2 within a class when for_vis. */
+ * class-agnostic, or IoU > 0.2 within a class when for_vis (float64 IoU against the doubles 0.1 / 0.2).  Boxes are visited by
+ * descending score, equal scores from the higher index down; a NaN score is visited before every number (NumPy's argsort order),
+ * so a row that went NaN is picked, suppresses nothing, and leaves the other queries' bits as they would be without it. */
 int parq_parse_pred(const float *center, const float *size, const float *ortho6d, const float *sem_cls_prob, int32_t B,
                     int32_t Q, int32_t num_classes, const float *track_scale6_host, int32_t for_vis, int32_t enable_nms,
                     float *obbs_out, unsigned char *mask_out, parq_stream stream);

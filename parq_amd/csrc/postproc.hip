@@ -5,8 +5,8 @@
 //   19-vector [-s/2, s/2 per axis | R t | label], axis-aligned bounds of its 8 corners in the local frame, score = max class
 //   probability, label = first arg-max, validity window on the centre (x and z, strict inequalities);
 //   NMS: candidates = non-background boxes, visited by descending score (ties: higher index first, NumPy's order for
-//   argsort(...)[-1] is unspecified there), IoU of the axis-aligned bounds in float64, suppress when IoU (times "same class"
-//   in the visualisation variant) > threshold.
+//   argsort(...)[-1] is unspecified there; a NaN score first, as argsort puts it last), IoU of the axis-aligned bounds in
+//   float64, suppress when IoU (times "same class" in the visualisation variant) > threshold, the double 0.1 / 0.2.
 #include "common.hpp"
 
 namespace parq {
@@ -23,6 +23,16 @@ struct ParseArgs {
     float* obbs;                  // (B, Q, 19)
     unsigned char* mask;          // (B, Q)
 };
+
+// Visit order of the NMS as a total order on (score, index): true when candidate p ranks below candidate q.  A NaN score ranks
+// above every number (np.argsort puts NaN last, so such a box is visited first); equal scores and NaNs rank by index.  Every
+// candidate gets a distinct rank, so order[0 .. n_cand) is fully written whatever the scores are.
+__device__ __forceinline__ bool ranks_below(float sp, int p, float sq, int q) {
+    const bool nan_p = sp != sp, nan_q = sq != sq;
+    if (nan_p != nan_q) return nan_q;
+    if (!nan_p && sp != sq) return sp < sq;
+    return p < q;
+}
 
 __global__ __launch_bounds__(256) void parse_pred_kernel(ParseArgs a) {
     __shared__ float lo[3][kMaxQ], hi[3][kMaxQ], score[kMaxQ];
@@ -85,12 +95,12 @@ __global__ __launch_bounds__(256) void parse_pred_kernel(ParseArgs a) {
         if (!alive[q]) continue;
         int r = 0;
         for (int p = 0; p < Q; ++p)
-            if (alive[p] && (score[p] < score[q] || (score[p] == score[q] && p < q))) ++r;
+            if (alive[p] && ranks_below(score[p], p, score[q], q)) ++r;
         order[r] = q;
         atomicAdd(&n_cand, 1);
     }
     __syncthreads();
-    const float thr = a.for_vis ? 0.2f : 0.1f;
+    const double thr = a.for_vis ? 0.2 : 0.1;                       // the reference compares the float64 IoU with Python doubles
     const int nc = n_cand;
     for (int pos = nc - 1; pos >= 0; --pos) {
         const int i = order[pos];
@@ -107,7 +117,7 @@ __global__ __launch_bounds__(256) void parse_pred_kernel(ParseArgs a) {
                 const double vp = ((double)hi[0][p] - lo[0][p]) * ((double)hi[1][p] - lo[1][p]) * ((double)hi[2][p] - lo[2][p]);
                 double o = inter / (vi + vp - inter);
                 if (a.for_vis && label[i] != label[p]) o = 0.0;      // nms_3d_faster_samecls
-                if (o > (double)thr) alive[p] = 0;
+                if (o > thr) alive[p] = 0;
             }
         }
         __syncthreads();
