@@ -555,6 +555,32 @@ int parq_parse_pred(const float *center, const float *size, const float *ortho6d
 int parq_obb_iou(const double *boxes_a, int64_t n_a_total, const double *boxes_b, int64_t n_b_total, const int64_t *segments,
                  int32_t S, int64_t total_pairs, double *iou3d_out, double *iou2d_out, parq_stream stream);
 
+/* ---- boxes drawn into the normalised input views (utils/parq_utils.py:141-211 draw_detections), three launches ------------------
+ * images (B,T,3,H,W) float32; camera (B,T,6) = [w, h, fx, fy, cx, cy]; T_camera_pseudoCam, T_world_pseudoCam (B,T,12) = [R row-major |
+ * t]; corners_world (B,M,8,3) float32 in Obb3D.bb3corners_object order; labels (B,M) int32; keep (B,M) bytes or NULL (all);
+ * count (B) int32 or NULL (M each); colors (num_classes - 1, 3) float32 on the device.  out (B,3,T*H,W), views stacked vertically:
+ * float32, or with out_uint8 = 1 bytes = truncation of value * 255 (NaN -> 0).
+ * Per view: base = (x - min) / (max - min) over its 3*H*W values, two correctly rounded float32 operations (NaN propagates: one NaN
+ * pixel or a constant view makes the whole base NaN).  Box m of scene b is drawn unless labels[b,m] is the background class
+ * num_classes - 1 or outside [0, num_classes), keep[b,m] == 0, or m >= count[b].  Its corners go through
+ * p_c = R_cp (R_wp^T (p_w - t_wp)) + t_cp and uv = p_c.xy / max(z, 1e-3) * f + c in float64 without contraction, in that order;
+ * a corner is valid when z > 1e-3, 0 <= u <= w - 1 and 0 <= v <= h - 1 (and u, v <= 8191: a camera larger than the largest image);
+ * the 12 edges 01 12 23 03 04 15 26 37 45 56 67 47 are drawn between valid corners truncated to integers, as capsules of half-width
+ * 1 px evaluated in integers (thickness 2; pixel equality with OpenCV's line is NOT claimed).  Boxes are drawn in index order: a pixel
+ * takes the colour colors[labels[b,m]] of the last covering edge of the highest covering box, else base.  No atomics: the output is
+ * a pure function of the inputs.
+ * workspace: parq_draw_boxes_workspace_bytes(B, T, M) bytes (0 for dims this entry refuses), 16-byte aligned; the library allocates
+ * nothing and does not synchronise.  M = 0 is valid (out = base; corners_world, labels, colors may be NULL).  PARQ_ERR_ARG, with
+ * nothing launched: a NULL required pointer, a workspace too small or misaligned, H or W above 8192, B * T above 65535, M above
+ * 2^24, num_classes < 2 with M > 0, out_uint8 other than 0 / 1.
+ * (Parenthesised names: see parq_set_batch_invariant; both are typed in _lib.EXTRA_SYMBOLS.) */
+size_t (parq_draw_boxes_workspace_bytes)(int32_t B, int32_t T, int32_t M);
+int (parq_draw_boxes)(const float *images, const float *camera, const float *T_camera_pseudoCam, const float *T_world_pseudoCam,
+                    const float *corners_world, const int32_t *labels, const unsigned char *keep /*NULL = all*/,
+                    const int32_t *count /*NULL = M each*/, const float *colors /*(num_classes-1, 3)*/, int32_t num_classes,
+                    int32_t B, int32_t T, int32_t H, int32_t W, int32_t M, void *workspace, size_t workspace_bytes,
+                    void *out, int32_t out_uint8, parq_stream stream);
+
 /* ---- set loss for a given matching (model/parq_decoder.py:264-370), three launches --------------------------------------------
  * The reference matches predictions to boxes per (iteration, scene) on the host (utils/matcher.py: scipy LSAP + a capped random
  * neighbourhood) and then evaluates ~100 tiny tensor operations per step, forward and in autograd.  Given the matching, this entry

@@ -6,7 +6,8 @@ Public surface mirrors the reference (ymingxie/PARQ):
     Pose, Camera (utils/wrappers.py:194,441)     tensor wrappers drivers pass in
     InFlight     (no counterpart: the reference calls its model once per batch, eval.py:46)  several forwards of one module in flight
     ViewWindow   (no counterpart: the reference re-projects every view of every snippet)  a streaming window of view slots
-    ResnetFPN    (model/resnet_fpn.py:16)        wrapper of a user-supplied ResNet-FPN; its neck is fused into the tokenisation
+    draw_boxes, box_colors (utils/parq_utils.py:134,141 get_colors / draw_detections)  boxes drawn into the views on the device
+    ResnetFPN    (model/resnet_fpn.py:16)       wrapper of a user-supplied ResNet-FPN; its neck is fused into the tokenisation
 The compute lives in ``parq_amd/_C/libparq_hip.so`` (C ABI: include/parq_hip.h).
 """
 from .wrappers import Camera, Obb3D, Pose, TensorWrapper  # noqa: F401
@@ -32,4 +33,7 @@ def __getattr__(name):
     if name == "ViewWindow":
         from .view_window import ViewWindow
         return ViewWindow
+    if name in ("draw_boxes", "box_colors"):
+        from . import draw
+        return getattr(draw, name)
     raise AttributeError(name)

@@ -136,6 +136,8 @@ EXTRA_SYMBOLS = {
     "parq_set_batch_invariant": (C.c_int, [_vp, _i32]),
     "parq_forward_views": (C.c_int, [_vp, _vp, C.POINTER(ParqScene), _vp, _sz, C.POINTER(ParqOutputs), C.POINTER(_i32), _i32,
                                      C.POINTER(_i64), _vp]),
+    "parq_draw_boxes_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "parq_draw_boxes": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _i32, _vp]),
 }
 
 _lib = None

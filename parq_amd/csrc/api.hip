@@ -2684,6 +2684,36 @@ int parq_obb_iou(const double* boxes_a, int64_t n_a_total, const double* boxes_b
     return PARQ_OK;
 }
 
+size_t parq_draw_boxes_workspace_bytes(int32_t B, int32_t T, int32_t M) {
+    if (B < 1 || T < 1 || M < 0 || M > (1 << 24) || (int64_t)B * T > 65535) return 0;
+    return draw_minmax_bytes(B, T) + (size_t)B * T * M * 12 * 8;
+}
+
+int parq_draw_boxes(const float* images, const float* camera, const float* T_camera_pseudoCam, const float* T_world_pseudoCam,
+                    const float* corners_world, const int32_t* labels, const unsigned char* keep, const int32_t* count, const float* colors,
+                    int32_t num_classes, int32_t B, int32_t T, int32_t H, int32_t W, int32_t M, void* workspace, size_t workspace_bytes,
+                    void* out, int32_t out_uint8, parq_stream stream) {
+    if (B < 1 || T < 1 || H < 1 || W < 1 || M < 0 || M > (1 << 24) || (int64_t)B * T > 65535)
+        return fail(PARQ_ERR_ARG, "parq_draw_boxes: bad dims (B, T, H, W >= 1, 0 <= M <= 2^24, B * T <= 65535)");
+    if (H > 8192 || W > 8192) return fail(PARQ_ERR_ARG, "parq_draw_boxes: H = %d, W = %d; at most 8192 each", H, W);
+    if (!images || !camera || !T_camera_pseudoCam || !T_world_pseudoCam || !workspace || !out)
+        return fail(PARQ_ERR_ARG, "parq_draw_boxes: NULL argument");
+    if (M > 0 && (!corners_world || !labels || !colors)) return fail(PARQ_ERR_ARG, "parq_draw_boxes: NULL boxes, labels or colours with M = %d", M);
+    if (M > 0 && num_classes < 2) return fail(PARQ_ERR_ARG, "parq_draw_boxes: num_classes = %d (the last class is the background)", num_classes);
+    if (out_uint8 != 0 && out_uint8 != 1) return fail(PARQ_ERR_ARG, "parq_draw_boxes: out_uint8 must be 0 or 1");
+    const size_t need = parq_draw_boxes_workspace_bytes(B, T, M);
+    if (workspace_bytes < need) return fail(PARQ_ERR_ARG, "parq_draw_boxes: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 15) return fail(PARQ_ERR_ARG, "parq_draw_boxes: the workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    char* slots = static_cast<char*>(workspace) + draw_minmax_bytes(B, T);
+    HIPCHK(launch_draw_minmax(images, B, T, H, W, workspace, s));
+    if (M > 0)
+        HIPCHK(launch_draw_project(camera, T_camera_pseudoCam, T_world_pseudoCam, corners_world, labels, keep, count, num_classes, B, T, M,
+                                   slots, s));
+    HIPCHK(launch_draw_raster(images, workspace, slots, labels, colors, B, T, H, W, M, out, out_uint8, s));
+    return PARQ_OK;
+}
+
 int parq_set_loss(const float* pred_logits, const float* center_unnormalized, const float* size_unnormalized, const float* ortho6d,
                   int32_t I, int32_t B, int32_t Q, int32_t num_classes, const float* t_center, const float* t_size, const float* t_rot,
                   const int32_t* t_label, const int32_t* t_sym, int32_t nmax, const int32_t* pairs, const float* pair_coef, int32_t P,

@@ -756,6 +756,15 @@ hipError_t launch_parse_pred(const float* center, const float* size, const float
 // obb_iou.hip: the tracker's oriented-box IoU, S segments of (n_a x n_b) pairs in one launch (total >= 1)
 hipError_t launch_obb_iou(const double* boxes_a, const double* boxes_b, const int64_t* seg, int S, int64_t total, int64_t n_a_total,
                           int64_t n_b_total, double* iou3, double* iou2, hipStream_t s);
+// draw.hip: boxes drawn into the normalised views.  Workspace = the min / max parts (draw_minmax_bytes, a multiple of 16 bytes)
+// followed by the (B, T, M, 12) edge slots of 8 bytes each
+size_t draw_minmax_bytes(int B, int T);
+hipError_t launch_draw_minmax(const float* images, int B, int T, int H, int W, void* parts, hipStream_t s);
+hipError_t launch_draw_project(const float* camera, const float* T_cp, const float* T_wp, const float* corners, const int32_t* labels,
+                               const unsigned char* keep, const int32_t* count, int num_classes, int B, int T, int M, void* slots,
+                               hipStream_t s);
+hipError_t launch_draw_raster(const float* images, const void* parts, const void* slots, const int32_t* labels, const float* colors, int B,
+                              int T, int H, int W, int M, void* out, int out_uint8, hipStream_t s);
 hipError_t launch_gemm_split(const float* X, int64_t ldx, const void* Whi, const void* Wlo, const float* bias, float* Y,
                              int64_t ldy, int M, int N, int K, int relu, const float* feat, int hw, hipStream_t s,
                              const float* scale_dev = nullptr, float scale_mul = 1.f, const float* xscale_dev = nullptr,

@@ -311,6 +311,9 @@ class PARQDecoder(_Tracked, nn.Module):
     # device, one parq_obb_iou launch per step and per compute_metrics, instead of the host's pair-by-pair loop; same tracks and
     # metrics (parq_amd/f1_eval.py)
     metrics_on_device = False
+    # True (on the class or on one module): log_images draws the predicted / ground-truth boxes of scene 0 into the RGB views on the
+    # device (parq_amd/draw.py).  False: log_images returns {} and costs nothing, as before the drawing existed.
+    draw_images = False
 
     def __init__(self, cfg):
         super().__init__()
@@ -1662,11 +1665,40 @@ class PARQDecoder(_Tracked, nn.Module):
 
     def log_images(self, out_dict, obbs_padded, Ts_world_pseudoCam, Ts_world_local, T_camera_pseudoCam, rgb_img=None, calib_rgb=None,
                    slaml_img=None, calib_slaml=None, slamr_img=None, calib_slamr=None):
-        """model/parq_decoder.py:470-538 draws predicted / ground-truth boxes into the input images (cv2, utils/parq_utils.py:108-225)
-        for TensorBoard; called from parq_lightning.py:280 (``get_log_images``).  Visualisation is outside this path's scope
-        (SURVEY.md §2): same name, same argument list, an empty dict of images, so that a reference-style driver with image logging
-        switched on keeps running instead of hitting AttributeError."""
-        return {}
+        """model/parq_decoder.py:470-538: predicted / ground-truth boxes drawn into the input images for TensorBoard and the
+        ``FOR_VIS`` demo; called from ``PARQ.get_log_images`` (parq_lightning.py:280).  With ``draw_images`` off (the default) or
+        without ``rgb_img`` this returns ``{}``.  With it on, scene 0 of the RGB stream is drawn on the device (parq_amd/draw.py,
+        whose rule replaces cv2's): ``{"rgb_img": the views normalised per view, "rgb_imgwithbox": + the boxes ``parse_pred`` keeps,
+        "rgb_img_gtwithbox": + the boxes of obbs_padded[0] up to its padding (only when obbs_padded is given)}``, each a float32
+        device tensor ``(3, T*H, W)``; nothing is copied to the host.  The two grey SLAM streams (``slaml_img`` / ``slamr_img`` and
+        their calibrations) are accepted and ignored: ScanNet has none."""
+        if not self.draw_images or rgb_img is None:
+            return {}
+        return self._draw_log_images(out_dict, obbs_padded, Ts_world_pseudoCam, Ts_world_local, T_camera_pseudoCam, rgb_img, calib_rgb,
+                                     torch.float32)
+
+    @torch.no_grad()
+    def _draw_log_images(self, out_dict, obbs_padded, Ts_world_pseudoCam, Ts_world_local, T_camera_pseudoCam, rgb_img, calib_rgb, dtype):
+        """log_images' three overlays of scene 0 in ``dtype`` (float32, or uint8 for PARQ.get_log_images)."""
+        from .draw import draw_boxes
+        from .wrappers import Obb3D, Pose, raw
+        if calib_rgb is None:
+            raise ValueError("log_images: calib_rgb (the cameras of rgb_img) is needed to draw")
+        out = self.parse_pred(out_dict)
+        obbs = out["obbs_pred"]
+        corners = Pose(raw(Ts_world_local)).transform(obbs.T_world_object.transform(obbs.bb3corners_object))
+        img, cam, T_cp, T_wp = (raw(a)[0:1] for a in (rgb_img, calib_rgb, T_camera_pseudoCam, Ts_world_pseudoCam))
+        kw = dict(num_semcls=self.num_semcls, dtype=dtype)
+        none = corners.new_zeros(1, 0, 8, 3), torch.zeros(1, 0, dtype=torch.int32, device=corners.device)
+        images = {"rgb_img": draw_boxes(img, cam, T_cp, T_wp, *none, **kw)[0],
+                  "rgb_imgwithbox": draw_boxes(img, cam, T_cp, T_wp, corners[0:1], raw(obbs)[0:1, :, 18].to(torch.int32),
+                                               keep=out["pred_mask"][0:1], **kw)[0]}
+        if obbs_padded is not None:
+            gt = Obb3D(raw(obbs_padded)[0:1].to(corners.device, torch.float32))
+            count = (~torch.all(raw(gt) == -1, dim=-1)).sum(dim=-1)          # remove_padding's count, left on the device
+            images["rgb_img_gtwithbox"] = draw_boxes(img, cam, T_cp, T_wp, gt.T_world_object.transform(gt.bb3corners_object),
+                                                     raw(gt)[..., 18].to(torch.int32), count=count, **kw)[0]
+        return images
 
     def compute_metrics(self):
         metrics = {}

@@ -100,12 +100,51 @@ class PARQ(_Base):
         return losses, outputs
 
     def validation_step(self, batch, batch_idx):
-        """model/parq_lightning.py:102-112 without the image logging: with ground truth in the batch the scene-level F1
-        trackers are advanced by this snippet batch."""
+        """model/parq_lightning.py:102-112 without the TensorBoard logging: with ground truth in the batch the scene-level F1
+        trackers are advanced by this snippet batch; with ``for_vis`` and ``box3d_decoder.draw_images`` the snippet's overlays
+        are written to ``demo_vis/`` (:110-111)."""
         losses, outputs = self.forward(batch, batch_idx)
         if "obbs_padded" in batch:
             self.box3d_decoder.update_metrics(outputs, batch["obbs_padded"], batch["T_world_local"], batch["scene_name"])
+        if self.for_vis and self.box3d_decoder.draw_images:
+            self.vis_output(batch, outputs, output_name="demo_vis")
         return losses["total_loss"]
+
+    def get_log_images(self, batch, outputs):
+        """model/parq_lightning.py:256-293: tag -> uint8 NumPy ``(3, T*H, W)`` of ``box3d_decoder.log_images``' overlays (scene 0;
+        ``{}`` while ``box3d_decoder.draw_images`` is off or the batch has no ``rgb_img``).  The bytes are the drawing kernel's
+        own ``trunc(value * 255)`` output: one device-to-host copy per tag and no arithmetic on the host."""
+        dec = self.box3d_decoder
+        if not dec.draw_images or batch.get("rgb_img") is None:
+            return {}
+        images = dec._draw_log_images(outputs, batch.get("obbs_padded"), batch["T_world_pseudoCam"], batch["T_world_local"],
+                                      batch["T_camera_pseudoCam"], batch["rgb_img"], batch["camera"], torch.uint8)
+        return {tag: im.cpu().numpy() for tag, im in images.items()}
+
+    @staticmethod
+    def save_log_images(log_ims, directory, name):
+        """Write every ``(3, H, W)`` uint8 array of ``log_ims`` to ``"{directory}/{name}_{tag}.png"`` (the directory is made)
+        and return the paths.  Needs Pillow, imported here and nowhere else."""
+        import os
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise RuntimeError("parq_amd.PARQ.save_log_images writes PNG files through Pillow (PIL), which is not installed; "
+                               "get_log_images still returns the uint8 arrays") from e
+        os.makedirs(directory, exist_ok=True)
+        paths = []
+        for tag, im in log_ims.items():
+            path = os.path.join(directory, "%s_%s.png" % (name, tag))
+            Image.fromarray(im.transpose(1, 2, 0)).save(path)
+            paths.append(path)
+        return paths
+
+    def vis_output(self, batch, outputs, output_name="output"):
+        """model/parq_lightning.py:295-304: the overlays of this snippet as ``{output_name}/{scene}_{snippet id}_{tag}.png``."""
+        log_ims = self.get_log_images(batch, outputs)
+        sid = batch["snippet_id"]
+        sid = sid.reshape(-1)[0].item() if hasattr(sid, "reshape") else sid
+        return self.save_log_images(log_ims, output_name, "%s_%s" % (batch["scene_name"][0], sid))
 
     def on_validation_epoch_start(self):
         self.box3d_decoder.reset_metrics()
