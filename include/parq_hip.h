@@ -581,6 +581,40 @@ int (parq_draw_boxes)(const float *images, const float *camera, const float *T_c
                     int32_t B, int32_t T, int32_t H, int32_t W, int32_t M, void *workspace, size_t workspace_bytes,
                     void *out, int32_t out_uint8, parq_stream stream);
 
+/* ---- raw camera frames resized on the device (datasets/transforms.py:65-100,118-132,177-188 pad_scannet + ResizeImage + ToTensor +
+ * Normalize), one launch -------------------------------------------------------------------------------------------------------------
+ * frames (N, H_in, W_in, 3) bytes, rows contiguous (3 * W_in bytes: in general not 4-byte aligned; any buffer alignment is taken).
+ * A zero border pad = (left, top, right, bottom) is added first (the reference's pad_scannet: (0, 2, 0, 2) for 1296 x 968 frames):
+ * Wp = W_in + left + right, Hp = H_in + top + bottom; the border is never read from memory.  The resize is Pillow's
+ * Image.resize(size, BILINEAR) on 8-bit RGB restated in integers.  Per axis, with padded size `in` and output size `out`, the plan
+ * is computed in float64 without contraction, in this order:
+ *   scale = in / out; fs = max(scale, 1); support = fs; ksize = (int)ceil(support) * 2 + 1; ss = 1.0 / fs;
+ *   for each output index xx:  center = (xx + 0.5) * scale;
+ *     xmin = max((int)(center - support + 0.5), 0);  n = min((int)(center + support + 0.5), in) - xmin;
+ *     w[x] = max(0, 1 - |(x + xmin - center + 0.5) * ss|) for x < n;  ww = w[0] + w[1] + ... in index order;
+ *     k[x] = (int)(0.5 + (w[x] / ww) * 4194304)          (22 fractional bits; the weights are never negative).
+ * Two passes, horizontal first, in 32-bit signed integers, clip8 clamping to 0..255:
+ *   tmp[y][xx][c]  = clip8((2097152 + sum_x k_x[xx][x] * in[y][xmin_x[xx] + x][c]) >> 22)   (rounded to 8 bits: part of the rule)
+ *   res[yy][xx][c] = clip8((2097152 + sum_y k_y[yy][y] * tmp[ymin_y[yy] + y][xx][c]) >> 22)
+ * (an axis with in == out has the identity plan and is run like any other).  out (N, 3, H_out, W_out): bytes res with out_uint8 = 1,
+ * else float32 (float)res / 255.0f, ONE correctly rounded division (a multiplication by the float32 reciprocal differs for 126 of
+ * the 256 values).  No atomics: the output is a pure function of the inputs.
+ * parq_frame_plan writes one axis plan to HOST memory: pure host code, no GPU, no allocation, no environment.  Layout, int32:
+ * [0] = ksize, then per output index 2 + ksize words: xmin, n, k[0 .. ksize) (k[x] = 0 for x >= n); parq_frame_plan_ints gives
+ * the word count 1 + out * (2 + ksize), or 0 for sizes it refuses: a size below 1 or above 8192, or in > 8 * out — the largest
+ * downscale factor is 8 (17 taps; the workload's is 4.05); upscaling is not limited.  parq_frame_plan returns PARQ_ERR_ARG for those
+ * and for a NULL plan (it does not set parq_last_error).
+ * parq_frames_resize reads both plans from DEVICE memory (plan_x for Wp -> W_out, plan_y for Hp -> H_out; a plan that is not
+ * parq_frame_plan's gives other pixels, never an access outside the frames), allocates nothing and does not synchronise.
+ * PARQ_ERR_ARG, with nothing launched: a NULL pointer, N, a size below 1, a negative pad, a side (input, padded or output) above
+ * 8192, Wp > 8 * W_out or Hp > 8 * H_out, N above 65535, out_uint8 other than 0 / 1.
+ * (Parenthesised names: see parq_set_batch_invariant; the three are typed in _lib.EXTRA_SYMBOLS.) */
+size_t (parq_frame_plan_ints)(int32_t in_size, int32_t out_size);
+int (parq_frame_plan)(int32_t in_size, int32_t out_size, int32_t *plan_host);
+int (parq_frames_resize)(const unsigned char *frames, int32_t N, int32_t H_in, int32_t W_in, int32_t pad_left, int32_t pad_top,
+                       int32_t pad_right, int32_t pad_bottom, const int32_t *plan_x, const int32_t *plan_y, int32_t H_out,
+                       int32_t W_out, void *out, int32_t out_uint8, parq_stream stream);
+
 /* ---- set loss for a given matching (model/parq_decoder.py:264-370), three launches --------------------------------------------
  * The reference matches predictions to boxes per (iteration, scene) on the host (utils/matcher.py: scipy LSAP + a capped random
  * neighbourhood) and then evaluates ~100 tiny tensor operations per step, forward and in autograd.  Given the matching, this entry

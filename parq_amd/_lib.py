@@ -138,6 +138,9 @@ EXTRA_SYMBOLS = {
                                      C.POINTER(_i64), _vp]),
     "parq_draw_boxes_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "parq_draw_boxes": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _i32, _vp]),
+    "parq_frame_plan_ints": (_sz, [_i32, _i32]),
+    "parq_frame_plan": (C.c_int, [_i32, _i32, C.POINTER(_i32)]),
+    "parq_frames_resize": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
 }
 
 _lib = None

@@ -2714,6 +2714,20 @@ int parq_draw_boxes(const float* images, const float* camera, const float* T_cam
     return PARQ_OK;
 }
 
+int parq_frames_resize(const unsigned char* frames, int32_t N, int32_t H_in, int32_t W_in, int32_t pad_left, int32_t pad_top, int32_t pad_right,
+                       int32_t pad_bottom, const int32_t* plan_x, const int32_t* plan_y, int32_t H_out, int32_t W_out, void* out,
+                       int32_t out_uint8, parq_stream stream) {
+    if (!frames || !plan_x || !plan_y || !out) return fail(PARQ_ERR_ARG, "parq_frames_resize: NULL argument");
+    if (out_uint8 != 0 && out_uint8 != 1) return fail(PARQ_ERR_ARG, "parq_frames_resize: out_uint8 must be 0 or 1");
+    if (!frames_sizes_ok(N, H_in, W_in, pad_left, pad_top, pad_right, pad_bottom, H_out, W_out))
+        return fail(PARQ_ERR_ARG, "parq_frames_resize: N = %d frames of %d x %d, pad (%d, %d, %d, %d), to %d x %d (W x H): 1 <= N <= 65535, "
+                    "sizes >= 1, pads >= 0, every side (padded too) at most 8192 and at most 8 times the output's",
+                    N, W_in, H_in, pad_left, pad_top, pad_right, pad_bottom, W_out, H_out);
+    HIPCHK(launch_frames_resize(frames, N, H_in, W_in, pad_left, pad_top, pad_right, pad_bottom, plan_x, plan_y, H_out, W_out, out, out_uint8,
+                                (hipStream_t)stream));
+    return PARQ_OK;
+}
+
 int parq_set_loss(const float* pred_logits, const float* center_unnormalized, const float* size_unnormalized, const float* ortho6d,
                   int32_t I, int32_t B, int32_t Q, int32_t num_classes, const float* t_center, const float* t_size, const float* t_rot,
                   const int32_t* t_label, const int32_t* t_sym, int32_t nmax, const int32_t* pairs, const float* pair_coef, int32_t P,

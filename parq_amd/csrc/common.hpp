@@ -765,6 +765,10 @@ hipError_t launch_draw_project(const float* camera, const float* T_cp, const flo
                                hipStream_t s);
 hipError_t launch_draw_raster(const float* images, const void* parts, const void* slots, const int32_t* labels, const float* colors, int B,
                               int T, int H, int W, int M, void* out, int out_uint8, hipStream_t s);
+// frames.hip: raw uint8 frames resized by Pillow's 8-bit bilinear rule (one launch).  frames_sizes_ok: the sizes the launch takes
+bool frames_sizes_ok(int N, int H_in, int W_in, int pl, int pt, int pr, int pb, int H_out, int W_out);
+hipError_t launch_frames_resize(const unsigned char* frames, int N, int H_in, int W_in, int pl, int pt, int pr, int pb, const int32_t* plan_x,
+                                const int32_t* plan_y, int H_out, int W_out, void* out, int out_uint8, hipStream_t s);
 hipError_t launch_gemm_split(const float* X, int64_t ldx, const void* Whi, const void* Wlo, const float* bias, float* Y,
                              int64_t ldy, int M, int N, int K, int relu, const float* feat, int hw, hipStream_t s,
                              const float* scale_dev = nullptr, float scale_mul = 1.f, const float* xscale_dev = nullptr,

@@ -345,6 +345,8 @@ class FeatureViewWindow(ViewWindow):
     def __init__(self, module, B, V, h, w, T_world_local):
         super().__init__(module.box3d_decoder, B, V, h, w, T_world_local, module.token_dtype or torch.float32)
         self._pe = module.add_ray_pe
+        self._module = module
+        self.frame_prep = None             # the FramePrep of put_frames (made at its first call: parq_amd.FramePrep(); assign another)
 
     @torch.no_grad()
     def put_features(self, slot, features_or_pyramid, camera, T_camera_pseudoCam, T_world_pseudoCam):
@@ -378,3 +380,30 @@ class FeatureViewWindow(ViewWindow):
             else:
                 tok = self._pe.tokens(features_or_pyramid, cam, T_cp, T_wp, self._T_wl, dtype=self.dtype)
             self._store(slots, tok.view(self.B, n, self.h * self.w, -1), cam, T_cp, T_wp)
+
+    @torch.no_grad()
+    def put_frames(self, slot, frames, intrinsics, T_world_camera):
+        """Replace the views in `slot` from raw frames: `frames` (B, len(slots), H, W, 3) uint8 on the window's device, `intrinsics`
+        (B, len(slots), 3, 3) of the frames as they are and `T_world_camera` (B, len(slots), 4, 4).  ``self.frame_prep``
+        (``parq_amd.FramePrep()`` unless another was assigned: size, border, up axis, whose intrinsics) prepares the put views only,
+        the module's ``backbone2d`` runs on them and the result — ``all_features`` or ``(fpn_features, fpn_layer)``, with
+        ``camera_feature`` and the two pose tables — goes to ``put_features``.  The window's ``T_world_local`` stays what it was
+        given (the prepared views' own local frame is not used).  ValueError when the module has no ``backbone2d``."""
+        self._alive()
+        backbone = self._module.backbone2d
+        if backbone is None:
+            raise ValueError("ViewWindow.put_frames: the module has no backbone2d to turn images into features (use put_features)")
+        n = 1 if isinstance(slot, int) and not isinstance(slot, bool) else len(slot) if isinstance(slot, (list, tuple, range)) else -1
+        if not isinstance(frames, torch.Tensor) or frames.ndim != 5 or tuple(frames.shape[:2]) != (self.B, n):
+            raise ValueError("ViewWindow.put_frames: frames must be (B, len(slots), H, W, 3) with (B, len(slots)) = %s, got %s"
+                             % ((self.B, n), tuple(getattr(frames, "shape", ()))))
+        if frames.device != self._dev:
+            raise ValueError("ViewWindow.put_frames: the frames are on %s, the window on %s" % (frames.device, self._dev))
+        if self.frame_prep is None:
+            from .frames import FramePrep
+            self.frame_prep = FramePrep()
+        batch = self.frame_prep(frames, intrinsics, T_world_camera)
+        del batch["T_world_local"]
+        batch = backbone(batch)
+        feats = (batch["fpn_features"], batch["fpn_layer"]) if "fpn_features" in batch else batch["all_features"]
+        self.put_features(slot, feats, batch["camera_feature"], batch["T_camera_pseudoCam"], batch["T_world_pseudoCam"])
