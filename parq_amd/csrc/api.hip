@@ -288,10 +288,8 @@ bool kvproj_big_on() {
 // Training: the cross-attention backward of all recurrent iterations can run as ONE launch when the iterations share the layer
 // weights (hence K / V) and the split-precision kernel applies (head dim 64, long key axis); parq_set_backward_batched(h, 0) restores the
 // per-iteration launches.
-int bwd_sets(int I) {          // concurrent iterations of the batched chain backward (development build: PARQ_BWD_SETS)
-    static const int want = [] { const char* e = dev_env("PARQ_BWD_SETS"); return e && atoi(e) > 0 ? atoi(e) : 8; }();
-    int n = want < I ? want : I;
-    return n < 1 ? 1 : (n > 8 ? 8 : n);
+int bwd_sets(int I) {          // concurrent iterations of the batched chain backward: up to 8
+    return I < 1 ? 1 : (I > 8 ? 8 : I);
 }
 bool bwd_batched_ok(const parq_ctx* c, int64_t N);
 // the batched cross-attention backward at head dim 64 takes K / V straight from the forward's 16-bit cache: no fp32 rebuild
@@ -715,10 +713,11 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
         return a;
     };
     // inference only (the backward differentiates the unfolded layers from the stashed pos), and only where chain.hip has the kernels
-    static const bool fold_off = [] { const char* e = dev_env("PARQ_FOLD_POS"); return e && e[0] == '0'; }();
-    const bool fold_pos = !train && !fold_off && chain_linear_supported(self_in_args(true), 1) && chain_linear_supported(cross_q_args(true), 1);
+    // (profiles/r03_ab_fold_pos_mlp.txt)
+    const bool fold_pos = !train && chain_linear_supported(self_in_args(true), 1) && chain_linear_supported(cross_q_args(true), 1);
     // the norm1 seam (self out-projection | cross-attention query projection) as ONE launch (chain.hip seam_tile): inference at d = 256
-    static const int seams = [] { const char* e = dev_env("PARQ_FUSE_SEAMS"); return e ? atoi(e) : 1; }();      // 0: self out-projection and query projection as two launches (A/B)
+    // where the caller asks for it: parq_set_seam_fusion(h, 1).  Two launches are the default since round 6
+    // (profiles/r05_ab_seam_q.txt; under graph replay: profiles/r06_ab_seam_q_under_graph_replay.txt)
     const bool seam_ok = !train && !sharded && fold_pos && C == 256 && TP != nullptr && (inv ? Q : M) % 16 == 0 && c->seam_fusion;
 
     if (sh.mask & 1) {
@@ -731,9 +730,9 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
     float* sample_cnt = sharded ? sh.out + (int64_t)M * C : nullptr;
     // the position MLP's first layer and project + sample are independent (both read only what the previous decode left): one
     // launch when the chain kernels apply; the profiled pass keeps them apart so that the per-kernel groups stay per kernel
-    static const bool fuse_off = [] { const char* e = dev_env("PARQ_FUSE_PE1_SAMPLE"); return e && e[0] == '0'; }();
+    // (profiles/r03_ab_fused_pe1_sample.txt)
     bool fused = false;
-    if (!train && !fuse_off && !c->profiling) {
+    if (!train && !c->profiling) {
         const hipError_t e = launch_pe1_sample(pe1, sc->tokens, reinterpret_cast<const double*>(wsp + ws.T_cl), cam_in, ref, c->sb, B, sc->V,
                                                sc->h, sc->w, C, Q, sample_out, o->coord_pos, gn1, B * 8 * nsl, sample_cnt, s, ind, row0 * 3,
                                                c->tok_type);
@@ -778,8 +777,7 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
     fa.out = wi + ws.sa; fa.out_batch = (int64_t)Q * C; fa.out_row = C;
     {
         Prof p(c, s, PARQ_PROF_SELF_ATTN);
-        static const bool self_one = [] { const char* e = dev_env("PARQ_SELF_ONE_LAUNCH"); return !(e && e[0] == '0'); }();
-        if (dh <= 64 || (self_one && (dh == 128 || dh == 256) && Q <= 1024)) {
+        if (dh <= 64 || ((dh == 128 || dh == 256) && Q <= 1024)) {
             // one launch: a workgroup = 16 queries of one head against all keys (the 256-key self-attention has no long axis to split)
             HIPCHK(launch_self_attn(wi + ws.qkv, 3 * C, B, H, Q, dh, wi + ws.sa, C, s, train ? wi + ws.lse_s : nullptr, dp,
                                     c->site_seed(layer_num, 0)));
@@ -808,7 +806,7 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
         LinearArgs a = lin(wi + ws.sa, C, A + L.self_out_w, C, A + L.self_out_b, wi + ws.xa, C, M, C, C);
         a.R = wi + ws.tgt; a.ldr = C; a.Wp = TP ? TP + L.self_out_w : nullptr; halfw(a, L.self_out_w);
         a.drop_p = dp; a.drop_seed = c->site_seed(layer_num, 1);
-        if (seam_ok && (seams & 1)) {
+        if (seam_ok) {
             // ... and, in the same launch, the query projection behind norm1 (chain.hip seam_tile): q tiles contract sa, tgt and pe_h with
             // pack-time weight products and take norm1's statistics from the partial row sums the xa tiles publish
             a.lnp_out = reinterpret_cast<double*>(wi + ws.lnp1);
@@ -842,10 +840,8 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
         Prof p(c, s, PARQ_PROF_CROSS_ATTN);
         fa.q = wi + ws.qc; fa.q_batch = (int64_t)Q * C; fa.q_head = dh; fa.q_row = C;
         fa.Lk = (int)N; fa.nsplit = ws.cross_split;
-        // odd iterations sweep the K/V cache backwards (Infinity Cache reuse); development: PARQ_FLASH_ALT_PHASE=1 flips the parity,
-        // so that iteration 0 starts on the blocks the K/V projection wrote last
-        const int alt_phase = [] { const char* e = dev_env("PARQ_FLASH_ALT_PHASE"); return e && e[0] == '1' ? 1 : 0; }();
-        fa.flags = ((layer_num + alt_phase) & 1) ? 2 : 0;
+        // odd iterations sweep the K/V cache backwards (Infinity Cache reuse)
+        fa.flags = (layer_num & 1) ? 2 : 0;
         const int64_t lp = flash_lq_pad(Q);
         fa.o_part = wsp + ws.flash;
         fa.m_part = fa.o_part + (int64_t)B * H * fa.nsplit * dh * lp;
@@ -1238,8 +1234,7 @@ int do_backward_kvproj(parq_ctx* c, const parq_scene* sc, float* wsp, const Work
         const LayerW& L = c->ar.layers[li];
         const float* g = wsp + ws.g_kv + (int64_t)li * B * 2 * N * C;          // [B*N][2C]
         const int Mr = (int)(B * N);
-        static const bool split_off = [] { const char* e = dev_env("PARQ_KVPROJ_BWD"); return e && e[0] == 'f'; }();   // "fp32": generic kernels
-        const bool split_ok = ws.bwd_batched && !split_off;                      // the batched backward leaves max |g| in g_kvmax
+        const bool split_ok = ws.bwd_batched;                                    // the batched backward leaves max |g| in g_kvmax
         if (split_ok && kvproj_bwd_split_supported(C)) {
             // dW, db on the fp16 matrix pipe (hi/lo split); g is scaled by the power of two derived from max |g| (attention epilogue)
             HIPCHK(launch_kvproj_bwd_split(g, tok, Mr, C, G + L.cross_in_w + (int64_t)C * C, G + L.cross_in_b + C,
@@ -2520,13 +2515,10 @@ static int ray_pe_impl(const float* camera, const float* T_cp, const float* T_wp
         HIPCHK(launch_split_f32(w2, w2hi, w2lo, (int64_t)C * C, s));
     }
     if (C == 256 && num_samples == 64) {
-        // development: PARQ_RAYPE_TWO_KERNELS=1 runs the round-1 form (hidden tensor written and re-read) for A/B
-        static const int two = [] { const char* e = dev_env("PARQ_RAYPE_TWO_KERNELS"); return e && e[0] == '1' ? 1 : 0; }();
-        if (two && !Hd) return fail(PARQ_ERR_ARG, "the two-kernel form needs the hidden region (do not pass the no-hidden flag)");
-        if (two && fpn) return fail(PARQ_ERR_ARG, "the two-kernel development form of the ray-PE does not take pyramids");
+        // one pass (against the hidden tensor written and re-read by two kernels: profiles/r04_raype_onepass.txt)
         HIPCHK(launch_raype_fused(camera, T_cp, T_wp, T_wl, scale6_host, min_depth, max_depth, B, V, hh, ww, w1hi, w1lo, b1,
                                   w2hi, w2lo, b2, features_nchw, Hd, tabs, tabs + (int64_t)B * V * 12, tokens_out,
-                                  nchw_out ? 1 : 0, s, W2f, two | (cached ? 2 : 0), out16, fpn));
+                                  nchw_out ? 1 : 0, s, W2f, cached ? 1 : 0, out16, fpn));
         return PARQ_OK;
     }
     if (nchw_out) return fail(PARQ_ERR_ARG, "NCHW output needs the fused path (C = 256, 64 samples)");

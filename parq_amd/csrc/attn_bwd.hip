@@ -673,8 +673,9 @@ __global__ __launch_bounds__(256) void attn_bwd_pack_kernel(AttnBwdArgs a, const
 
 // (no scheduling barriers inside the MFMA groups here: letting hipcc hoist the fragment reads over the previous step's MFMAs
 // measured 18.2 -> 16.6 ms; the first version needs them to stay inside its register budget)
-// PIPE (round 3): the dQ tile of query tile n - 1 is computed next to the softmax / dS arithmetic of tile n instead of at the end
-// of its own tile — same results (same operands, same order inside every accumulation), two barriers per tile as before.
+// Pipelined since round 3: the dQ tile of query tile n - 1 is computed next to the softmax / dS arithmetic of tile n instead of at
+// the end of its own tile — same results (same operands, same order inside every accumulation), two barriers per tile as before
+// (13.66 -> 13.51 ms against the unpipelined form: profiles/r03_attn_bwd_phase_shift_variants.txt).
 // CACHE: 0 = fp32 K / V (a.k, a.v); 8 = the forward's mode-4 stage cache; 3 / 1 = the forward's split / single-product cache (a.kvcache): the hi / lo pairs the forward
 // multiplied are used as they are (no fp32 rebuild pass over 2 N C floats per scene, no second copy of K / V in HBM)
 // kGrad1: in the three GRADIENT products of the tile (dV^T += dO^T P, dK^T += Q^T dS, dQ += dS K) the probabilities and dS enter as ONE fp16
@@ -686,7 +687,7 @@ constexpr bool kGrad1 = true;
 
 // One key block of 256 keys (kbx) against every query tile of every iteration.  `add`: the workgroup has already written dQ partials of an
 // earlier key block of its group into its slot (attn_bwd_split2_kernel): this block's are added to them.
-template <bool DROP, bool RAGGED, int PIPE, int CACHE>
+template <bool DROP, bool RAGGED, int CACHE>
 __device__ __forceinline__ void attn_bwd_split2_block(const AttnBwdArgs& a, const float oscale, const _Float16* __restrict__ pack,
                                                       const int kbx, const bool add) {
 #ifdef PARQ_DEV_PROBES
@@ -887,8 +888,8 @@ __device__ __forceinline__ void attn_bwd_split2_block(const AttnBwdArgs& a, cons
             for (int r = 0; r < 4; ++r) part[(qb + 4 * g16 + r) * 64 + db + t16] = g4[r] * cn * inv_os;
         }
     };
-    // which waves go first: PIPE 1 = waves 4..7, PIPE 2 = odd waves (whichever pairs share a SIMD).  Wave-uniform: a scalar branch
-    const bool upper_wave = PIPE == 2 ? (__builtin_amdgcn_readfirstlane(wave) & 1) != 0 : __builtin_amdgcn_readfirstlane(wave) >= 4;
+    // which waves go first: waves 4..7.  Wave-uniform: a scalar branch
+    const bool upper_wave = __builtin_amdgcn_readfirstlane(wave) >= 4;
     tile_dma(0, 0);
     for (int n = 0; n < ntot; ++n) {
         const _Float16* Im = Stg + (n & 1) * kImgHalfs;
@@ -900,16 +901,14 @@ __device__ __forceinline__ void attn_bwd_split2_block(const AttnBwdArgs& a, cons
         if (n + 1 < ntot) tile_dma(n + 1, (n + 1) & 1);     // the other slot was last read before the barrier above
         const float* st = reinterpret_cast<const float*>(Im + 8192);
 
-        // PIPE: the dQ tile of the PREVIOUS query tile (its dS^T image sits in Ds since the barrier above) is computed in THIS
+        // The dQ tile of the PREVIOUS query tile (its dS^T image sits in Ds since the barrier above) is computed in THIS
         // interval, by the upper four waves FIRST (then S / dP, P / dS, dV / dK) and by the lower four LAST.  A SIMD hosts waves w
         // and w + 4: shifted by one phase, one of them is in its VALU phase (softmax, dS, hi/lo splits) while the other one feeds
         // the matrix pipe (upper S/dP ‖ lower P/dS, upper P/dS ‖ lower dV/dK), instead of both running MFMA phase, VALU phase,
         // MFMA phase in lockstep.  The dV / dK products need no barrier (registers + the Q / dO image), only the dS^T image does.  No fences, no extra live
         // registers.  At n == 0 there is no previous tile: the same code runs on whatever Ds holds and its result lands in tile
         // 0's slot, which the next iteration overwrites with the real dQ of tile 0 (same lanes, stores retire in order).
-        if constexpr (PIPE) {
-            if (upper_wave) dq_tile(n > 0 ? n - 1 : 0, n > 0);
-        }
+        if (upper_wave) dq_tile(n > 0 ? n - 1 : 0, n > 0);
 
         // ---- S = Q K^T, dP = dO V^T  (rows = queries, columns = this wave's keys)
         f32x16 sacc, pacc;
@@ -965,8 +964,8 @@ __device__ __forceinline__ void attn_bwd_split2_block(const AttnBwdArgs& a, cons
             }
         }
         }
-        // the dS^T rows of this wave's keys go into Ds: without PIPE right away (nobody reads Ds between the top barrier and the
-        // barrier below); with PIPE after a barrier, because every wave's dq_tile above was still reading the previous tile's image
+        // the dS^T rows of this wave's keys go into Ds after a barrier, because every wave's dq_tile above was still reading the
+        // previous tile's image
         auto write_ds = [&]() {
 #pragma unroll
             for (int m = 0; m < 2; ++m)
@@ -979,7 +978,6 @@ __device__ __forceinline__ void attn_bwd_split2_block(const AttnBwdArgs& a, cons
                         *reinterpret_cast<half4v*>(Ds + 8192 + off) = half4v{sl[m][4 * hh], sl[m][4 * hh + 1], sl[m][4 * hh + 2], sl[m][4 * hh + 3]};
                 }
         };
-        if constexpr (!PIPE) write_ds();
         // ---- dV^T += dO^T P, dK^T += Q^T dS: contraction over the queries; A operands by transpose reads of the natural images
         if (!(probe & 4))
 #pragma unroll
@@ -1001,19 +999,12 @@ __device__ __forceinline__ void attn_bwd_split2_block(const AttnBwdArgs& a, cons
                 if constexpr (!kGrad1) gk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(qth, sl[m], gk[dt], 0, 0, 0);
                 gk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(qtl, sh[m], gk[dt], 0, 0, 0);
                 }
-        if constexpr (!PIPE) {
-            lds_barrier();
-            dq_tile(n);
-        } else {
-            if (!upper_wave) dq_tile(n > 0 ? n - 1 : 0, n > 0);    // the lower waves' turn (their P / dS operands are dead by now)
-            lds_barrier();                                   // every wave has read the previous tile's dS^T image
-            write_ds();                                      // visible to the next interval through the barrier at the top of the loop
-        }
+        if (!upper_wave) dq_tile(n > 0 ? n - 1 : 0, n > 0);    // the lower waves' turn (their P / dS operands are dead by now)
+        lds_barrier();                                   // every wave has read the previous tile's dS^T image
+        write_ds();                                      // visible to the next interval through the barrier at the top of the loop
     }
-    if constexpr (PIPE) {
-        lds_barrier();                                      // the last tile's dS^T image is complete
-        dq_tile(ntot - 1);
-    }
+    lds_barrier();                                      // the last tile's dS^T image is complete
+    dq_tile(ntot - 1);
     // ---- dK, dV of this wave's keys: (d x keys) accumulators -> [key][d] through LDS (Ds + head of Ki, free now), row-contiguous stores
     __syncthreads();
     float* tr = reinterpret_cast<float*>(Ds) + wave * (32 * 65);
@@ -1052,7 +1043,7 @@ __device__ __forceinline__ void attn_bwd_split2_block(const AttnBwdArgs& a, cons
 // partial tiles, the later ones add theirs with no-return float atomics (the slot belongs to this workgroup alone: no contention, a fixed
 // order, the same vmcnt bookkeeping as stores).  The partial array — written by this kernel and read back by attn_bwd_dq_reduce_kernel — shrinks
 // by that factor: at BASELINE cfg 4's shard (4 scenes, 8 iterations) from 6.3 GB to 1.6 GB per step, the reduction from 1.05 to ~0.3 ms.
-template <bool DROP, bool RAGGED, int PIPE = 1, int CACHE = 0>
+template <bool DROP, bool RAGGED, int CACHE = 0>
 __global__ __launch_bounds__(512) void attn_bwd_split2_kernel(AttnBwdArgs a, const float* __restrict__ oscale_ptr,
                                                               const _Float16* __restrict__ pack) {
     const float oscale = *oscale_ptr;
@@ -1061,7 +1052,7 @@ __global__ __launch_bounds__(512) void attn_bwd_split2_kernel(AttnBwdArgs a, con
         const int kbx = (int)blockIdx.x * a.kb_group + pass;
         if (kbx >= nkb) break;
         if (pass > 0) __syncthreads();          // the next block rewrites the K image and the staging slots
-        attn_bwd_split2_block<DROP, RAGGED, PIPE, CACHE>(a, oscale, pack, kbx, pass > 0);
+        attn_bwd_split2_block<DROP, RAGGED, CACHE>(a, oscale, pack, kbx, pass > 0);
     }
 }
 
@@ -1245,13 +1236,8 @@ hipError_t launch_attn_bwd(const float* q, int64_t q_batch, int64_t q_head, int6
     const DetScratch* det = det_scratch();
     if (det && dh != 64) return hipErrorNotSupported;            // deterministic mode: dQ of the head-dim-32 kernel is float atomics
     dim3 grid(ceil_div(Lk, 256), B * H);
-    static const int force = [] {
-        const char* e = dev_env("PARQ_ATTN_BWD");            // "naive" / "mfma" (exact fp32 MFMA): debugging overrides of the split kernel
-        return e ? (e[0] == 'n' ? 1 : 2) : 0;
-    }();
-    if (det && force == 1) return hipErrorNotSupported;
     if (det && Lk >= 2048 && !gq_part) return hipErrorInvalidValue;
-    if (dh == 64 && force == 0 && Lk >= 2048 && absmax) {
+    if (dh == 64 && Lk >= 2048 && absmax) {
         // split-precision kernel: dO scaled by a power of two so that max |dO| sits near 2^10 (keeps the low halves of the small
         // gradient values out of the fp16 subnormals); the scale is computed and consumed on the device (absmax[0] bits, absmax[1] scale)
         hipError_t e = hipMemsetAsync(absmax, 0, sizeof(unsigned int), s);
@@ -1273,7 +1259,7 @@ hipError_t launch_attn_bwd(const float* q, int64_t q_batch, int64_t q_head, int6
         }
         return hipGetLastError();
     }
-    if (dh == 64 && force != 1) {
+    if (dh == 64) {                                   // exact fp32 MFMA: short key axes, and callers without the scale scratch
         const bool big = Lk >= 2048;
         const int nwv = big ? 8 : 2;
         const int KW = nwv * 32;
@@ -1298,17 +1284,10 @@ hipError_t launch_attn_bwd(const float* q, int64_t q_batch, int64_t q_head, int6
         }
         return hipGetLastError();
     }
-    if (dh == 64) {
-        const size_t lds = (size_t)(2 * 32 * 64 + 32 * 257 + 256 * 65 + 64) * sizeof(float);
-        static DynLdsOnce once;
-        if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&attn_bwd_kernel<64>), lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(attn_bwd_kernel<64>, grid, dim3(256), lds, s, a);
-    } else {
-        const size_t lds = (size_t)(2 * 32 * 32 + 32 * 257 + 256 * 33 + 64) * sizeof(float);
-        static DynLdsOnce once;
-        if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&attn_bwd_kernel<32>), lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(attn_bwd_kernel<32>, grid, dim3(256), lds, s, a);
-    }
+    const size_t lds = (size_t)(2 * 32 * 32 + 32 * 257 + 256 * 33 + 64) * sizeof(float);      // head dim 32
+    static DynLdsOnce once;
+    if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&attn_bwd_kernel<32>), lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL(attn_bwd_kernel<32>, grid, dim3(256), lds, s, a);
     return hipGetLastError();
 }
 
@@ -1448,6 +1427,22 @@ static hipError_t attn_bwd_batched_256(const AttnBwdArgs& a, int64_t gq_it, cons
     return hipGetLastError();
 }
 
+// One instantiation of attn_bwd_split2_kernel (512 threads; its K / V images, two Q / dO staging slots and the dS^T image in LDS).
+template <bool DROP, bool RAGGED, int CACHE>
+static hipError_t launch_split2(dim3 grid, const AttnBwdArgs& a, const float* oscale, const _Float16* pk, hipStream_t s) {
+    constexpr size_t lds = (size_t)(2 * 8192 + 2 * 16384 + 2 * kImgHalfs) * sizeof(_Float16);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_split2_kernel<DROP, RAGGED, CACHE>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((attn_bwd_split2_kernel<DROP, RAGGED, CACHE>), grid, dim3(512), lds, s, a, oscale, pk);
+    return hipSuccess;
+}
+template <int CACHE>
+static hipError_t launch_split2(bool drop, bool rag, dim3 grid, const AttnBwdArgs& a, const float* oscale, const _Float16* pk, hipStream_t s) {
+    if (drop) return rag ? launch_split2<true, true, CACHE>(grid, a, oscale, pk, s) : launch_split2<true, false, CACHE>(grid, a, oscale, pk, s);
+    return rag ? launch_split2<false, true, CACHE>(grid, a, oscale, pk, s) : launch_split2<false, false, CACHE>(grid, a, oscale, pk, s);
+}
+
 // Cross-attention backward of n_it recurrent iterations that share K / V (hoisted projection, shared layer weights) in ONE launch of
 // the split-precision kernel: dK / dV are written once instead of read-modify-written per iteration, and the K / V prologue and the
 // transposing epilogue are paid once per key block instead of once per iteration.  q / lse of iteration t live at q + q_off[t] /
@@ -1495,69 +1490,29 @@ hipError_t launch_attn_bwd_batched(const float* q, const int64_t* q_off, int64_t
     float* oscale = reinterpret_cast<float*>(absmax + 1);
     hipLaunchKernelGGL(oscale_kernel, dim3(1), dim3(1), 0, s, absmax, oscale);
     if (dh == 256) return attn_bwd_batched_256(a, gq_it, oscale, mat_scratch, s);     // (kv_absmax: taken by the caller over its dK | dV buffer)
-    static const bool v1 = [] { const char* e = dev_env("PARQ_ATTN_BWD_V"); return e && e[0] == '1'; }();
-    // second version: a workgroup takes kb_group consecutive key blocks and keeps one slot of dQ partials for them (see the kernel)
-    if (v1 || !pack) return hipErrorNotSupported;          // (the first-version kernel wants one partial slot per key block: the workspace no longer has them)
-    const bool grouped = true;
-    a.kb_group = grouped ? attn_bwd_kb_group(B, H, Lk) : 1;
-    a.gqp_it = (int64_t)attn_bwd_dq_partial_floats(B, H, Lq, Lk, dh, grouped);
+    // a workgroup takes kb_group consecutive key blocks and keeps one slot of dQ partials for them (see the kernel); the tile images
+    // are packed once and fetched by LDS-DMA
+    if (!pack) return hipErrorNotSupported;
+    a.kb_group = attn_bwd_kb_group(B, H, Lk);
+    a.gqp_it = (int64_t)attn_bwd_dq_partial_floats(B, H, Lq, Lk, dh, true);
     dim3 g2(ceil_div(ceil_div(Lk, kSpKW), a.kb_group), B * H);
     const int Lq_pad = (Lq + 31) & ~31;
-    if (kvcache && (v1 || !pack)) return hipErrorNotSupported;          // only the second-version kernel reads the 16-bit cache
-    if (pack && !v1) {
-        // second version: tile images packed once, fetched by LDS-DMA; transpose reads
-        constexpr size_t lds2 = (size_t)(2 * 8192 + 2 * 16384 + 2 * kImgHalfs) * sizeof(_Float16);
-        const bool rag = (Lk % kSpKW) != 0;
-        static const int pipe = [] { const char* e = dev_env("PARQ_ATTN_BWD_PIPE"); return e ? atoi(e) : 1; }();
-        if (kvcache && pipe != 1) return hipErrorNotSupported;
-        _Float16* pk = reinterpret_cast<_Float16*>(pack);
-        static const int probe = [] { const char* e = dev_env("PARQ_ATTN_BWD_PROBE"); return e ? atoi(e) : 0; }();
-        a.probe = probe;
-        hipLaunchKernelGGL(attn_bwd_pack_kernel, dim3(Lq_pad / 32, B * H, n_it), dim3(256), 0, s, a, oscale, pk);
-#define PARQ_BWD2(DROP_, RAG_, PIPE_)                                                                                          \
-        {                                                                                                                      \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_split2_kernel<DROP_, RAG_, PIPE_>),                  \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);                                    \
-            if (e != hipSuccess) return e;                                                                                     \
-            hipLaunchKernelGGL((attn_bwd_split2_kernel<DROP_, RAG_, PIPE_>), g2, dim3(512), lds2, s, a, oscale, pk);           \
-        }
-#define PARQ_BWD2C(DROP_, RAG_, C_)                                                                                           \
-        {                                                                                                                      \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_split2_kernel<DROP_, RAG_, 1, C_>),                 \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);                                    \
-            if (e != hipSuccess) return e;                                                                                     \
-            hipLaunchKernelGGL((attn_bwd_split2_kernel<DROP_, RAG_, 1, C_>), g2, dim3(512), lds2, s, a, oscale, pk);          \
-        }
-        if (kvcache && pipe == 1 && cache_terms == 8) {                            // K / V from the forward's mode-4 stage cache
-            if (Lk & 63) return hipErrorNotSupported;
-            if (drop_p > 0.f) { if (rag) PARQ_BWD2C(true, true, 8) else PARQ_BWD2C(true, false, 8) }
-            else { if (rag) PARQ_BWD2C(false, true, 8) else PARQ_BWD2C(false, false, 8) }
-        } else if (kvcache && pipe == 1 && (cache_terms == 3 || cache_terms == 1)) {       // K / V from the forward's 16-bit cache
-            if (cache_terms == 3) {
-                if (drop_p > 0.f) { if (rag) PARQ_BWD2C(true, true, 3) else PARQ_BWD2C(true, false, 3) }
-                else { if (rag) PARQ_BWD2C(false, true, 3) else PARQ_BWD2C(false, false, 3) }
-            } else {
-                if (drop_p > 0.f) { if (rag) PARQ_BWD2C(true, true, 1) else PARQ_BWD2C(true, false, 1) }
-                else { if (rag) PARQ_BWD2C(false, true, 1) else PARQ_BWD2C(false, false, 1) }
-            }
-        } else if (pipe == 1) {
-            if (drop_p > 0.f) { if (rag) PARQ_BWD2(true, true, 1) else PARQ_BWD2(true, false, 1) }
-            else { if (rag) PARQ_BWD2(false, true, 1) else PARQ_BWD2(false, false, 1) }
-        } else if (pipe == 2) {
-            if (drop_p > 0.f) { if (rag) PARQ_BWD2(true, true, 2) else PARQ_BWD2(true, false, 2) }
-            else { if (rag) PARQ_BWD2(false, true, 2) else PARQ_BWD2(false, false, 2) }
-        } else {
-            if (drop_p > 0.f) { if (rag) PARQ_BWD2(true, true, 0) else PARQ_BWD2(true, false, 0) }
-            else { if (rag) PARQ_BWD2(false, true, 0) else PARQ_BWD2(false, false, 0) }
-        }
-#undef PARQ_BWD2
-#undef PARQ_BWD2C
-    } else {
-        e = split_bwd_lds_attr();
-        if (e != hipSuccess) return e;
-        if (drop_p > 0.f) hipLaunchKernelGGL(attn_bwd_split_kernel<true>, g2, dim3(512), kSplitBwdLds, s, a, oscale);
-        else hipLaunchKernelGGL(attn_bwd_split_kernel<false>, g2, dim3(512), kSplitBwdLds, s, a, oscale);
+    const bool drop = drop_p > 0.f, rag = (Lk % kSpKW) != 0;
+    _Float16* pk = reinterpret_cast<_Float16*>(pack);
+    static const int probe = [] { const char* e = dev_env("PARQ_ATTN_BWD_PROBE"); return e ? atoi(e) : 0; }();
+    a.probe = probe;
+    hipLaunchKernelGGL(attn_bwd_pack_kernel, dim3(Lq_pad / 32, B * H, n_it), dim3(256), 0, s, a, oscale, pk);
+    if (kvcache && cache_terms == 8) {                     // K / V from the forward's mode-4 stage cache
+        if (Lk & 63) return hipErrorNotSupported;
+        e = launch_split2<8>(drop, rag, g2, a, oscale, pk, s);
+    } else if (kvcache && cache_terms == 3) {              // K / V from the forward's 16-bit cache: hi / lo pairs
+        e = launch_split2<3>(drop, rag, g2, a, oscale, pk, s);
+    } else if (kvcache && cache_terms == 1) {              // ... single products
+        e = launch_split2<1>(drop, rag, g2, a, oscale, pk, s);
+    } else {                                               // fp32 K / V
+        e = launch_split2<0>(drop, rag, g2, a, oscale, pk, s);
     }
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(attn_bwd_dq_reduce_kernel, dim3(ceil_div(Lq * 64, 256), B * H, n_it), dim3(256), 0, s, gq_part, (int)g2.x, Lq,
                        Lq_pad, H, gq, gq_batch, gq_head, gq_row, a.gqp_it, gq_it);
     return hipGetLastError();
@@ -1583,8 +1538,7 @@ size_t attn_bwd_dq_partial_floats(int B, int H, int Lq, int Lk, int dh, bool gro
 // key blocks per workgroup of the batched split-precision kernel (attn_bwd_split2_kernel): 4 while that leaves at least 512 workgroups
 int attn_bwd_kb_group(int B, int H, int Lk) {
     const int nkb = ceil_div(Lk, 256);
-    static const int want = [] { const char* e = dev_env("PARQ_BWD_KB_GROUP"); return e && atoi(e) > 0 ? atoi(e) : 4; }();      // development A/B: 1 = one slot per key block
-    int g = want;
+    int g = 4;                                      // (against one slot per key block: profiles/r06_ab_train_backward_kb_group_side_kv.txt)
     while (g > 1 && (int64_t)B * H * ceil_div(nkb, g) < 512) g >>= 1;
     return g;
 }

@@ -1035,8 +1035,7 @@ hipError_t launch_gemm_tn(const float* A, int64_t lda, const void* B, int64_t ld
     const int tiles = ceil_div(N, 32) * ceil_div(K, 32);
     if (accumulate && M >= 256) {
         splits = ceil_div(4 * device_num_cus(), tiles);
-        static const int min_rows = [] { const char* e = dev_env("PARQ_TN_ROWS"); return e && atoi(e) > 0 ? atoi(e) : 256; }();
-        const int cap = M >= 8192 ? M / 1024 : M / min_rows;
+        const int cap = M >= 8192 ? M / 1024 : M / 256;
         if (splits > cap) splits = cap;
         if (splits < 1) splits = 1;
     }

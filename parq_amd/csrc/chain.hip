@@ -27,10 +27,11 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 enum : int { kProNone = 0, kProLN = 1, kProGN = 2 };
 enum : int { kResNone = 0, kResPlain = 1, kResLN = 2 };
 
-template <int K, int NT, int PRO, int ADD2, bool BIAS, bool RELU, int RES, bool GNOUT, int NWV = 4, bool LNP = false>
+template <int K, int NT, int PRO, int ADD2, bool BIAS, bool RELU, int RES, bool GNOUT, bool LNP = false>
 __device__ __forceinline__ void chain_tile(const LinearArgs& a, const int block_x, const int block_y) {
     if (block_x == 0 && block_y == 0) publish_progress(a);
-    static_assert(K % (16 * NWV) == 0 && NT >= 1 && NT <= 4 && (NWV == 4 || NWV == 8), "tile shape");
+    constexpr int NWV = 4;                            // waves of a workgroup: they split K
+    static_assert(K % (16 * NWV) == 0 && NT >= 1 && NT <= 4, "tile shape");
     constexpr int NCH = K / (16 * NWV);               // 16-wide K chunks per wave
     constexpr int CS = 16 * NWV;                      // the workgroup's K step per chunk (wave w takes columns w*16 .. w*16+15 of it)
     __shared__ __attribute__((aligned(16))) float red[NWV * NT * 4 * 64];   // [wave][sub-tile][acc reg][lane]
@@ -282,10 +283,10 @@ __device__ __forceinline__ void chain_tile(const LinearArgs& a, const int block_
     }
 }
 
-template <int K, int NT, int PRO, int ADD2, bool BIAS, bool RELU, int RES, bool GNOUT, int NWV = 4>
-__global__ __launch_bounds__(NWV * 64) void chain_linear_kernel(LinearArgs a) {
+template <int K, int NT, int PRO, int ADD2, bool BIAS, bool RELU, int RES, bool GNOUT>
+__global__ __launch_bounds__(256) void chain_linear_kernel(LinearArgs a) {
     PARQ_TL_KERNEL(kTlLinear);
-    chain_tile<K, NT, PRO, ADD2, BIAS, RELU, RES, GNOUT, NWV>(a, (int)blockIdx.x, (int)blockIdx.y);
+    chain_tile<K, NT, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // ONE launch for the two independent stages at the head of an iteration (both depend only on the previous iteration's decode):
@@ -303,7 +304,7 @@ __global__ __launch_bounds__(1024) void pe1_sample_kernel(LinearArgs a, SampleAr
     if ((int)blockIdx.x < n_lin) {
         PARQ_TL_KERNEL(kTlLinear);
         if (threadIdx.x >= 256) return;
-        chain_tile<384, 1, kProNone, 0, true, true, kResNone, false, 4>(a, (int)blockIdx.x, 0);
+        chain_tile<384, 1, kProNone, 0, true, true, kResNone, false>(a, (int)blockIdx.x, 0);
     } else {
         PARQ_TL_KERNEL(kTlProjectSample);
         if (sa.ind != nullptr) {
@@ -527,7 +528,7 @@ template <int NTB>
 __global__ __launch_bounds__(256) void seam_q_kernel(LinearArgs aA, SeamArgs sb, int nA) {
     PARQ_TL_KERNEL(kTlLinear);
     const int bx = (int)blockIdx.x;
-    if (bx < nA) chain_tile<256, 4, kProNone, 0, true, false, kResPlain, false, 4, true>(aA, bx, 0);
+    if (bx < nA) chain_tile<256, 4, kProNone, 0, true, false, kResPlain, false, true>(aA, bx, 0);
     else seam_tile<256, false, 256, 256, NTB, false, false>(sb, bx - nA);
 }
 // The same tile for LONG contractions (K = 1024: the reference's shipped decoder width, config/train.yaml:37-56): the A rows of
@@ -1433,16 +1434,6 @@ hipError_t go(const LinearArgs& a0, int groups, hipStream_t s) {
 }
 
 template <int K, int NT, int PRO, int ADD2, bool BIAS, bool RELU, int RES, bool GNOUT>
-hipError_t go8(const LinearArgs& a0, int groups, hipStream_t s) {          // 8 waves split K: twice the loads in flight per CU
-    if (g_dry_run) return hipSuccess;
-    LinearArgs a = a0;
-    a.tile_map = 0;
-    const dim3 grid((unsigned)((a.N / (16 * NT)) * (a.M / 16)), groups, 1);
-    hipLaunchKernelGGL((chain_linear_kernel<K, NT, PRO, ADD2, BIAS, RELU, RES, GNOUT, 8>), grid, dim3(512), 0, s, a);
-    return hipGetLastError();
-}
-
-template <int K, int NT, int PRO, int ADD2, bool BIAS, bool RELU, int RES, bool GNOUT>
 hipError_t go_stream(const LinearArgs& a0, int groups, hipStream_t s) {
     if (g_dry_run) return hipSuccess;
     LinearArgs a = a0;
@@ -1471,24 +1462,21 @@ hipError_t go_h3(const LinearArgs& a0, int groups, hipStream_t s) {
     LinearArgs a = a0;
     a.tile_map = 0;
     // 32-row tiles (every W fragment feeds two row halves) while their grid still has a workgroup per CU
-    static const int min_wg32 = [] { const char* e = dev_env("PARQ_CHAIN_H3_ROWS32"); return e ? atoi(e) : 256; }();   // 0: never
+    constexpr int min_wg32 = 256;
     const int gm = a.geom_M > 0 ? a.geom_M : a.M;      // batch-invariant inference: ONE scene's rows decide, so that the scene meets the
     // same row-tile form alone and in a batch
     const int64_t wg32 = (int64_t)((a.N / 16 + NT - 1) / NT) * (gm / 32) * groups;
-    constexpr bool fits32 = true;
     // measured per launch at the shipped width (profiles/r06_chain_fp16x3_rows32_threshold.txt): 32-row tiles win wherever their grid has a
     // workgroup per CU, except the launch with a plain addend (self in-projection: A and the addend for two row halves) below two full rounds
-    static const int add_factor = [] { const char* e = dev_env("PARQ_CHAIN_H3_ROWS32_ADD"); return e ? atoi(e) : 2; }();
-    const int64_t need32 = (PRO == kProNone && ADD2 != 0) ? add_factor * (int64_t)min_wg32 : min_wg32;
-    const bool rows32 = fits32 && min_wg32 > 0 && gm % 32 == 0 && a.M % 32 == 0 && wg32 >= need32 && (!a.gn_sums || a.gn_rows_per_scene % 32 == 0) &&
+    constexpr int64_t need32 = (PRO == kProNone && ADD2 != 0) ? 2 * min_wg32 : min_wg32;
+    const bool rows32 = gm % 32 == 0 && a.M % 32 == 0 && wg32 >= need32 && (!a.gn_sums || a.gn_rows_per_scene % 32 == 0) &&
                         (!a.gn_out_sums || a.gn_out_rows_per_scene % 32 == 0);
     if (rows32) {
-        constexpr int R2 = fits32 ? 2 : 1;
         static DynLdsOnce once;
-        if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&chain_linear_h3_kernel<K, NT, R2, PRO, ADD2, BIAS, RELU, RES, GNOUT, FOLD>), (size_t)H3Lds<K, NT, R2>::bytes); e != hipSuccess) return e;
+        if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&chain_linear_h3_kernel<K, NT, 2, PRO, ADD2, BIAS, RELU, RES, GNOUT, FOLD>), (size_t)H3Lds<K, NT, 2>::bytes); e != hipSuccess) return e;
         const dim3 grid((unsigned)((((a.N / 16 + NT - 1) / NT + 7) / 8 * 8) * (a.M / 32)), groups, 1);
-        constexpr int lds = H3Lds<K, NT, R2>::bytes;
-        hipLaunchKernelGGL((chain_linear_h3_kernel<K, NT, R2, PRO, ADD2, BIAS, RELU, RES, GNOUT, FOLD>), grid, dim3(512), lds, s, a);
+        constexpr int lds = H3Lds<K, NT, 2>::bytes;
+        hipLaunchKernelGGL((chain_linear_h3_kernel<K, NT, 2, PRO, ADD2, BIAS, RELU, RES, GNOUT, FOLD>), grid, dim3(512), lds, s, a);
     } else {
         static DynLdsOnce once;
         if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&chain_linear_h3_kernel<K, NT, 1, PRO, ADD2, BIAS, RELU, RES, GNOUT, FOLD>), (size_t)H3Lds<K, NT, 1>::bytes); e != hipSuccess) return e;
@@ -1511,6 +1499,18 @@ int pick_nt(const LinearArgs& a, int want) {
     return 1;
 }
 
+// the fp32 tile with pick_nt(a, WANT) sub-tiles.  pick_nt walks WANT, WANT - 1, .. 2 and falls back to 1, so it returns a value in
+// [1, WANT] and every one of them for some N / 16 (N / 16 = 5: 1): exactly the forms up to WANT are instantiated
+template <int WANT, int K, int PRO, int ADD2, bool BIAS, bool RELU, int RES, bool GNOUT>
+hipError_t go_nt(const LinearArgs& a, int groups, hipStream_t s) {
+    static_assert(WANT >= 2 && WANT <= 4, "sub-tiles per workgroup");
+    const int nt = pick_nt(a, WANT);
+    if constexpr (WANT >= 4) if (nt == 4) return go<K, 4, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);
+    if constexpr (WANT >= 3) if (nt == 3) return go<K, 3, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);
+    if (nt == 2) return go<K, 2, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);
+    return go<K, 1, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);
+}
+
 }  // namespace
 
 // The instantiations are the launches of one decoder iteration (api.hip do_iterate) at the reference's widths:
@@ -1518,7 +1518,6 @@ int pick_nt(const LinearArgs& a, int want) {
 //   cross out-proj (+LN1(xa)) | FFN1 (LN2, ReLU) | FFN2 (K = F, +LN2(xb)) | heads layer 1 (LN3, moments) | heads layer 2 (GN, moments)
 // returns hipErrorNotSupported when no instantiation matches (the caller then launches the generic kernel).
 hipError_t launch_chain_linear(const LinearArgs& a_in, int groups, hipStream_t s) {
-    static const bool wp_off = [] { const char* e = dev_env("PARQ_CHAIN_WPACK"); return e && e[0] == '0'; }();
     // the latency-bound regime (one or a few scenes); above it the generic kernel's 32 x 32 tiles fill the chip
     static const int chain_max_m = [] { const char* e = dev_env("PARQ_CHAIN_MAX_M"); return e ? atoi(e) : 4096; }();   // 0: generic kernel only (measured at 8 scenes, M = 2048: 1.64 -> 1.37 ms of linears)
     // batch-invariant inference (LinearArgs::geom_M): every choice below — this kernel family or the generic one, sub-tiles per
@@ -1528,7 +1527,7 @@ hipError_t launch_chain_linear(const LinearArgs& a_in, int groups, hipStream_t s
     LinearArgs a = a_in;
     if (a.gn_slots <= 0) a.gn_slots = kGnSlots;
     if (a.gn_slots % 64 != 0) return hipErrorInvalidValue;
-    if (wp_off || (a.Wp && (!al16(a.Wp) || a.ldw != a.K))) a.Wp = nullptr;     // the tile-ordered copy mirrors a dense [N][K] matrix
+    if (a.Wp && (!al16(a.Wp) || a.ldw != a.K)) a.Wp = nullptr;     // the tile-ordered copy mirrors a dense [N][K] matrix
     // shape / layout conditions of the specialised kernel
     if (gm % 16 != 0 || a.M % 16 != 0 || a.N % 16 != 0) return hipErrorNotSupported;
     if (a.relu_mask || a.drop_p > 0.f || a.rows_per_batch != a.M || a.col_blk != a.N) return hipErrorNotSupported;
@@ -1549,14 +1548,13 @@ hipError_t launch_chain_linear(const LinearArgs& a_in, int groups, hipStream_t s
     };
     // ---- K = 1024 / 768 with the fp16 hi / lo mirror (LinearArgs::Wh): fp16 x 3 tile
     if (a.Wh && a.wh_scale && al16(a.Wh) && al16(a.wh_scale) && a.ldw == a.K && (a.gW % 256) == 0) {
-        static const int nt_h3 = [] { const char* e = dev_env("PARQ_CHAIN_NT_H3"); return e ? atoi(e) : 4; }();
-        static const bool h3_partial = [] { const char* e = dev_env("PARQ_CHAIN_H3_PARTIAL"); return !(e && e[0] == '0'); }();
+        // pick_nt(a, 4) returns any of 4 .. 1 (N / 16 = 129 at head layer 1: 3): all four forms stay
 #define PARQ_H3(KK, PRO, ADD2, BIAS, RELU, RES, GNOUT)                                                          \
     {                                                                                                           \
-        int nt = pick_nt(a, nt_h3);                                                                             \
+        int nt = pick_nt(a, 4);                                                                                 \
         /* a ragged sub-tile count (head layer 1: 129) takes full-width tiles with a partial last one instead of narrower tiles */ \
         /* where the grid is four rounds and more (head layer 1 at one / two / four / eight scenes: 23.0 | 24.2, 35.4 | 36.8, 66.0 | 60.5 us, -0.75 % per forward at eight) */ \
-        if (nt < nt_h3 && nt_h3 == 4 && a.N >= 1024 && (!a.X2 || a.x2_ncols >= a.N) && h3_partial &&             \
+        if (nt < 4 && a.N >= 1024 && (!a.X2 || a.x2_ncols >= a.N) &&                                            \
             (int64_t)((a.N / 16 + 3) / 4) * (gm / 32) * groups >= 1024) nt = 4;                                 \
         const hipError_t e = nt == 4   ? go_h3<KK, 4, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s)          \
                              : nt == 3 ? go_h3<KK, 3, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s)          \
@@ -1576,75 +1574,55 @@ hipError_t launch_chain_linear(const LinearArgs& a_in, int groups, hipStream_t s
         if (is(768, kProNone, false, true, false, kResNone, false) && a.N >= 512) PARQ_H3(768, kProNone, false, true, false, kResNone, false)   // (kernel-level entry parq_k_linear_half)
 #undef PARQ_H3
     }
-    static const int nt_wide = [] { const char* e = dev_env("PARQ_CHAIN_NT_WIDE"); return e ? atoi(e) : 3; }();     // N = 768 / 528 launches
-    static const int nt_inproj = [] { const char* e = dev_env("PARQ_CHAIN_NT_INPROJ"); return e ? atoi(e) : 4; }();
-    static const int nt_heads2 = [] { const char* e = dev_env("PARQ_CHAIN_NT_HEADS2"); return e ? atoi(e) : 2; }();
-#define PARQ_NT_SWITCH(nt, K, PRO, ADD2, BIAS, RELU, RES, GNOUT)                                                \
-    switch (nt) {                                                                                               \
-        case 4: return go<K, 4, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);                               \
-        case 3: return go<K, 3, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);                               \
-        case 2: return go<K, 2, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);                               \
-        default: return go<K, 1, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);                              \
-    }
+    // sub-tiles wanted per launch (go_nt<WANT, ...>): 4 at the self in-projection, 3 at the N = 768 / 528 launches, 2 at head layer 2.
+    // pick_nt(a, WANT) returns the largest nt in WANT .. 2 that divides N / 16 (and the addend boundary), else 1: never more than
+    // WANT, so go_nt<3> has no NT = 4 form and go_nt<2> no NT = 4 / 3 form; every nt <= WANT occurs for some N and stays
     if (is(384, kProNone, false, true, true, kResNone, false)) return go<384, 1, kProNone, false, true, true, kResNone, false>(a, groups, s);      // pe1
     if (is(256, kProNone, false, true, false, kResNone, false)) return go<256, 1, kProNone, false, true, false, kResNone, false>(a, groups, s);    // pe2
     if (is(256, kProNone, true, true, false, kResNone, false)) {                                                                                   // self in-proj
-        const int nt = pick_nt(a, nt_inproj);
-        PARQ_NT_SWITCH(nt, 256, kProNone, true, true, false, kResNone, false)
+        return go_nt<4, 256, kProNone, true, true, false, kResNone, false>(a, groups, s);
     }
     if (is(256, kProNone, 2, true, false, kResNone, false)) {                                                                                      // self in-proj, folded pos MLP
-        const int nt = pick_nt(a, nt_inproj);
-        PARQ_NT_SWITCH(nt, 256, kProNone, 2, true, false, kResNone, false)
+        return go_nt<4, 256, kProNone, 2, true, false, kResNone, false>(a, groups, s);
     }
     if (is(256, kProLN, 2, true, false, kResNone, false)) return go<256, 1, kProLN, 2, true, false, kResNone, false>(a, groups, s);                 // cross q-proj, folded pos MLP
     if (is(256, kProNone, false, true, false, kResPlain, false)) return go<256, 1, kProNone, false, true, false, kResPlain, false>(a, groups, s);  // self out-proj
     if (is(256, kProLN, true, true, false, kResNone, false)) return go<256, 1, kProLN, true, true, false, kResNone, false>(a, groups, s);          // cross q-proj
     if (is(256, kProNone, false, true, false, kResLN, false)) return go<256, 1, kProNone, false, true, false, kResLN, false>(a, groups, s);        // cross out-proj
     if (is(256, kProLN, false, true, true, kResNone, false)) {                                                                                     // FFN1
-        const int nt = pick_nt(a, nt_wide);
-        PARQ_NT_SWITCH(nt, 256, kProLN, false, true, true, kResNone, false)
+        return go_nt<3, 256, kProLN, false, true, true, kResNone, false>(a, groups, s);
     }
     if (is(768, kProNone, false, true, false, kResLN, false)) return go<768, 1, kProNone, false, true, false, kResLN, false>(a, groups, s);        // FFN2
     if (is(256, kProLN, false, true, false, kResNone, true)) {                                                                                     // heads layer 1
-        const int nt = pick_nt(a, nt_wide);
-        PARQ_NT_SWITCH(nt, 256, kProLN, false, true, false, kResNone, true)
+        return go_nt<3, 256, kProLN, false, true, false, kResNone, true>(a, groups, s);
     }
     if (is(256, kProGN, false, false, false, kResNone, true)) {                                                                                    // heads layer 2
-        const int nt = pick_nt(a, nt_heads2);
-        PARQ_NT_SWITCH(nt, 256, kProGN, false, false, false, kResNone, true)
+        return go_nt<2, 256, kProGN, false, false, false, kResNone, true>(a, groups, s);
     }
-#undef PARQ_NT_SWITCH
     // ---- K = 1024 (the reference's shipped DEC_DIM): streamed-W kernel.  Sub-tiles: 4 (64 columns per workgroup: at one scene
     // N = 1024 gives 256 workgroups) where the addend / moment boundaries allow it
-    static const int nt_big = [] { const char* e = dev_env("PARQ_CHAIN_NT_K1024"); return e ? atoi(e) : 4; }();
-    // K = 1024 forms: "stream" (default; W double-buffered in 256-step batches, 4 waves: measured 1.55 ms of linears per shipped-size
-    // forward) or "8w" (8 waves split K, everything in flight at once: 1.66 ms)
-    static const bool stream_env = [] { const char* e = dev_env("PARQ_CHAIN_K1024"); return !(e && e[0] == '8'); }();
+    // (W double-buffered in 256-step batches, 4 waves: measured 1.55 ms of linears per shipped-size forward, against 1.66 ms with
+    // 8 waves splitting K and everything in flight at once)
     // 32-row form (chain_linear_stream32_kernel) for launches whose 32-row grid still has a workgroup per CU (512 lanes and ~200
     // registers: one per CU is all that fits).  Shipped geometry, per launch, 16-row -> 32-row (profiles/r06_ab_chain_rows32.txt):
     // one scene: head layer 1 34.9 -> 32.5 us, head layer 2 23.3 -> 18.5, self in-projection 30.8 -> 31.6, the N = 1024 launches
     // (128 workgroups: below the threshold) 10.8 -> 20; forward 2.380 -> 2.333 ms at one scene, 7.51 -> 6.82 ms at four
-    static const int min_wg32 = [] { const char* e = dev_env("PARQ_CHAIN_K1024_ROWS32"); return e ? atoi(e) : 256; }();   // 0: never
-    const bool rows32_ok = min_wg32 > 0 && gm % 32 == 0 && a.M % 32 == 0 && (!a.gn_sums || a.gn_rows_per_scene % 32 == 0) &&
+    constexpr int min_wg32 = 256;
+    const bool rows32_ok = gm % 32 == 0 && a.M % 32 == 0 && (!a.gn_sums || a.gn_rows_per_scene % 32 == 0) &&
                            (!a.gn_out_sums || a.gn_out_rows_per_scene % 32 == 0);
+    // Both tables below ask pick_nt(a, 4), which returns any of 4, 3, 2, 1 (N / 16 = 64: 4; 129 at head layer 1: 3; 2: 2; 1: 1), so
+    // go_stream keeps all four forms.  The 32-row kernel was never instantiated with one sub-tile: nt == 1 goes to go_stream
 #define PARQ_STREAM(PRO, ADD2, BIAS, RELU, RES, GNOUT)                                                          \
     {                                                                                                           \
         if (rows32_ok) {                                                                                        \
-            const int nt = pick_nt(a, nt_big);                                                                  \
+            const int nt = pick_nt(a, 4);                                                                       \
             if ((int64_t)(a.N / (16 * nt)) * (gm / 32) * groups >= min_wg32) {                                 \
                 if (nt == 4) return go_stream32<1024, 4, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);      \
                 if (nt == 3) return go_stream32<1024, 3, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);      \
                 if (nt == 2) return go_stream32<1024, 2, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);      \
             }                                                                                                   \
         }                                                                                                       \
-        /* 8-wave form: 256 registers per lane — LayerNorm prologues (gamma, beta per lane) leave room for 3 sub-tiles, 2 with an addend */ \
-        const int nt = pick_nt(a, stream_env || PRO != kProLN ? nt_big : (ADD2 ? 2 : (nt_big < 3 ? nt_big : 3)));       \
-        if (!stream_env) {                                                                                      \
-            if (nt == 4) return go8<1024, 4, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);                  \
-            if (nt == 3) return go8<1024, 3, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);                  \
-            if (nt == 2) return go8<1024, 2, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);                  \
-            return go8<1024, 1, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);                               \
-        }                                                                                                       \
+        const int nt = pick_nt(a, 4);                                                                           \
         if (nt == 4) return go_stream<1024, 4, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);                \
         if (nt == 3) return go_stream<1024, 3, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);                \
         if (nt == 2) return go_stream<1024, 2, PRO, ADD2, BIAS, RELU, RES, GNOUT>(a, groups, s);                \
@@ -1703,9 +1681,8 @@ hipError_t launch_pe1_sample(const LinearArgs& a_in, const void* tokens, const d
     const Sig g = sig_of(a_in);
     if (!(g.K == 384 && g.pro == kProNone && g.add2 == 0 && g.bias && g.relu && g.res == kResNone && !g.gnout)) return hipErrorNotSupported;
     if (C % 4 != 0 || C > 1024 || V <= 0 || V > 16) return hipErrorNotSupported;
-    static const bool wp_off = [] { const char* e = dev_env("PARQ_CHAIN_WPACK"); return e && e[0] == '0'; }();
     LinearArgs a = a_in;
-    if (wp_off || (a.Wp && (!al16(a.Wp) || a.ldw != a.K))) a.Wp = nullptr;
+    if (a.Wp && (!al16(a.Wp) || a.ldw != a.K)) a.Wp = nullptr;
     a.tile_map = 0;
     const int n_lin = (a.N / 16) * (a.M / 16);
     const int nwv = V < 4 ? 4 : V;                                   // >= 4 waves: the linear tiles need 256 threads
@@ -1734,18 +1711,9 @@ hipError_t launch_seam_q(const LinearArgs& xa, const SeamArgs& q, hipStream_t s)
     if (!fused_tile_ok(xa) || xa.rln_stats || !seam_ok(q, xa.M, 4) || !q.X3 || !al16(q.X3) || !al16(q.W3p) || q.ldx3 % 4 != 0) return hipErrorNotSupported;
     LinearArgs a = xa;
     a.tile_map = 0;
-    static const int ntq = [] { const char* e = dev_env("PARQ_SEAM_NT_Q"); return e ? atoi(e) : 2; }();      // column sub-tiles of a query workgroup (A/B)
-    const int nA = (a.N / 64) * (a.M / 16);
-    if (ntq == 1) {
-        const int nB = (q.N / 16) * (q.M / 16);
-        hipLaunchKernelGGL((seam_q_kernel<1>), dim3((unsigned)(nA + nB)), dim3(256), 0, s, a, q, nA);
-    } else if (ntq == 4) {
-        const int nB = (q.N / 64) * (q.M / 16);
-        hipLaunchKernelGGL((seam_q_kernel<4>), dim3((unsigned)(nA + nB)), dim3(256), 0, s, a, q, nA);
-    } else {
-        const int nB = (q.N / 32) * (q.M / 16);
-        hipLaunchKernelGGL((seam_q_kernel<2>), dim3((unsigned)(nA + nB)), dim3(256), 0, s, a, q, nA);
-    }
+    // two column sub-tiles per query workgroup (against one and four: profiles/r05_ab_seam_query_tile_width.txt)
+    const int nA = (a.N / 64) * (a.M / 16), nB = (q.N / 32) * (q.M / 16);
+    hipLaunchKernelGGL((seam_q_kernel<2>), dim3((unsigned)(nA + nB)), dim3(256), 0, s, a, q, nA);
     return hipGetLastError();
 }
 

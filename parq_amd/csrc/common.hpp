@@ -644,7 +644,7 @@ hipError_t launch_raype_fused(const float* cam, const float* T_cp, const float* 
                               float min_depth, float max_depth, int B, int V, int h, int w, const void* W1hi, const void* W1lo,
                               const float* b1, const void* W2hi, const void* W2lo, const float* b2, const float* feat,
                               float* hidden, double* Tl, double* depth, float* out, int nchw_out, hipStream_t s,
-                              void* W2f = nullptr, int two_kernels = 0,
+                              void* W2f, int w2f_cached = 0,      // W2f: 256 KB for W2 in fragment order; cached: it holds this W2 already
                               int out16 = kTokF32,       // out16: kTokF16 / kTokBF16 token rows (one-pass kernel, no hidden, channels-last)
                               const FpnDev* fpn = nullptr);   // features gathered from a pyramid (feat == nullptr)
 // d level_l (B*V, cl, h[l], w[l]) for all four levels from d tokens (B*V*h*w, 4*cl): the adjoint of the bilinear gather in gather

@@ -733,12 +733,10 @@ hipError_t launch_box_decode(const BoxDecodeArgs& a_in, hipStream_t s) {
     if (a.gn_slots % 64 != 0) return hipErrorInvalidValue;
     const int gm = a.geom_M > 0 ? a.geom_M : a.M;      // batch-invariant inference: one scene's rows
     // one row per wave; rows per workgroup: 1 while that still leaves CUs idle (pure latency: spread the rows over the chip), else 4
-    static const int rows_env = [] { const char* e = dev_env("PARQ_DECODE_ROWS"); return e ? atoi(e) : 0; }();
-    const int rows = (rows_env >= 1 && rows_env <= 4) ? rows_env : (gm <= 2 * device_num_cus() ? 1 : 4);
-    static const bool fast_off = [] { const char* e = dev_env("PARQ_DECODE_FAST"); return e && e[0] == '0'; }();
+    const int rows = gm <= 2 * device_num_cus() ? 1 : 4;
     const bool al = ((reinterpret_cast<uintptr_t>(a.h2) | reinterpret_cast<uintptr_t>(a.gn_gamma) | reinterpret_cast<uintptr_t>(a.gn_beta) |
                       reinterpret_cast<uintptr_t>(a.w3)) & 15u) == 0 && a.ld2 % 4 == 0;
-    if (a.C == 256 && a.n_mean * 3 <= 128 && a.n_mean >= 1 && al && !fast_off)
+    if (a.C == 256 && a.n_mean * 3 <= 128 && a.n_mean >= 1 && al)
         hipLaunchKernelGGL(box_decode256_kernel, dim3(ceil_div(a.M, rows)), dim3(rows * 64), 0, s, a);
     else
         hipLaunchKernelGGL(box_decode_kernel, dim3(ceil_div(a.M, rows)), dim3(rows * 64), 0, s, a);

@@ -732,21 +732,19 @@ hipError_t launch_dh(const FlashArgs& a, int nw, hipStream_t s) {
 template <int DH>
 hipError_t merge_dh(const FlashArgs& a, hipStream_t s) {
     const size_t lds = ((size_t)a.nsplit * 32 + 8 * 32 + (size_t)2 * 16 * 32) * sizeof(float);
-    static const int dg_env = [] { const char* e = dev_env("PARQ_MERGE_DG"); return e ? atoi(e) : 0; }();
     // 8 dims per workgroup while that is what it takes to cover the chip (one scene), else 16
     // (batch-invariant inference, FlashArgs::geom_B: the width is chosen as for that many scenes)
     const int64_t wg16 = (int64_t)ceil_div(a.Lq, 32) * (a.geom_B > 0 ? a.geom_B : a.B) * flash_launch_heads(a) * (DH / 16);
-    const int dg = dg_env == 8 || dg_env == 16 ? dg_env : (wg16 < device_num_cus() ? 8 : 16);
-    static const bool fixed_off = [] { const char* e = dev_env("PARQ_MERGE_FIXED"); return e && e[0] == '0'; }();
+    const int dg = wg16 < device_num_cus() ? 8 : 16;
     if constexpr (DH == 64) {
-        if (dg == 8 && a.nsplit == 64 && a.Lq % 32 == 0 && !fixed_off) {       // the one-scene cross-attention merge: all loads up front
+        if (dg == 8 && a.nsplit == 64 && a.Lq % 32 == 0) {       // the one-scene cross-attention merge: all loads up front
             hipLaunchKernelGGL((flash_merge_fixed_kernel<DH, 8, 64>), dim3(a.Lq / 32, a.B * flash_launch_heads(a), DH / 8), dim3(256), 0, s, a);
             return hipGetLastError();
         }
     }
     if constexpr (DH == 256) {
         // the shipped geometry at one scene (32 key splits): the same all-loads-up-front form (10.5 -> ~7 us per launch: 1.986 -> 1.959 ms per forward, outputs bit-identical)
-        if (dg == 16 && a.nsplit == 32 && a.Lq % 32 == 0 && !fixed_off) {
+        if (dg == 16 && a.nsplit == 32 && a.Lq % 32 == 0) {
             hipLaunchKernelGGL((flash_merge_fixed_kernel<DH, 16, 32>), dim3(a.Lq / 32, a.B * flash_launch_heads(a), DH / 16), dim3(256), 0, s, a);
             return hipGetLastError();
         }

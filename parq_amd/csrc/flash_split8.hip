@@ -522,8 +522,7 @@ hipError_t launch_flash_split8(const FlashArgs& a, const void* cache, hipStream_
     if (!flash_split8_supported(a.dh, a.Lk) || a.nsplit < 1 || a.nsplit > 256) return hipErrorInvalidValue;
     FlashArgs b = a;
     b.defer_log2 = kDefer8;
-    static const int wt = [] { const char* e = dev_env("PARQ_FLASH_WT"); return e ? atoi(e) : 1; }();
-    b.flags = ((a.flags & 2) ? 2 : 0) | ((wt && a.Lq % 256 == 0) ? 8 : 0);
+    b.flags = ((a.flags & 2) ? 2 : 0) | (a.Lq % 256 == 0 ? 8 : 0);      // bit 3: write-through partials (flash_split.hip)
     const dim3 grid(b.nsplit, ceil_div(b.Lq, 32 * kNW), b.B * flash_launch_heads(b));
     const unsigned char* c8 = reinterpret_cast<const unsigned char*>(cache);
 #define PARQ_F8_LAUNCH_RR(PROBE, RING, REV)                                                                                    \

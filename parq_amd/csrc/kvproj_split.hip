@@ -710,12 +710,11 @@ static hipError_t launch_dma_nk(const KvProjArgs& a, int B, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int TERMS, int KIND, int D, int TT = kTokF32>
+// ring depth 4 (a fifth slot, one more k-step in flight, measured no gain)
+template <int TERMS, int KIND, int TT = kTokF32>
 static hipError_t launch_dma(const KvProjArgs& a, int B, hipStream_t s) {
-    if (a.C == 4 * kBK) return launch_dma_nk<64, TERMS, KIND, 4, D, 0, TT>(a, B, s);
-    if constexpr (D <= 4) {
-        if (a.C == 2 * kBK) return launch_dma_nk<64, TERMS, KIND, 2, D, 0, TT>(a, B, s);
-    }
+    if (a.C == 4 * kBK) return launch_dma_nk<64, TERMS, KIND, 4, 4, 0, TT>(a, B, s);
+    if (a.C == 2 * kBK) return launch_dma_nk<64, TERMS, KIND, 2, 4, 0, TT>(a, B, s);
     return hipErrorInvalidValue;
 }
 
@@ -735,8 +734,8 @@ template <int TT>
 static hipError_t launch_dma_tok16(const KvProjArgs& a, int B, int N, int C, int terms, int kind, hipStream_t s) {
     if (terms == 8) return (N % 64 == 0 && C == 256) ? launch_dma_nk<64, 8, kF16, 4, 4, 0, TT>(a, B, s) : hipErrorInvalidValue;
     if (terms == 11) return (N % 64 == 0 && C == 256) ? launch_dma_nk<64, 11, kF16, 4, 4, 0, TT>(a, B, s) : hipErrorInvalidValue;
-    if (terms != 3) return kind == kF16 ? launch_dma<1, kF16, 4, TT>(a, B, s) : launch_dma<1, kBF16, 4, TT>(a, B, s);
-    return launch_dma<3, kF16, 4, TT>(a, B, s);
+    if (terms != 3) return kind == kF16 ? launch_dma<1, kF16, TT>(a, B, s) : launch_dma<1, kBF16, TT>(a, B, s);
+    return launch_dma<3, kF16, TT>(a, B, s);
 }
 
 template <int TT>
@@ -842,7 +841,7 @@ hipError_t launch_kvproj_split(const void* tokens, const void* Whi, const void* 
 #endif
         if (terms == 8) return (N % 64 == 0 && C == 256) ? launch_dma_nk<64, 8, kF16, 4, 4>(a, B, s) : hipErrorInvalidValue;
         if (terms == 11) return (N % 64 == 0 && C == 256) ? launch_dma_nk<64, 11, kF16, 4, 4>(a, B, s) : hipErrorInvalidValue;
-        if (terms != 3) return kind == kF16 ? launch_dma<1, kF16, 4>(a, B, s) : launch_dma<1, kBF16, 4>(a, B, s);
+        if (terms != 3) return kind == kF16 ? launch_dma<1, kF16>(a, B, s) : launch_dma<1, kBF16>(a, B, s);
 #ifdef PARQ_DEV_PROBES
         static const int probe = [] { const char* e = dev_env("PARQ_KVPROJ_PROBE"); return e ? atoi(e) : 0; }();      // development
         if (probe && C == 256) {
@@ -858,9 +857,7 @@ hipError_t launch_kvproj_split(const void* tokens, const void* Whi, const void* 
             }
         }
 #endif
-        static const int depth = [] { const char* e = dev_env("PARQ_KVPROJ_RING"); return e ? atoi(e) : 4; }();       // 5: one more k-step in flight (no gain measured)
-        if (depth == 5 && C == 256) return launch_dma<3, kF16, 5>(a, B, s);
-        return launch_dma<3, kF16, 4>(a, B, s);
+        return launch_dma<3, kF16>(a, B, s);
     }
     if (terms != 3) return hipErrorInvalidValue;            // the single-term modes exist on the persistent kernel only
     dim3 grid(ceil_div(nrt, 8) * 8 * nct, B, 1);

@@ -418,11 +418,7 @@ static int pick_tile(int64_t tiles32) {
         return e ? atoi(e) : 0;
     }();
     if (forced == 16 || forced == 32) return forced;
-    static const int below = [] {
-        const char* e = dev_env("PARQ_LINEAR_T16_BELOW");
-        return e ? atoi(e) : 0;
-    }();
-    return tiles32 < (below > 0 ? below : device_num_cus()) ? 16 : 32;
+    return tiles32 < device_num_cus() ? 16 : 32;
 }
 
 // gn_own (batch-invariant inference) asks that no moment of the output is added with atomics: possible where every T x T tile lies

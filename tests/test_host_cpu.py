@@ -73,6 +73,23 @@ def test_product_library_reads_no_environment():
         _lib.load().parq_dev_timeline                              # the development entry point is not exported
 
 
+def test_development_switches_are_exactly_the_documented_ones():
+    """Every environment variable the development library reads (dev_env("PARQ_...") in parq_amd/csrc/) is listed, with what it does,
+    under "Development switches" in tools/README.md — and nothing is listed that the source no longer reads.  A settled A/B is
+    retired from both (profiles/variant_retirement.txt)."""
+    csrc = os.path.join(ROOT, "parq_amd", "csrc")
+    read = set()
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".hip", ".hpp")):
+            read |= set(re.findall(r'dev_env\("(PARQ_[A-Z0-9_]+)"', open(os.path.join(csrc, name)).read()))
+    text = open(os.path.join(ROOT, "tools", "README.md")).read()
+    section = text.split("## Development switches", 1)[1].split("\n## ", 1)[0]
+    listed = re.findall(r"^ {4}(PARQ_[A-Z0-9_]+) ", section, re.M)       # one indented line per switch: name, then what it does
+    assert len(listed) == len(set(listed)), sorted(listed)
+    assert read, "no dev_env() call found: the scan is broken"
+    assert set(listed) == read, (sorted(read - set(listed)), sorted(set(listed) - read))
+
+
 def test_create_validates_config_without_gpu():
     from parq_amd import _lib
     lib = _lib.load()
