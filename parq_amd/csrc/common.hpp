@@ -203,11 +203,14 @@ __device__ __forceinline__ void split8(const float* x, half8& hi, half8& lo) {
 }
 
 // ---- fp8 (OCP e4m3) operand forms of the MX cross terms (flash_split8.hip, the K/V projection's mode-4 epilogue)
-__device__ __forceinline__ float clamp_e4m3(float x) { return __builtin_amdgcn_fmed3f(x, -448.f, 448.f); }
-// e4m3 of four floats, byte i = x[i]; values past +-448 saturate (v_cvt_pk_fp8_f32 itself returns NaN beyond its rounding range)
+template <bool CLAMP = true>
+__device__ __forceinline__ float clamp_e4m3(float x) { return CLAMP ? __builtin_amdgcn_fmed3f(x, -448.f, 448.f) : x; }
+// e4m3 of four floats, byte i = x[i]; values past +-448 saturate (v_cvt_pk_fp8_f32 itself returns NaN beyond its rounding range).
+// CLAMP = false is for callers that know all four inside +-448 (the K/V projection decides that once per block): the same bytes
+template <bool CLAMP = true>
 __device__ __forceinline__ int pack4_e4m3(float a, float b, float c, float d) {
-    const int w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(a), clamp_e4m3(b), 0, false);
-    return __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(c), clamp_e4m3(d), w, true);
+    const int w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3<CLAMP>(a), clamp_e4m3<CLAMP>(b), 0, false);
+    return __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3<CLAMP>(c), clamp_e4m3<CLAMP>(d), w, true);
 }
 // x0, x1 -> packed hi16 (round toward zero: the value split_pair takes its residual against) and the fp32 residuals x - hi (exact)
 __device__ __forceinline__ void split_rtz(float x0, float x1, unsigned& hi, float& d0, float& d1) {
@@ -217,7 +220,9 @@ __device__ __forceinline__ void split_rtz(float x0, float x1, unsigned& hi, floa
 }
 constexpr float kLo8Scale = 1024.f;          // lo parts of K, V, Q enter e4m3 as lo * 2^10 (|lo| < 2^-10 |x|); E8M0 scale 117 undoes it
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-// 16 floats -> 16 bytes e4m3(x) and 16 bytes e4m3((x - hi16(x)) * 2^10), byte i = x[i]
+// 16 floats -> 16 bytes e4m3(x) and 16 bytes e4m3((x - hi16(x)) * 2^10), byte i = x[i].  (|x - hi16(x)| 2^10 < max(2^floor(log2 |x|), 2^-14)
+// — hi16 rounds toward zero — so CLAMP = false needs |x| <= 448 only)
+template <bool CLAMP = true>
 __device__ __forceinline__ void pieces_e4m3(const float* x, i32x4& hi8, i32x4& lo8) {
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
@@ -225,8 +230,8 @@ __device__ __forceinline__ void pieces_e4m3(const float* x, i32x4& hi8, i32x4& l
         float d[4];
         split_rtz(x[4 * w], x[4 * w + 1], h0, d[0], d[1]);
         split_rtz(x[4 * w + 2], x[4 * w + 3], h1, d[2], d[3]);
-        hi8[w] = pack4_e4m3(x[4 * w], x[4 * w + 1], x[4 * w + 2], x[4 * w + 3]);
-        lo8[w] = pack4_e4m3(d[0] * kLo8Scale, d[1] * kLo8Scale, d[2] * kLo8Scale, d[3] * kLo8Scale);
+        hi8[w] = pack4_e4m3<CLAMP>(x[4 * w], x[4 * w + 1], x[4 * w + 2], x[4 * w + 3]);
+        lo8[w] = pack4_e4m3<CLAMP>(d[0] * kLo8Scale, d[1] * kLo8Scale, d[2] * kLo8Scale, d[3] * kLo8Scale);
     }
 }
 // byte offsets inside a 64-key stage of the mode-4 cache (layout: flash_split8.hip): K as hi16 + e4m3 hi8 + e4m3 lo8, V as fp16 (round to

@@ -274,7 +274,7 @@ __global__ __launch_bounds__(kThreads) void kvproj_split_kernel(KvProjArgs a) {
 //
 // Measured on the tiled kernel above: 2.3 GB of global->CU traffic per scene (the 128-column W tile is re-fetched for every row
 // tile: 1.5 GB from L2; tokens re-read once per column tile) — the load path, not HBM or MFMA, sets its time.  Here a workgroup
-// of 8 waves OWNS a 256-column slice of W_kv (all K heads or all V heads at C = 256): each wave keeps the hi/lo fragments of 32
+// of 8 waves OWNS 256 columns of W_kv (a slice: the K and the V columns of two heads): each wave keeps the hi/lo fragments of 32
 // columns x all K in registers (128 VGPRs) for the whole launch and the workgroup walks 64-token tiles of the scene batch,
 // streaming only tokens; B operands never touch LDS.  The token stream is LDS-DMA with a software-pipelined k-step:
 //
@@ -294,7 +294,8 @@ __global__ __launch_bounds__(kThreads) void kvproj_split_kernel(KvProjArgs a) {
 // when ks(q) < D - 2, except in the workgroup's first tile).  A tile with blocks past the scene skips stores, so its epilogue ends
 // with vmcnt(0) and the counts that follow are merely conservative.  Rows past the scene are read clamped and zeroed at conversion.
 // PROBE (development, results wrong by construction; tools/kvproj_probe.sh): bit 0 no MFMAs, 1 no global stores, 2 no conversion
-// (MFMAs on whatever LDS holds), 3 no token DMA, 4 no epilogue at all
+// (MFMAs on whatever LDS holds), 3 no token DMA, 4 no epilogue at all.  Bits 9 and 10 give right results: 9 = slice 0 all K heads, slice 1
+// all V heads (the mapping before the balanced one), 10 = the range handling per value on every block (profiles/kvproj_pairing_ab.txt)
 // Development build with -DPARQ_KV_STAMPS on top (PARQ_DEV_EXTRA_FLAGS=-DPARQ_KV_STAMPS python -c "import __graft_entry__ as g;
 // g.build_dev(force=True)"): cycle-counter stamps of waves 0 and 4 of the first four workgroups over the first 96 k-steps, kept in LDS during
 // the launch and dumped at its end (tools/r06_kvproj_stamps.py -> profiles/r06_kvproj_stamps.txt).  Point 0 = top of a k-step, 1 = this
@@ -355,9 +356,16 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
         slice = r >> 3;
     }
     if (p >= P) return;
-    const int n0 = slice * kCols;
-    const int headcol = (n0 + wave * 32) >> 6;    // scalar: the two waves ct = 0, 1 of a pair share a head
-    const bool isK = headcol < a.H;
+    // A slice is TWO HEADS, K and V: waves 0 - 3 own K of heads 2 slice, 2 slice + 1 (two waves ct = 0, 1 per head), waves 4 - 7 the
+    // V of the same heads.  The workgroups of one slot (ids w and w + 8: the same XCD, the same tiles in the same order) then do
+    // the same work per tile, so neither runs ahead of the other and the k-step the second one requests is still in that XCD's L2;
+    // and each SIMD hosts one K wave and one V wave (waves i and i + 4) instead of two of the longer K epilogues.  Nothing waits
+    // for anything: a partner that falls behind misses L2 and reads HBM.  Which wave computes a head changes nothing the head's
+    // image is made of.  (Until this mapping slice 0 was all K heads and slice 1 all V heads: the V workgroup, whose epilogue is
+    // shorter, ran away from its partner — PROBE & 512 keeps that form for A/B in the development library.)
+    const bool isK = (PROBE & 512) ? slice * kCols + wave * 32 < C : wave < NWV / 2;
+    const int headcol = (PROBE & 512) ? (slice * kCols + wave * 32) >> 6           // scalar: the two waves ct = 0, 1 of a pair share a head
+                                      : (isK ? 0 : a.H) + slice * (kCols / 128) + ((wave & 3) >> 1);
     const int ct = (wave & 1);
     // Which 32 of the head's 64 dims a wave owns is chosen so that its outputs form whole 64-byte pieces of the cache image
     // (see the epilogue): V waves own d = 32 ct + li (whole 64-byte V rows); K waves own the dims whose cache chunk has kh' = ct,
@@ -559,73 +567,117 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
                 const int blk = (m0 >> 5) + t;
                 if (blk >= nblk) continue;                                   // scalar
                 _Float16* out = a.cache + (((int64_t)b * a.H + h) * nblk + blk) * kBlkH;          // (= head_bytes apart when MIX)
+                unsigned char* stage = nullptr;
                 if constexpr (F8) {
                     // mode-4 stage image (flash_split8.hip): this block's fp16 plane at t * 4 KB of the K / V 16-bit region; K lanes also
                     // store their 16 accumulator registers as ONE 16-byte piece of the hi8 plane and one of the lo8 plane
-                    unsigned char* stage = reinterpret_cast<unsigned char*>(a.cache) +
-                                           (MIX ? ((int64_t)b * a.H + h) * ((int64_t)nblk * (2 * kBlkHalfs)) + (int64_t)(m0 >> 6) * kStage8Bytes
-                                                : (((int64_t)b * a.H + h) * (nblk >> 1) + (m0 >> 6)) * kStage8Bytes);
+                    stage = reinterpret_cast<unsigned char*>(a.cache) +
+                            (MIX ? ((int64_t)b * a.H + h) * ((int64_t)nblk * (2 * kBlkHalfs)) + (int64_t)(m0 >> 6) * kStage8Bytes
+                                 : (((int64_t)b * a.H + h) * (nblk >> 1) + (m0 >> 6)) * kStage8Bytes);
                     out = reinterpret_cast<_Float16*>(stage + (ISK ? kS8Kh16 : kS8Vh16 - 2 * kVoff) + t * 4096);
-                    if constexpr (ISK) {
-                        float x16[16];
+                }
+                // ---- the block's values, with the range handling (GUARD: the e4m3 clamps of the stage cache's 8-bit K planes and the
+                // fp16 range compares, per value) or without it; which one runs is decided once per block below
+                auto emit = [&](auto guard_tag) __attribute__((always_inline)) {
+                    constexpr bool GUARD = decltype(guard_tag)::value;
+                    if constexpr (F8) {
+                        if constexpr (ISK) {
+                            float x16[16];
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) x16[r] = acc[t][r] + bK[r];
+                            for (int r = 0; r < 16; ++r) x16[r] = acc[t][r] + bK[r];
 #if defined(PARQ_DEV_PROBES) && defined(PARQ_KV_STAMPS)
-                        if (t == 0) { asm volatile("" : "+v"(x16[0]), "+v"(x16[15])); PARQ_KV_STAMP(5); }
+                            if (t == 0) { asm volatile("" : "+v"(x16[0]), "+v"(x16[15])); PARQ_KV_STAMP(5); }
 #endif
-                        i32x4 hi8, lo8;
-                        pieces_e4m3(x16, hi8, lo8);
-                        const int piece = ((t * 2 + kh) * 2 + ct) * 32 + li;        // piece (c = kh, h = ct) of key li
-                        if constexpr (PROBE & 32) {                                  // development: where does the read-back come from?
-                            if (hi8[0] == 0x12345678 && lo8[1] == 0x1234567) stage[tid] = 1;
-                        } else if constexpr (PROBE & 256) {                          // non-temporal: the written cache is not read again by this kernel
-                            __builtin_nontemporal_store(hi8, reinterpret_cast<i32x4*>(stage + kS8K8hi + piece * 16));
-                            __builtin_nontemporal_store(lo8, reinterpret_cast<i32x4*>(stage + kS8K8lo + piece * 16));
-                        } else if constexpr (!(PROBE & 2)) {
-                            *reinterpret_cast<i32x4*>(stage + kS8K8hi + piece * 16) = hi8;
-                            *reinterpret_cast<i32x4*>(stage + kS8K8lo + piece * 16) = lo8;
-                            if (t == 0) PARQ_KV_STAMP(6);
+                            i32x4 hi8, lo8;
+                            pieces_e4m3<GUARD>(x16, hi8, lo8);
+                            const int piece = ((t * 2 + kh) * 2 + ct) * 32 + li;        // piece (c = kh, h = ct) of key li
+                            if constexpr (PROBE & 32) {                                  // development: where does the read-back come from?
+                                if (hi8[0] == 0x12345678 && lo8[1] == 0x1234567) stage[tid] = 1;
+                            } else if constexpr (PROBE & 256) {                          // non-temporal: the written cache is not read again by this kernel
+                                __builtin_nontemporal_store(hi8, reinterpret_cast<i32x4*>(stage + kS8K8hi + piece * 16));
+                                __builtin_nontemporal_store(lo8, reinterpret_cast<i32x4*>(stage + kS8K8lo + piece * 16));
+                            } else if constexpr (!(PROBE & 2)) {
+                                *reinterpret_cast<i32x4*>(stage + kS8K8hi + piece * 16) = hi8;
+                                *reinterpret_cast<i32x4*>(stage + kS8K8lo + piece * 16) = lo8;
+                                if (t == 0) PARQ_KV_STAMP(6);
+                            }
                         }
                     }
-                }
-                half8 hi[2], lo[2];
+                    half8 hi[2], lo[2];
 #pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    float x[8];
+                    for (int m = 0; m < 2; ++m) {
+                        float x[8];
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) x[e] = acc[t][8 * m + e] + (ISK ? bK[ISK ? 8 * m + e : 0] : bK[0]);
-                    if constexpr (F8 && !ISK) hi[m] = cvt8_rn<kF16>(x);          // mode 4: V as one fp16 value, round to nearest
-                    else if constexpr (SPLIT) split8(x, hi[m], lo[m]);
-                    else hi[m] = cvt8_rn<KIND>(x);
-                    if constexpr (KIND == kF16) {
+                        for (int e = 0; e < 8; ++e) x[e] = acc[t][8 * m + e] + (ISK ? bK[ISK ? 8 * m + e : 0] : bK[0]);
+                        if constexpr (F8 && !ISK) hi[m] = cvt8_rn<kF16>(x);          // mode 4: V as one fp16 value, round to nearest
+                        else if constexpr (SPLIT) split8(x, hi[m], lo[m]);
+                        else hi[m] = cvt8_rn<KIND>(x);
+                        if constexpr (GUARD && KIND == kF16) {
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) ovf |= !(fabsf(x[e]) < 60000.f);
-                    }
-                }
-#pragma unroll
-                for (int pl = 0; pl < (SPLIT && !F8 ? 2 : 1); ++pl) {
-#pragma unroll
-                    for (int m = 0; m < 2; ++m)
-                        *reinterpret_cast<half8*>(strip + li * 32 + (((2 * m + kh) ^ swz) << 3)) = pl ? lo[m] : hi[m];
-                    // same-wave LDS round trip: DS operations of one wave complete in order
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const int row = (lane >> 2) + 16 * j, pc = lane & 3;
-                        const half8 v = *reinterpret_cast<const half8*>(strip + row * 32 + pc * 8);
-                        if constexpr ((PROBE & 2) || ((PROBE & 64) && ISK) || ((PROBE & 128) && !ISK)) {
-                            if (v[0] == (_Float16)123.f) out[tid] = v[1];
-                        } else if constexpr (ISK) {
-                            const int half_row = ct ^ ((row >> 3) & 1);           // bit 2 of the row's swizzle (key >> 1) & 7
-                            half8* dst = reinterpret_cast<half8*>(out + pl * 2048 + row * 64 + ((4 * half_row + pc) << 3));
-                            if constexpr (PROBE & 256) __builtin_nontemporal_store(v, dst);
-                            else *dst = v;
-                        } else {
-                            half8* dst = reinterpret_cast<half8*>(out + kVoff + pl * 2048 + (32 * ct + row) * 32 + pc * 8);
-                            if constexpr (PROBE & 256) __builtin_nontemporal_store(v, dst);
-                            else *dst = v;
+                            for (int e = 0; e < 8; ++e) ovf |= !(fabsf(x[e]) < 60000.f);
                         }
                     }
-                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int pl = 0; pl < (SPLIT && !F8 ? 2 : 1); ++pl) {
+#pragma unroll
+                        for (int m = 0; m < 2; ++m)
+                            *reinterpret_cast<half8*>(strip + li * 32 + (((2 * m + kh) ^ swz) << 3)) = pl ? lo[m] : hi[m];
+                        // same-wave LDS round trip: DS operations of one wave complete in order
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const int row = (lane >> 2) + 16 * j, pc = lane & 3;
+                            const half8 v = *reinterpret_cast<const half8*>(strip + row * 32 + pc * 8);
+                            if constexpr ((PROBE & 2) || ((PROBE & 64) && ISK) || ((PROBE & 128) && !ISK)) {
+                                if (v[0] == (_Float16)123.f) out[tid] = v[1];
+                            } else if constexpr (ISK) {
+                                const int half_row = ct ^ ((row >> 3) & 1);           // bit 2 of the row's swizzle (key >> 1) & 7
+                                half8* dst = reinterpret_cast<half8*>(out + pl * 2048 + row * 64 + ((4 * half_row + pc) << 3));
+                                if constexpr (PROBE & 256) __builtin_nontemporal_store(v, dst);
+                                else *dst = v;
+                            } else {
+                                half8* dst = reinterpret_cast<half8*>(out + kVoff + pl * 2048 + (32 * ct + row) * 32 + pc * 8);
+                                if constexpr (PROBE & 256) __builtin_nontemporal_store(v, dst);
+                                else *dst = v;
+                            }
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                };
+                if constexpr (KIND != kF16 || (PROBE & 1024)) {      // (bf16 has no range handling; PROBE & 1024: per value, always — A/B)
+                    emit(std::true_type{});
+                } else {
+                    // One range decision per 32-key block and wave.  A K wave of the stage cache needs no clamp and no compare when
+                    // every |x| < 448 (the lo pieces are no larger: |x - hi16(x)| 2^10 < max(2^floor(log2 |x|), 2^-14)); every other
+                    // wave needs no compare when every |x| < 60000.  Then the guarded code would store the same bytes and raise
+                    // nothing, so the plain code runs; otherwise the guarded code runs, for the whole block.
+                    bool out_of_range;
+                    if constexpr (ISK) {
+                        // transposed product: a lane's registers are different rows of W, so a NaN can sit in one register alone, and
+                        // a float maximum would drop it.  On the raw words it cannot hide: the signed maximum finds the largest
+                        // positive pattern (+NaN above +inf), the unsigned one the largest negative pattern (-NaN above -inf)
+                        constexpr unsigned lim = __builtin_bit_cast(unsigned, F8 ? 448.f : 60000.f);
+                        int pmax = (int)0x80000000;
+                        unsigned nmax = 0u;
+#pragma unroll
+                        for (int r = 0; r < 16; r += 2) {
+                            const unsigned u0 = __builtin_bit_cast(unsigned, acc[t][r] + bK[ISK ? r : 0]);
+                            const unsigned u1 = __builtin_bit_cast(unsigned, acc[t][r + 1] + bK[ISK ? r + 1 : 0]);
+                            pmax = max(max((int)u0, (int)u1), pmax);
+                            nmax = max(max(u0, u1), nmax);
+                        }
+                        out_of_range = !(pmax < (int)lim && nmax < (lim | 0x80000000u));
+                    } else {
+                        // a lane's registers are tokens of ONE row of W: a non-finite weight or bias makes all of them non-finite
+                        // (caught: an infinity wins the maximum, and the maximum of NaNs alone is NaN), and a non-finite token has
+                        // raised the same flag word where this launch converted it
+                        float m = fabsf(acc[t][0] + bK[0]);
+#pragma unroll
+                        for (int r = 1; r < 16; r += 2)
+                            m = fmaxf(fmaxf(fabsf(acc[t][r] + bK[0]), r + 1 < 16 ? fabsf(acc[t][r + 1] + bK[0]) : m), m);
+                        out_of_range = !(m < 60000.f);
+                    }
+                    if (__builtin_amdgcn_ballot_w64(out_of_range) != 0ull) emit(std::true_type{});      // wave-uniform
+                    else emit(std::false_type{});
                 }
                 if (t == 0) PARQ_KV_STAMP(7);
             }
@@ -816,7 +868,7 @@ hipError_t launch_kvproj_split(const void* tokens, const void* Whi, const void* 
     a.row0 = row0; a.row_end = row_end;
     const int nct = 2 * C / kBN, nrt = ceil_div(row_end - row0, kBM);
     if (C <= 4 * kBK && C % (2 * kBK) == 0) {
-        // W-stationary persistent kernel: one workgroup per CU, the column slices of one slot on one XCD
+        // W-stationary persistent kernel: one workgroup per CU, the slices (head pairs) of one slot on one XCD, walking the same tiles
         if (tok_type == kTokF16) return launch_dma_tok16<kTokF16>(a, B, N, C, terms, kind, s);
         if (tok_type == kTokBF16) return launch_dma_tok16<kTokBF16>(a, B, N, C, terms, kind, s);
 #ifdef PARQ_DEV_PROBES
@@ -835,6 +887,9 @@ hipError_t launch_kvproj_split(const void* tokens, const void* Whi, const void* 
                 case 128: return launch_dma_nk<64, 8, kF16, 4, 4, 128>(a, B, s);
                 case 224: return launch_dma_nk<64, 8, kF16, 4, 4, 224>(a, B, s);
                 case 256: return launch_dma_nk<64, 8, kF16, 4, 4, 256>(a, B, s);
+                case 512: return launch_dma_nk<64, 8, kF16, 4, 4, 512>(a, B, s);          // (512, 1024: results right — the two forms this kernel had
+                case 1024: return launch_dma_nk<64, 8, kF16, 4, 4, 1024>(a, B, s);        // before, each alone and together, for A/B)
+                case 1536: return launch_dma_nk<64, 8, kF16, 4, 4, 1536>(a, B, s);
                 default: break;
             }
         }

@@ -71,7 +71,7 @@ def launches(rec):
         name = "+".join(NAMES.get(int(k), str(k)) for k in ids)
         blk = rec[idx, 1].astype(np.int64)
         dur = (t1[idx] - t0[idx]) * 0.01
-        sl = (blk % 16) >> 3                            # kvproj_dma_kernel at C = 256: slice 0 = K heads, 1 = V heads
+        sl = (blk % 16) >> 3                            # kvproj_dma_kernel at C = 256: slice 0 = heads 0, 1 (K and V), slice 1 = heads 2, 3
         extra = {}
         if name == "flash_split":
             # workgroup run time by XCD and by head (grid = (key splits, 1, heads): linear index = split + nsplit * head)
@@ -113,7 +113,7 @@ def main():
             print("# K/V projection: %d workgroups, body %.2f us; workgroup run time min %.2f / p10 %.2f / median %.2f / p90 %.2f / max %.2f us"
                   % (l["wgs"], (l["last_end"] - l["first_start"]) * 0.01, l["min_wg_us"], l["p10_wg_us"], l["median_wg_us"], l["p90_wg_us"], l["max_wg_us"]))
             if "k_wg" in l:
-                print("#   K-slice workgroups median %.2f / max %.2f us, V-slice workgroups median %.2f / max %.2f us" % (l["k_wg"] + l["v_wg"]))
+                print("#   slice-0 workgroups median %.2f / max %.2f us, slice-1 workgroups median %.2f / max %.2f us" % (l["k_wg"] + l["v_wg"]))
     # per-iteration table: the chain of 15 launches starting at the first 'linear' after the (k-1)-th box_decode
     dec_idx = [i for i, l in enumerate(ls) if l["kernel"] == "box_decode"]
     k = args.iteration
