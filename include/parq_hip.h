@@ -555,6 +555,69 @@ int parq_parse_pred(const float *center, const float *size, const float *ortho6d
 int parq_obb_iou(const double *boxes_a, int64_t n_a_total, const double *boxes_b, int64_t n_b_total, const int64_t *segments,
                  int32_t S, int64_t total_pairs, double *iou3d_out, double *iou2d_out, parq_stream stream);
 
+/* ---- rectangular assignment on the device (scipy.optimize.linear_sum_assignment(-m)), one launch, one wavefront per problem ----
+ * S independent problems: segment s is a row-major float32 matrix of n_rows[s] x n_cols[s] inside m (m_total elements).
+ * segments (S, 4) int64 on the DEVICE: [first element in m, n_rows, n_cols, first element in row_to_col].  row_to_col (out_total)
+ * int32: per row the column it is assigned, or -1; with more rows than columns every column is used once, otherwise every row.  The
+ * assignment maximises the sum of the chosen entries taken as float64, for m without NaN.
+ * Algorithm (its NumPy statement is tests/scene_tracks_cases.py assign_statement, which this entry reproduces exactly, ties
+ * included): shortest augmenting paths on cost = -(double)m with float64 duals u, v starting at 0, rows in index order, on the
+ * transpose (by index) when n_rows > n_cols.  From row i the reduced cost of an unscanned column j is ((min + cost[i][j]) - u[i]) -
+ * v[j]; the next column is the unscanned one of least path cost, among equal ones an UNASSIGNED column before an assigned one, then
+ * the lower index; at the sink, with d_j = min - path_cost[j] over the scanned columns, v[j] -= d_j, u[row of j] += d_j,
+ * u[current row] += min.  Each sum is rounded once (no contraction).  No atomics: two calls give the same bits.
+ * max_rows / max_cols: host bounds of every segment's sides, at most 2048 each; they choose the kernel's LDS size and the workspace.
+ * workspace: parq_assign_max_workspace_bytes(S, max_rows, max_cols) bytes, 16-byte aligned (0 for arguments this entry refuses).
+ * It receives each problem's final duals, float64, S rows of [u of the max_rows rows | v of the max_cols columns] in the
+ * matrix's own orientation (entries beyond a segment's sides are not written): u[r] + v[c] <= -m[r][c], with equality on assigned
+ * pairs, is the certificate that the assignment is optimal.  The library allocates nothing and does not synchronise.
+ * S = 0 is valid and launches nothing.  PARQ_ERR_ARG, with nothing launched: a NULL array that is needed, a negative count,
+ * max_rows or max_cols above 2048, a workspace too small or misaligned.  A table row that reaches outside what the arguments describe
+ * (a side above max_rows / max_cols, elements beyond m_total or out_total, a negative number) writes nothing.
+ * (Parenthesised names: see parq_set_batch_invariant; the five entries of this section and the next are typed in
+ * _lib.EXTRA_SYMBOLS.) */
+size_t (parq_assign_max_workspace_bytes)(int32_t S, int32_t max_rows, int32_t max_cols);
+int (parq_assign_max)(const float *m, int64_t m_total, const int64_t *segments, int32_t S, int32_t max_rows, int32_t max_cols,
+                    void *workspace, size_t workspace_bytes, int32_t *row_to_col, int64_t out_total, parq_stream stream);
+
+/* ---- a device-resident track store: detections followed across snippets (utils/f1_eval.py:293-352 matching_pred), three launches
+ * store: parq_tracks_store_bytes(S_cap, max_tracks) bytes of DEVICE memory, zero-filled by the caller before first use; S_cap scene
+ * slots of 2 + 26 * max_tracks 32-bit words each: count (int32), dropped (int32), labels[max_tracks] (int32), scores[max_tracks]
+ * (float32), corners[max_tracks][8][3] (float32, world frame, Obb3D.bb3corners_object order).  A track's id is its position in its
+ * slot; tracks are never removed.
+ * Per call: slots_host (B) int32 on the HOST, the slot of each scene of the batch, each in [0, S_cap) and listed once;
+ * corners_world (B,Q,8,3) float32; sem_cls_prob (B,Q,K) float32; pred_mask (B,Q) bytes.  track_id (B,Q) int32 out; iou_out
+ * (B,Q,max_tracks) float32 or NULL: for tests, row d of scene b receives the IoUs of that scene's d-th detection with its tracks
+ * (other elements are not written).
+ * The rule, per scene, with n = the slot's count before the call:
+ *  1. Selection.  Query q is a detection when the arg-max class of its K probabilities (first index of the maximum) is not K - 1,
+ *     the maximum exceeds conf_thresh (a float32 comparison) and pred_mask is non-zero; a row with a NaN probability is none.
+ *     Detections keep query order: D of them.
+ *  2. IoU[d][t] = (float32) iou3d(canon(detection d), canon(track t)), iou3d being parq_obb_iou's routine (one text:
+ *     csrc/obb_pair.hpp) and canon computed in float64 from the float32 corners: re-order with [4,0,1,5,7,3,2,6], then (x, y, z) ->
+ *     (x, c*y - z, y + c*z) with c = cos(pi/2) = 6.123233995736766e-17, each product and sum rounded once.  A box with a non-finite
+ *     corner has IoU 0 with everything.
+ *  3. parq_assign_max's assignment on that D x n matrix; n = 0 assigns nothing.
+ *  4. An assigned pair (d, t) matches unless IoU[d][t] < iou_thresh (float32 comparison).  A matched detection's track_id is t; if
+ *     scores[t] < score_d (float32), the track takes the detection's label, score and corners and keeps its id.
+ *  5. Every other detection, in query order, is a birth: the k-th of the call becomes track n + k and gets that id.  A position
+ *     >= max_tracks is not stored: its id is -2 and `dropped` grows by one; count = min(n + births, max_tracks).
+ *  6. track_id = -1 for queries that are no detection.
+ * (The reference lists never-assigned detections before assigned-under-threshold ones when it appends; here births are numbered in
+ * query order.  Same set of tracks, possibly other ids among tracks born in one step.)
+ * No atomics; counts never leave the device; the call only enqueues.  Every number read from device memory is checked before it
+ * indexes anything: a slot whose count is outside [0, max_tracks] is left untouched and its scene's track_id is all -1.
+ * workspace: parq_tracks_update_workspace_bytes(B, Q, max_tracks) bytes, 16-byte aligned.  B = 0 is valid and launches nothing.
+ * PARQ_ERR_ARG, with nothing launched: Q or max_tracks outside [1, 2048], K < 2, a negative count, a NULL pointer (iou_out
+ * excepted), a slot outside [0, S_cap) or listed twice, a workspace too small or misaligned.  The *_bytes functions return 0 for
+ * arguments the entry refuses. */
+size_t (parq_tracks_store_bytes)(int32_t S_cap, int32_t max_tracks);
+size_t (parq_tracks_update_workspace_bytes)(int32_t B, int32_t Q, int32_t max_tracks);
+int (parq_tracks_update)(void *store, int32_t S_cap, int32_t max_tracks, const int32_t *slots_host, int32_t B,
+                       const float *corners_world, const float *sem_cls_prob, const unsigned char *pred_mask, int32_t Q, int32_t K,
+                       float conf_thresh, float iou_thresh, void *workspace, size_t workspace_bytes, int32_t *track_id,
+                       float *iou_out /*NULL in normal use*/, parq_stream stream);
+
 /* ---- boxes drawn into the normalised input views (utils/parq_utils.py:141-211 draw_detections), three launches ------------------
  * images (B,T,3,H,W) float32; camera (B,T,6) = [w, h, fx, fy, cx, cy]; T_camera_pseudoCam, T_world_pseudoCam (B,T,12) = [R row-major |
  * t]; corners_world (B,M,8,3) float32 in Obb3D.bb3corners_object order; labels (B,M) int32; keep (B,M) bytes or NULL (all);

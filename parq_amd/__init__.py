@@ -7,6 +7,8 @@ Public surface mirrors the reference (ymingxie/PARQ):
     InFlight     (no counterpart: the reference calls its model once per batch, eval.py:46)  several forwards of one module in flight
     ViewWindow   (no counterpart: the reference re-projects every view of every snippet)  a streaming window of view slots
     draw_boxes, box_colors (utils/parq_utils.py:134,141 get_colors / draw_detections)  boxes drawn into the views on the device
+    SceneTracks  (utils/f1_eval.py:293 matching_pred, there on the host and inside the evaluator only)  detections followed across
+                 snippets in a device-resident track store: one enqueue per snippet batch returns a track id per query
     FramePrep, resize_frames, resized_intrinsics, gravity_aligned, snippet_local (datasets/transforms.py:211 ScanNetBaseTransform)
                  raw uint8 frames, intrinsics and T_world_camera prepared on the device into the batch PARQ.forward reads
     ResnetFPN    (model/resnet_fpn.py:16)       wrapper of a user-supplied ResNet-FPN; its neck is fused into the tokenisation
@@ -38,6 +40,9 @@ def __getattr__(name):
     if name in ("draw_boxes", "box_colors"):
         from . import draw
         return getattr(draw, name)
+    if name == "SceneTracks":
+        from .scene_tracks import SceneTracks
+        return SceneTracks
     if name in ("FramePrep", "resize_frames", "resized_intrinsics", "gravity_aligned", "snippet_local"):
         from . import frames
         return getattr(frames, name)

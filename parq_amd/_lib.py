@@ -141,6 +141,11 @@ EXTRA_SYMBOLS = {
     "parq_frame_plan_ints": (_sz, [_i32, _i32]),
     "parq_frame_plan": (C.c_int, [_i32, _i32, C.POINTER(_i32)]),
     "parq_frames_resize": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
+    "parq_assign_max_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "parq_assign_max": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _sz, _vp, _i64, _vp]),
+    "parq_tracks_store_bytes": (_sz, [_i32, _i32]),
+    "parq_tracks_update_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "parq_tracks_update": (C.c_int, [_vp, _i32, _i32, C.POINTER(_i32), _i32, _vp, _vp, _vp, _i32, _i32, _f, _f, _vp, _sz, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -2676,6 +2676,64 @@ int parq_obb_iou(const double* boxes_a, int64_t n_a_total, const double* boxes_b
     return PARQ_OK;
 }
 
+size_t parq_assign_max_workspace_bytes(int32_t S, int32_t max_rows, int32_t max_cols) {
+    if (S < 0 || max_rows < 0 || max_cols < 0 || max_rows > 2048 || max_cols > 2048) return 0;
+    return ((size_t)S * ((size_t)max_rows + (size_t)max_cols) * 8 + 15) & ~(size_t)15;
+}
+
+int parq_assign_max(const float* m, int64_t m_total, const int64_t* segments, int32_t S, int32_t max_rows, int32_t max_cols,
+                    void* workspace, size_t workspace_bytes, int32_t* row_to_col, int64_t out_total, parq_stream stream) {
+    if (S < 0 || m_total < 0 || out_total < 0 || max_rows < 0 || max_cols < 0) return fail(PARQ_ERR_ARG, "parq_assign_max: negative count");
+    if (max_rows > 2048 || max_cols > 2048) return fail(PARQ_ERR_ARG, "parq_assign_max: max_rows = %d, max_cols = %d; at most 2048 each", max_rows, max_cols);
+    if (S == 0) return PARQ_OK;                                         // nothing to solve: no launch
+    if (!segments || (m_total > 0 && !m) || (out_total > 0 && !row_to_col)) return fail(PARQ_ERR_ARG, "parq_assign_max: NULL argument");
+    const size_t need = parq_assign_max_workspace_bytes(S, max_rows, max_cols);
+    if (need > 0 && !workspace) return fail(PARQ_ERR_ARG, "parq_assign_max: NULL workspace");
+    if (workspace_bytes < need) return fail(PARQ_ERR_ARG, "parq_assign_max: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 15) return fail(PARQ_ERR_ARG, "parq_assign_max: the workspace must be 16-byte aligned");
+    HIPCHK(launch_assign_max(m, m_total, segments, S, max_rows, max_cols, static_cast<double*>(workspace), row_to_col, out_total,
+                             (hipStream_t)stream));
+    return PARQ_OK;
+}
+
+size_t parq_tracks_store_bytes(int32_t S_cap, int32_t max_tracks) {
+    if (S_cap < 0 || max_tracks < 1 || max_tracks > 2048) return 0;
+    return (size_t)S_cap * (2 + 26 * (size_t)max_tracks) * 4;
+}
+
+size_t parq_tracks_update_workspace_bytes(int32_t B, int32_t Q, int32_t max_tracks) {
+    if (B < 0 || Q < 1 || Q > 2048 || max_tracks < 1 || max_tracks > 2048) return 0;
+    return tracks_update_workspace_bytes(B, Q, max_tracks);
+}
+
+int parq_tracks_update(void* store, int32_t S_cap, int32_t max_tracks, const int32_t* slots_host, int32_t B, const float* corners_world,
+                       const float* sem_cls_prob, const unsigned char* pred_mask, int32_t Q, int32_t K, float conf_thresh,
+                       float iou_thresh, void* workspace, size_t workspace_bytes, int32_t* track_id, float* iou_out, parq_stream stream) {
+    if (B < 0 || S_cap < 0) return fail(PARQ_ERR_ARG, "parq_tracks_update: negative count");
+    if (Q < 1 || Q > 2048 || max_tracks < 1 || max_tracks > 2048 || K < 2)
+        return fail(PARQ_ERR_ARG, "parq_tracks_update: Q = %d, max_tracks = %d, K = %d; 1 <= Q, max_tracks <= 2048 and K >= 2", Q, max_tracks, K);
+    if (B == 0) return PARQ_OK;                                         // no scene: no launch
+    if (!store || !slots_host || !corners_world || !sem_cls_prob || !pred_mask || !workspace || !track_id)
+        return fail(PARQ_ERR_ARG, "parq_tracks_update: NULL argument");
+    {
+        std::vector<char> seen((size_t)S_cap, 0);
+        for (int b = 0; b < B; ++b) {
+            const int32_t sl = slots_host[b];
+            if (sl < 0 || sl >= S_cap) return fail(PARQ_ERR_ARG, "parq_tracks_update: slot %d of scene %d outside [0, %d)", sl, b, S_cap);
+            if (seen[(size_t)sl]) return fail(PARQ_ERR_ARG, "parq_tracks_update: slot %d listed twice in one call", sl);
+            seen[(size_t)sl] = 1;
+        }
+    }
+    const size_t need = parq_tracks_update_workspace_bytes(B, Q, max_tracks);
+    if (workspace_bytes < need) return fail(PARQ_ERR_ARG, "parq_tracks_update: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 15) return fail(PARQ_ERR_ARG, "parq_tracks_update: the workspace must be 16-byte aligned");
+    for (int b0 = 0; b0 < B; b0 += kTrackChunk)
+        HIPCHK(launch_tracks_update(static_cast<int32_t*>(store), max_tracks, slots_host, b0, std::min(B - b0, (int)kTrackChunk), corners_world,
+                                    sem_cls_prob, pred_mask, Q, K, conf_thresh, iou_thresh, workspace, track_id, iou_out,
+                                    (hipStream_t)stream));
+    return PARQ_OK;
+}
+
 size_t parq_draw_boxes_workspace_bytes(int32_t B, int32_t T, int32_t M) {
     if (B < 1 || T < 1 || M < 0 || M > (1 << 24) || (int64_t)B * T > 65535) return 0;
     return draw_minmax_bytes(B, T) + (size_t)B * T * M * 12 * 8;

@@ -761,6 +761,15 @@ hipError_t launch_parse_pred(const float* center, const float* size, const float
 // obb_iou.hip: the tracker's oriented-box IoU, S segments of (n_a x n_b) pairs in one launch (total >= 1)
 hipError_t launch_obb_iou(const double* boxes_a, const double* boxes_b, const int64_t* seg, int S, int64_t total, int64_t n_a_total,
                           int64_t n_b_total, double* iou3, double* iou2, hipStream_t s);
+// tracks.hip: the rectangular assignment solver (one wave per segment, S >= 1, sides <= 2048; duals: S * (max_rows + max_cols) doubles)
+// and the device-resident track store's update for scenes [b0, b0 + nb) of a batch (nb <= kTrackChunk; three launches)
+constexpr int kTrackChunk = 64;
+hipError_t launch_assign_max(const float* m, int64_t m_total, const int64_t* seg, int S, int max_rows, int max_cols, double* duals,
+                             int32_t* row_to_col, int64_t out_total, hipStream_t s);
+size_t tracks_update_workspace_bytes(int B, int Q, int max_tracks);
+hipError_t launch_tracks_update(int32_t* store, int max_tracks, const int32_t* slots_host, int b0, int nb, const float* corners_world,
+                                const float* prob, const unsigned char* mask, int Q, int K, float conf, float iou_thresh, void* ws,
+                                int32_t* track_id, float* iou_out, hipStream_t s);
 // draw.hip: boxes drawn into the normalised views.  Workspace = the min / max parts (draw_minmax_bytes, a multiple of 16 bytes)
 // followed by the (B, T, M, 12) edge slots of 8 bytes each
 size_t draw_minmax_bytes(int B, int T);

@@ -311,6 +311,11 @@ class PARQDecoder(_Tracked, nn.Module):
     # device, one parq_obb_iou launch per step and per compute_metrics, instead of the host's pair-by-pair loop; same tracks and
     # metrics (parq_amd/f1_eval.py)
     metrics_on_device = False
+    # True (only read while metrics_on_device is on): the trackers keep their prediction tracks in a device-resident SceneTracks
+    # (parq_amd/scene_tracks.py), fed from the device tensors, so update_metrics no longer copies the outputs to the host; it still
+    # synchronises once per step for the ground truth, whose store stays on the host.  Same tracks and metrics; switch it between
+    # reset_metrics() and the first update_metrics(), not in mid-run (the two stores do not see each other).
+    tracks_on_device = False
     # True (on the class or on one module): log_images draws the predicted / ground-truth boxes of scene 0 into the RGB views on the
     # device (parq_amd/draw.py).  False: log_images returns {} and costs nothing, as before the drawing existed.
     draw_images = False
@@ -1661,7 +1666,23 @@ class PARQDecoder(_Tracked, nn.Module):
         out["pred_corners_world"] = Pose(raw(T_world_local)).transform(obbs.T_world_object.transform(obbs.bb3corners_object))
         for calc in self.metrics_calculator:
             calc.iou_device = obbs.device if self.metrics_on_device else None
+            calc.track_store = "device" if (self.metrics_on_device and self.tracks_on_device) else "host"
             calc.step(out, targets)
+
+    @torch.no_grad()
+    def track(self, out_dict, T_world_local, scene_name, tracks):
+        """Follow this snippet batch's detections in ``tracks`` (a ``parq_amd.SceneTracks``): ``parse_pred``, the box corners in
+        world coordinates exactly as ``update_metrics`` builds them, then ``tracks.update``.  Adds ``pred_corners_world`` and
+        ``track_id`` ((B,Q) int32 on the device: the object id of each kept detection, -1 for the other queries, -2 where the store
+        was full) next to ``pred_mask`` in the last iteration's dict and returns it.  Needs no ground truth, copies nothing to the
+        host and does not synchronise; under ``InFlight`` a deferred range check is settled first, as before the loss."""
+        from .wrappers import Pose, raw
+        self.settle_deferred()
+        out = self.parse_pred(out_dict)
+        obbs = out["obbs_pred"]
+        out["pred_corners_world"] = Pose(raw(T_world_local)).transform(obbs.T_world_object.transform(obbs.bb3corners_object))
+        out["track_id"] = tracks.update(scene_name, out["pred_corners_world"], out["sem_cls_prob"], out["pred_mask"])
+        return out
 
     def log_images(self, out_dict, obbs_padded, Ts_world_pseudoCam, Ts_world_local, T_camera_pseudoCam, rgb_img=None, calib_rgb=None,
                    slaml_img=None, calib_slaml=None, slamr_img=None, calib_slamr=None):
@@ -1707,6 +1728,7 @@ class PARQDecoder(_Tracked, nn.Module):
                 calc.iou_device = None
             elif calc.iou_device is None:                              # no update_metrics yet in this mode: the module's device
                 calc.iou_device = next(self.parameters()).device
+            calc.track_store = "device" if (self.metrics_on_device and self.tracks_on_device) else "host"
             metrics.update(calc.compute_metrics())
         return metrics
 

@@ -12,8 +12,11 @@ snippet's 30 detections x 80 tracks cost a quarter of a second, two orders of ma
 takes the matrices from ``parq_obb_iou`` instead (csrc/obb_iou.hip: the same routine in float64, one lane per pair): ``step``
 packs the (detections, tracks) pairs of every scene of the batch, predictions and ground truth together, into one launch, and
 ``compute_metrics`` all scenes' prediction x ground-truth pairs into one that every threshold reads.  ``iou_device=None`` (the
-default) is the host loop.  The device side of the rest of the evaluation path (box building, validity window, NMS) is
-``PARQDecoder.parse_pred``.
+default) is the host loop.  With ``track_store="device"`` on top of ``iou_device`` the prediction tracks do not live here at all
+but in a ``SceneTracks`` (parq_amd/scene_tracks.py): ``step`` hands it the outputs as device tensors in one enqueue, nothing of the
+predictions is copied to the host, and ``compute_metrics`` reads the tracks back once.  The ground-truth store stays on the host
+(its jitter draws from NumPy's generator box by box), so ``step`` still synchronises once for the ground truth.  The device side
+of the rest of the evaluation path (box building, validity window, NMS) is ``PARQDecoder.parse_pred``.
 
 The oriented IoU follows the reference's convention (utils/f1_eval.py:46-48,77-107): corners are re-ordered with
 [4,0,1,5,7,3,2,6] and rotated by +90 deg about x, the first four re-ordered corners (taken in reverse) are the footprint
@@ -273,9 +276,20 @@ class F1Calculator:
 
     ``iou_device``: None (default) fills every IoU matrix on the host, pair by pair; a CUDA device makes ``step`` and
     ``compute_metrics`` take them from one ``parq_obb_iou`` launch each (see the module docstring).  ``iou_backend``: any
-    callable [(A, B) canonical corner stacks] -> [float64 (n_a, n_b)] to run the batched path on instead (``host_iou_backend``)."""
+    callable [(A, B) canonical corner stacks] -> [float64 (n_a, n_b)] to run the batched path on instead (``host_iou_backend``).
+    ``track_store``: "host" (default), or "device" (needs ``iou_device``): the prediction tracks live in a ``SceneTracks`` of
+    ``track_capacity`` tracks per scene and ``preds`` is filled from it by ``compute_metrics`` (or ``pull_tracks``)."""
 
-    def __init__(self, conf_thresh, f1_iou_thresh=(0.25, 0.5, 0.7), verbose=False, iou_device=None, iou_backend=None):
+    track_capacity = 2048
+
+    def __init__(self, conf_thresh, f1_iou_thresh=(0.25, 0.5, 0.7), verbose=False, iou_device=None, iou_backend=None,
+                 track_store="host"):
+        if track_store not in ("host", "device"):
+            raise ValueError("track_store must be 'host' or 'device', got %r" % (track_store,))
+        if track_store == "device" and iou_device is None:
+            raise ValueError("track_store='device' needs iou_device (a CUDA device)")
+        self.track_store = track_store
+        self._tracks = None
         self.f1_iou_thresh = list(f1_iou_thresh)
         self.conf_thresh = conf_thresh
         self.iou_thresh = 0.1
@@ -301,14 +315,47 @@ class F1Calculator:
     def reset(self):
         self.preds = {}
         self.gts = {}
+        if getattr(self, "_tracks", None) is not None:
+            self._tracks.reset()
+
+    @property
+    def on_device_tracks(self):
+        return self.track_store == "device" and self._iou_device is not None
+
+    def _device_tracks(self, num_classes):
+        if self._tracks is None:
+            from .scene_tracks import SceneTracks
+            if num_classes != _NON_OBJECT + 1:
+                raise ValueError("the tracker's non-object class is %d: sem_cls_prob must have %d classes, got %d"
+                                 % (_NON_OBJECT, _NON_OBJECT + 1, num_classes))
+            self._tracks = SceneTracks(max_tracks=self.track_capacity, conf_thresh=self.conf_thresh, iou_thresh=self.iou_thresh,
+                                       num_classes=num_classes, device=self._iou_device)
+        return self._tracks
+
+    def pull_tracks(self):
+        """track_store="device": fill ``preds`` from the device store (one copy, synchronises); a full store is an error."""
+        if self._tracks is None:
+            return
+        lost = {n: k for n, k in self._tracks.dropped().items() if k}
+        if lost:
+            raise RuntimeError("F1Calculator: the device track store (track_capacity = %d per scene) dropped detections: %r"
+                               % (self.track_capacity, lost))
+        self.preds = self._tracks.to_host()
 
     # ---- one snippet batch ------------------------------------------------------------------------------------------
     def step(self, outputs, gt_list):
         """outputs: {"pred_corners_world" (B,Q,8,3), "sem_cls_prob" (B,Q,K), "pred_mask" (B,Q), "scene_name" [B]};
         gt_list: per scene {"labels" (n,), "gt_corners_world" (n,8,3)} (utils/f1_eval.py:277-291)."""
+        names = outputs["scene_name"]
+        if self.on_device_tracks:
+            import torch
+            dev = torch.device(self._iou_device)
+            corners, prob, mask = (torch.as_tensor(getattr(outputs[k], "_data", outputs[k])).to(dev)
+                                   for k in ("pred_corners_world", "sem_cls_prob", "pred_mask"))
+            self._device_tracks(prob.shape[-1]).update(names, corners, prob, mask)
+            return self._step_batched([], self.make_gt_list(gt_list), names)
         dets = self.parse_predictions(outputs, self.conf_thresh)
         gts = self.make_gt_list(gt_list)
-        names = outputs["scene_name"]
         if self.iou_backend is not None:
             return self._step_batched(dets, gts, names)
         self.matching_pred(dets, names)
@@ -412,6 +459,8 @@ class F1Calculator:
 
     def compute_metrics(self):
         metrics = {}
+        if self.on_device_tracks:
+            self.pull_tracks()
         ious = self.scene_ious() if self.iou_backend is not None else None           # every threshold reads the same matrices
         for thr in self.f1_iou_thresh:
             gts, preds, tps = self.counts(thr, ious)
