@@ -873,7 +873,7 @@ int do_iterate(parq_ctx* c, const parq_scene* sc, float* wsp, const Workspace& w
                     const int cus = device_num_cus();
                     f8.nsplit = flash_split_pick_splits(inv ? 1 : B, f8.nh, Q, (int)N, cus);
                     f3.nsplit = flash_split_pick_splits(inv ? 1 : B, f3.nh, Q, (int)N, cus);
-                    f8.cache_head_bytes = f3.cache_head_bytes = (int64_t)kvsplit_cache_bytes(1, 1, (int)N, 3);
+                    f8.cache_head_bytes = f3.cache_head_bytes = kv_blk_head_bytes((int)N, 3);
                     f8.m_part = f8.o_part + (int64_t)B * f8.nh * f8.nsplit * dh * lp;
                     f8.l_part = f8.m_part + (int64_t)B * f8.nh * f8.nsplit * lp;
                     f3.o_part = f8.l_part + (int64_t)B * f8.nh * f8.nsplit * lp;
@@ -1832,18 +1832,17 @@ int parq_attention_map(parq_handle h, const parq_scene* scene, const void* works
     if (h->cache_mode()) {
         // the layer's cache, read as the forward's cross-attention reads it (do_iterate)
         a.kbase = reinterpret_cast<const char*>(wsp + ws.kvc) + (size_t)r.li * kvsplit_cache_bytes(B, h->vheads(), N, h->terms());
-        const int nblk = (N + 31) / 32;
         // (the head tiers the cache was WRITTEN under, which a guard may have changed on the handle since: ctx terms_for with r.safe)
         const bool m4 = h->attn_mode == 4 && C == 256 && flash_split8_supported(h->dh, N);
         const int tf = (m4 && r.safe != h->all_heads()) ? 8 : h->terms();
         if (tf == 8) {
             a.klayout = kMapStage8;
             a.safe_mask = r.safe;
-            a.head_bytes = a.safe_mask ? (int64_t)kvsplit_cache_bytes(1, 1, N, 3) : (int64_t)(N / 64) * kStage8Bytes;
+            a.head_bytes = a.safe_mask ? kv_blk_head_bytes(N, 3) : kv_stage_head_bytes(N);
         } else if (tf == 3) {
-            a.klayout = kMapSplit3; a.head_bytes = (int64_t)nblk * 16384;
+            a.klayout = kMapSplit3; a.head_bytes = kv_blk_head_bytes(N, 3);
         } else {
-            a.klayout = h->kind() == kBF16 ? kMapBF16 : kMapF16; a.head_bytes = (int64_t)nblk * 8192;
+            a.klayout = h->kind() == kBF16 ? kMapBF16 : kMapF16; a.head_bytes = kv_blk_head_bytes(N, 1);
         }
     } else {
         a.klayout = kMapF32;

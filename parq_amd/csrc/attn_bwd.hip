@@ -43,7 +43,7 @@ struct AttnBwdArgs {
     int64_t q_off[kMaxBwdIters], lse_off[kMaxBwdIters];
     uint32_t seeds[kMaxBwdIters];
     unsigned int* kv_absmax;   // optional: atomicMax of the bit pattern of |dK|, |dV| as written (scale of the projection backward)
-    // split kernel, second version: K / V straight from the forward's 16-bit cache (flash_split.hip layout: 32-key blocks
+    // split kernel, second version: K / V straight from the forward's 16-bit cache (kv_layout.hpp: 32-key blocks
     // [K_hi | K_lo | V_hi | V_lo], or [K | V] in the single-product modes) instead of fp32 k / v rebuilt from it
     const _Float16* kvcache;
     int cache_kind;            // kF16 / kBF16 of a single-product cache
@@ -715,20 +715,20 @@ __device__ __forceinline__ void attn_bwd_split2_block(const AttnBwdArgs& a, cons
     // ---- K, V of this lane's key as B fragments: step t holds d = 16 t + 8 kh + e; K also goes into LDS (natural layout)
     half8 kfh[4], kfl[4], vfh[4], vfl[4];
     if constexpr (CACHE == 8) {
-        // the forward's mode-4 stage cache (flash_split8.hip; 64 keys = 24 KB: K hi16 | K hi8 | K lo8 | V fp16): this wave's 32 keys are
+        // the forward's mode-4 stage cache (kv_layout.hpp; 64 keys = 24 KB: K hi16 | K hi8 | K lo8 | V fp16): this wave's 32 keys are
         // block blk & 1 of stage blk >> 1.  K = hi16 + e4m3 lo 2^-10 (what the forward's scores saw, to its 15 bits), V = the fp16 value
         // (what the forward multiplied: the gradient goes straight through the rounding, as in the single-product modes).
         // K hi16 / V planes: the layouts of the split cache's K_hi / V_hi blocks.  K lo8: piece (c, h) of a key holds byte 8 m + e' <->
-        // d = 32 m + 16 c + 4 h + (e' & 3) + 8 (e' >> 2); element e of fragment t (d = 16 t + 8 kh + e) is byte 8 (t >> 1) + 4 kh + (e & 3)
+        // d = kv_dmap(h, 2 m + c, e'); element e of fragment t (d = 16 t + 8 kh + e) is byte 8 (t >> 1) + 4 kh + (e & 3)
         // of piece (c = t & 1, h = e >> 2).
         const int nblk = (a.Lk + 31) >> 5;
         int blk = kbx * (kSpKW / 32) + wave;
         blk = blk < nblk ? blk : nblk - 1;
         const unsigned char* stage = reinterpret_cast<const unsigned char*>(a.kvcache) + ((int64_t)bh * (nblk >> 1) + (blk >> 1)) * kStage8Bytes;
         const int b2 = blk & 1;
-        const _Float16* kb = reinterpret_cast<const _Float16*>(stage + kS8Kh16 + b2 * 4096);
-        const _Float16* vb = reinterpret_cast<const _Float16*>(stage + kS8Vh16 + b2 * 4096);
-        const int ksw = (li >> 1) & 7;
+        const _Float16* kb = reinterpret_cast<const _Float16*>(stage + kS8Kh16 + b2 * kS8Blk16Bytes);
+        const _Float16* vb = reinterpret_cast<const _Float16*>(stage + kS8Vh16 + b2 * kS8Blk16Bytes);
+        const int ksw = kv_kswz(li, 0);                  // this lane's key row: chunk c sits at position c ^ ksw
         const int vr = li & 15, vc = 2 * (li >> 4) + ((vr & 7) >> 2), ve = (vr & 3) + 4 * (vr >> 3);
         const half8 zero8 = half8{0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -738,7 +738,7 @@ __device__ __forceinline__ void attn_bwd_split2_block(const AttnBwdArgs& a, cons
             half8 lo8;
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
-                const int w = *reinterpret_cast<const int*>(stage + kS8K8lo + (((b2 * 2 + (t & 1)) * 2 + hh) * 32 + li) * 16 + 8 * (t >> 1) + 4 * kh);
+                const int w = *reinterpret_cast<const int*>(stage + kS8K8lo + kv_piece8(b2, t & 1, hh, li) * kS8PieceBytes + 8 * (t >> 1) + 4 * kh);
                 lo8[4 * hh + 0] = (_Float16)(__builtin_amdgcn_cvt_f32_fp8(w, 0) * (1.f / kLo8Scale));
                 lo8[4 * hh + 1] = (_Float16)(__builtin_amdgcn_cvt_f32_fp8(w, 1) * (1.f / kLo8Scale));
                 lo8[4 * hh + 2] = (_Float16)(__builtin_amdgcn_cvt_f32_fp8(w, 2) * (1.f / kLo8Scale));
@@ -749,7 +749,7 @@ __device__ __forceinline__ void attn_bwd_split2_block(const AttnBwdArgs& a, cons
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int d = 16 * t + 8 * kh + e;
-                vh8[e] = vb[d * 32 + ((vc ^ ((d >> 2) & 3)) << 3) + ve];
+                vh8[e] = vb[d * 32 + (kv_vswz(d, vc) << 3) + ve];
             }
             vfh[t] = vh8;
             vfl[t] = zero8;
@@ -759,16 +759,16 @@ __device__ __forceinline__ void attn_bwd_split2_block(const AttnBwdArgs& a, cons
             *reinterpret_cast<half8*>(Ki + 16384 + off) = kfl[t];
         }
     } else if constexpr (CACHE != 0) {
-        // this wave's 32 keys are ONE cache block (key li of block 8 blockIdx.x + wave).  K_x: [32 keys][8 chunks][8]; chunk 4 kh' + s
-        // holds d = 32 (s >> 1) + 16 (s & 1) + 4 kh' + (e & 3) + 8 (e >> 2), stored at chunk position c ^ ((key >> 1) & 7): the eight
-        // d = 16 t + 8 kh + e of fragment t are elements 4 kh .. 4 kh + 3 of chunks t (e < 4) and 4 + t (e >= 4).  V_x: [64 d][4 chunks][8];
-        // chunk 2 m + kh'' holds keys 16 m + 4 kh'' + (e & 3) + 8 (e >> 2) at position c ^ ((d >> 2) & 3): one 16-bit element per d.
-        constexpr int kBH = CACHE == 3 ? 8192 : 4096, kVo = CACHE == 3 ? 4096 : 2048;
+        // this wave's 32 keys are ONE cache block (key li of block 8 blockIdx.x + wave; layout: kv_layout.hpp).  K plane: chunk 4 kh' + s
+        // holds d = kv_dmap(kh', s, e) at chunk position kv_kswz(key, c): the eight d = 16 t + 8 kh + e of fragment t are elements
+        // 4 kh .. 4 kh + 3 of chunks t (e < 4) and 4 + t (e >= 4).  V plane: chunk 2 m + kh'' holds keys kv_kmap(m, kh'', e) at position
+        // kv_vswz(d, c): one 16-bit element per d.
+        typedef KvBlk<CACHE> Bk;
         const int nblk = (a.Lk + 31) >> 5;
         int blk = kbx * (kSpKW / 32) + wave;
         blk = blk < nblk ? blk : nblk - 1;                         // past the end: any valid block (masked by jok below)
-        const _Float16* cb = a.kvcache + ((int64_t)bh * nblk + blk) * kBH;
-        const int ksw = (li >> 1) & 7;
+        const _Float16* cb = a.kvcache + ((int64_t)bh * nblk + blk) * Bk::halfs;
+        const int ksw = kv_kswz(li, 0);                  // this lane's key row: chunk c sits at position c ^ ksw
         const int vr = li & 15, vc = 2 * (li >> 4) + ((vr & 7) >> 2), ve = (vr & 3) + 4 * (vr >> 3);
         const half8 zero8 = half8{0, 0, 0, 0, 0, 0, 0, 0};
         auto widen = [&](half8 raw, half8& hi, half8& lo) {          // single-product cache: the 16-bit value is the operand
@@ -786,14 +786,14 @@ __device__ __forceinline__ void attn_bwd_split2_block(const AttnBwdArgs& a, cons
             const int o0 = li * 64 + ((t ^ ksw) << 3) + 4 * kh, o1 = li * 64 + (((4 + t) ^ ksw) << 3) + 4 * kh;
             half8 kh8 = cat4(*reinterpret_cast<const half4v*>(cb + o0), *reinterpret_cast<const half4v*>(cb + o1));
             half8 kl8 = zero8;
-            if constexpr (CACHE == 3) kl8 = cat4(*reinterpret_cast<const half4v*>(cb + 2048 + o0), *reinterpret_cast<const half4v*>(cb + 2048 + o1));
+            if constexpr (CACHE == 3) kl8 = cat4(*reinterpret_cast<const half4v*>(cb + Bk::k_lo + o0), *reinterpret_cast<const half4v*>(cb + Bk::k_lo + o1));
             half8 vh8, vl8 = zero8;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int d = 16 * t + 8 * kh + e;
-                const int ov = kVo + d * 32 + ((vc ^ ((d >> 2) & 3)) << 3) + ve;
+                const int ov = Bk::v_hi + d * 32 + (kv_vswz(d, vc) << 3) + ve;
                 vh8[e] = cb[ov];
-                if constexpr (CACHE == 3) vl8[e] = cb[2048 + ov];
+                if constexpr (CACHE == 3) vl8[e] = cb[Bk::v_lo - Bk::v_hi + ov];
             }
             widen(kh8, kfh[t], kl8);
             if constexpr (CACHE == 3) kfl[t] = kl8; else kfl[t] = kl8;

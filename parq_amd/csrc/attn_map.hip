@@ -18,7 +18,7 @@
 //
 // Scores: the fp16 x 3 product of flash_split.hip (q_hi k_hi + q_hi k_lo + q_lo k_hi, v_mfma_f32_32x32x16_f16, fp32 accumulation).
 // K fragments come straight from global memory: in the cache layouts a lane's 8 contraction elements are one 16-byte chunk of the
-// block (flash_split.hip header), so there is no LDS stage and no barrier; the contraction order over d is the cache's (dmap), and
+// block (kv_layout.hpp), so there is no LDS stage and no barrier; the contraction order over d is the cache's (kv_dmap), and
 // phase 0 orders q the same way.  Per layout (a head of "split8" with tiers is read in the layout ITS region has):
 //   fp32 K (mode 0, head dims without a cache)   split in registers, d in natural order
 //   split cache                                  hi, lo as stored
@@ -40,8 +40,6 @@ constexpr int kViewSegKeys = 256;                   // keys of one view-mass seg
 // 0.618 / 0.770 — more blocks reuse the q fragments but cost registers (three waves per SIMD at 1), and the kernel lives on waves in
 // flight, not on reuse
 
-__device__ __forceinline__ int dmap(int kh, int s, int e) { return 32 * (s >> 1) + 16 * (s & 1) + 4 * kh + (e & 3) + 8 * (e >> 2); }
-
 __device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 struct KHead { const char* p; int lay; };
@@ -61,7 +59,7 @@ __device__ __forceinline__ KHead k_head(const AttnMapArgs& a, int b, int h, int 
 // kernels several times larger than the instruction cache)
 template <int LAY>
 __device__ __forceinline__ void load_kfrag(const KHead& k, const AttnMapArgs& a, int blk, int key, int kh, int s, half8& hi, half8& lo) {
-    const int pos = ((4 * kh + s) ^ ((key >> 1) & 7)) * 8 + key * 64;      // 16-bit units inside a K plane of the cache layouts
+    const int pos = kv_kswz(key, 4 * kh + s) * 8 + key * 64;      // 16-bit units inside a K plane of the cache layouts
     if constexpr (LAY == kMapF32) {
         int64_t n = (int64_t)blk * 32 + key;
         n = n < a.N ? n : a.N - 1;
@@ -70,15 +68,15 @@ __device__ __forceinline__ void load_kfrag(const KHead& k, const AttnMapArgs& a,
         const float x[8] = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
         split8(x, hi, lo);
     } else if constexpr (LAY == kMapSplit3) {
-        const _Float16* p = reinterpret_cast<const _Float16*>(k.p + (int64_t)blk * 16384);
+        const _Float16* p = reinterpret_cast<const _Float16*>(k.p + (int64_t)blk * KvBlk<3>::bytes);
         hi = *reinterpret_cast<const half8*>(p + pos);
-        lo = *reinterpret_cast<const half8*>(p + 2048 + pos);
+        lo = *reinterpret_cast<const half8*>(p + KvBlk<3>::k_lo + pos);
     } else if constexpr (LAY == kMapF16) {
-        const _Float16* p = reinterpret_cast<const _Float16*>(k.p + (int64_t)blk * 8192);
+        const _Float16* p = reinterpret_cast<const _Float16*>(k.p + (int64_t)blk * KvBlk<1>::bytes);
         hi = *reinterpret_cast<const half8*>(p + pos);
         lo = half8{0, 0, 0, 0, 0, 0, 0, 0};
     } else if constexpr (LAY == kMapBF16) {
-        const _Float16* p = reinterpret_cast<const _Float16*>(k.p + (int64_t)blk * 8192);
+        const _Float16* p = reinterpret_cast<const _Float16*>(k.p + (int64_t)blk * KvBlk<1>::bytes);
         const u32x4 raw = *reinterpret_cast<const u32x4*>(p + pos);
         float x[8];
         widen8<kTokBF16>(raw, x);
@@ -86,10 +84,10 @@ __device__ __forceinline__ void load_kfrag(const KHead& k, const AttnMapArgs& a,
     } else {        // kMapStage8: a 64-key stage holds two blocks
         const char* st = k.p + (int64_t)(blk >> 1) * kStage8Bytes;
         const int b2 = blk & 1;
-        hi = *reinterpret_cast<const half8*>(st + kS8Kh16 + b2 * 4096 + pos * 2);
-        // piece (b2, c = s & 1, kh) of the key, bytes 8 (s >> 1) .. + 7: d = 32 (s >> 1) + 16 (s & 1) + 4 kh + (e & 3) + 8 (e >> 2) = dmap
-        const int piece = ((b2 * 2 + (s & 1)) * 2 + kh) * 32 + key;
-        const uint2 w = *reinterpret_cast<const uint2*>(st + kS8K8lo + piece * 16 + 8 * (s >> 1));
+        hi = *reinterpret_cast<const half8*>(st + kS8Kh16 + b2 * kS8Blk16Bytes + pos * 2);
+        // piece (b2, c = s & 1, kh) of the key, bytes 8 (s >> 1) .. + 7: d = kv_dmap(kh, s, e)
+        const int piece = kv_piece8(b2, s & 1, kh, key);
+        const uint2 w = *reinterpret_cast<const uint2*>(st + kS8K8lo + piece * kS8PieceBytes + 8 * (s >> 1));
         const auto f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, false), f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, true);
         const auto f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, false), f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, true);
         constexpr float inv = 1.f / kLo8Scale;      // e4m3 x 2^-10: at most 4 significant bits, >= 2^-19 — exact in fp16
@@ -126,7 +124,7 @@ __global__ __launch_bounds__(64) void attn_map_qfrag_kernel(AttnMapArgs a, const
         float x[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const int d = a.klayout == kMapF32 ? 16 * s + 8 * kh + e : 64 * (s >> 2) + dmap(kh, s & 3, e);
+            const int d = a.klayout == kMapF32 ? 16 * s + 8 * kh + e : 64 * (s >> 2) + kv_dmap(kh, s & 3, e);
             x[e] = src < 0 ? 0.f : qp[d];
         }
         half8 hi, lo;

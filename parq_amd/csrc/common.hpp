@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <stdlib.h>
+#include "kv_layout.hpp"      // mfma32_row and the K/V cache layouts: block / stage geometry, index maps, swizzles
 
 namespace parq {
 
@@ -146,6 +147,29 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
+// Cross-half reductions of the attention kernels (a query's 32 scores of a block sit in lanes l and l + 32).
+// v_permlane32_swap exchanges lanes 32..63 of its first operand with lanes 0..31 of its second: fed the same value twice, the first
+// comes back as the low half broadcast to both halves and the second as the high half.  Written as inline asm: with hipcc of
+// ROCm 7.2 the SECOND result of __builtin_amdgcn_permlane32_swap is mis-assigned to the first result's register ("r[0] + r[1]"
+// compiled to v0 + v0 even for unrelated inputs: the row sums came out doubled).  s_nop: VALU write -> permlane read hazard.
+__device__ __forceinline__ void xhalf_swap(float v, float& lo_bcast, float& hi_bcast) {
+    float a = v, b = v;
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    lo_bcast = a;
+    hi_bcast = b;
+}
+__device__ __forceinline__ float xhalf_max(float v) {       // max over the two 32-lane halves, result in every lane
+    float a, b, o;
+    xhalf_swap(v, a, b);
+    asm("v_max_f32 %0, %1, %2" : "=v"(o) : "v"(a), "v"(b));
+    return o;
+}
+__device__ __forceinline__ float xhalf_sum(float v) {
+    float a, b;
+    xhalf_swap(v, a, b);
+    return a + b;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: a process that drives several GPUs must set
 // it on each of them.  One static instance per kernel; bit d of `done` = already set on device ordinal d.
 struct DynLdsOnce {
@@ -164,12 +188,6 @@ struct DynLdsOnce {
 
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// Row of a 32x32 MFMA C/D tile held in register `reg` of lane `lane`
-// (col = lane & 31):  row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
-__device__ __forceinline__ int mfma32_row(int reg, int lane) {
-    return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-}
 
 // ------------------------------------------------------------------ fp32 -> (hi, lo) fp16 split
 // x ~= hi + lo with hi = fp16(x) and lo = fp16(x - hi).  `hi` MUST be the value the residual is
@@ -234,10 +252,6 @@ __device__ __forceinline__ void pieces_e4m3(const float* x, i32x4& hi8, i32x4& l
         lo8[w] = pack4_e4m3<CLAMP>(d[0] * kLo8Scale, d[1] * kLo8Scale, d[2] * kLo8Scale, d[3] * kLo8Scale);
     }
 }
-// byte offsets inside a 64-key stage of the mode-4 cache (layout: flash_split8.hip): K as hi16 + e4m3 hi8 + e4m3 lo8, V as fp16 (round to
-// nearest): 24 KB per stage, 3 bytes per element
-constexpr int kStage8Bytes = 24576;
-constexpr int kS8Kh16 = 0, kS8K8hi = 8192, kS8K8lo = 12288, kS8Vh16 = 16384;
 
 // ---- dropout (training): counter-based keep decision, identical in forward and backward.  Element (row, col) of stream `seed`
 // is kept when a 24-bit hash is >= p * 2^24; kept values are scaled by 1 / (1 - p) (torch.nn.Dropout semantics).

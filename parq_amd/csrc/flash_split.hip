@@ -9,46 +9,20 @@
 // so the kernel moves from the fp32-MFMA roof (157 TF) towards the HBM roof of streaming
 // the K/V cache.  Range: |x| < 65504 (checked when the cache is built).
 //
-// K/V cache layout ("fragment-ready", written by kvsplit_convert_kernel or directly by the
-// K/V projection GEMM): per (scene, head) a sequence of 32-key blocks of 16 KB
-//     [K_hi 4 KB][K_lo 4 KB][V_hi 4 KB][V_lo 4 KB]
-//   K_x : [32 keys][8 chunks][8 fp16]; chunk c = 4*kh + s holds d = dmap(kh,s,e), stored at chunk
-//         position c ^ ((key>>1)&7)                    (conflict-free ds_read_b128 across keys)
-//   V_x : [64 d][4 chunks][8 fp16];  chunk c = 2*m + kh holds keys kmap(m,kh,e), stored at chunk
-//         position c ^ ((d>>2)&3)
-//   dmap(kh,s,e) = 32*(s>>1) + 16*(s&1) + 4*kh + (e&3) + 8*(e>>2)
-//   kmap(m,kh,e) = 16*m + 4*kh + (e&3) + 8*(e>>2)
-// Both maps are the row enumeration of the 32x32 MFMA accumulator layout, so (a) the
-// projection GEMM can store its accumulators as 16-byte chunks without any shuffle, and (b) the
-// softmax probabilities (S^T accumulator registers) are directly the B operand of V^T P^T.
-// The LDS image of a block equals its global image: staging is a linear 16-byte copy.
+// K/V cache: the "fragment-ready" split cache (16 KB blocks [K_hi|K_lo|V_hi|V_lo] of 32 keys) or the one-term cache (8 KB blocks
+// [K|V]) of kv_layout.hpp, written by kvsplit_convert_kernel below or directly by the K/V projection GEMM.
 #include "common.hpp"
 #include <cstdlib>
 #include <type_traits>
 
 namespace parq {
 
-
 namespace {
 
-constexpr int kDH = 64;
-constexpr int kBlkKeys = 32;
-// cache block of 32 keys: TERMS = 3 -> [K_hi|K_lo|V_hi|V_lo] 16 KB; TERMS = 1 -> [K|V] 8 KB (offsets in 16-bit units)
-template <int TERMS>
-struct Blk {
-    static constexpr int bytes = TERMS == 3 ? 16384 : 8192;
-    static constexpr int halfs = bytes / 2;
-    static constexpr int k_lo = 2048;
-    static constexpr int v_hi = TERMS == 3 ? 4096 : 2048;
-    static constexpr int v_lo = 6144;
-};
+constexpr int kDH = kKvHeadDim, kBlkKeys = kKvBlkKeys;
 constexpr int kStageBlks = 2;                       // 64 keys per LDS stage
 constexpr int kNW = 8;                              // waves per workgroup (32 queries each)
 constexpr float kDeferLog2 = 10.f;                  // running max moves only past this margin (log2 domain)
-
-__device__ __forceinline__ int dmap(int kh, int s, int e) {
-    return 32 * (s >> 1) + 16 * (s & 1) + 4 * kh + (e & 3) + 8 * (e >> 2);
-}
 
 // ------------------------------------------------------------------------------------------------
 // fp32 head-major K/V ([b][h][n][64], as written by the fp32 projection) -> split cache.
@@ -78,7 +52,7 @@ __global__ __launch_bounds__(256) void kvsplit_convert_kernel(const float* __res
     }
     if (ovf) atomicOr(overflow, 1);
     __syncthreads();
-    _Float16* out = cache + ((int64_t)bh * nblk + blk) * Blk<TERMS>::halfs;
+    _Float16* out = cache + ((int64_t)bh * nblk + blk) * KvBlk<TERMS>::halfs;
     // K: 32 keys x 8 chunks = 256 chunks -> one per thread
     {
         const int key = threadIdx.x >> 3, c = threadIdx.x & 7;
@@ -86,12 +60,12 @@ __global__ __launch_bounds__(256) void kvsplit_convert_kernel(const float* __res
         half8 hi, lo;
         float x[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = ks[key][dmap(kh, s, e)];
-        const int pos = c ^ ((key >> 1) & 7);
+        for (int e = 0; e < 8; ++e) x[e] = ks[key][kv_dmap(kh, s, e)];
+        const int pos = kv_kswz(key, c);
         if constexpr (TERMS == 3) {
             split8(x, hi, lo);
             *reinterpret_cast<half8*>(out + key * 64 + pos * 8) = hi;
-            *reinterpret_cast<half8*>(out + Blk<3>::k_lo + key * 64 + pos * 8) = lo;
+            *reinterpret_cast<half8*>(out + KvBlk<3>::k_lo + key * 64 + pos * 8) = lo;
         } else {
             *reinterpret_cast<half8*>(out + key * 64 + pos * 8) = cvt8_rn<KIND>(x);
         }
@@ -103,14 +77,14 @@ __global__ __launch_bounds__(256) void kvsplit_convert_kernel(const float* __res
         half8 hi, lo;
         float x[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = vs[16 * m + 4 * kh + (e & 3) + 8 * (e >> 2)][d];
-        const int pos = c ^ ((d >> 2) & 3);
+        for (int e = 0; e < 8; ++e) x[e] = vs[kv_kmap(m, kh, e)][d];
+        const int pos = kv_vswz(d, c);
         if constexpr (TERMS == 3) {
             split8(x, hi, lo);
-            *reinterpret_cast<half8*>(out + Blk<3>::v_hi + d * 32 + pos * 8) = hi;
-            *reinterpret_cast<half8*>(out + Blk<3>::v_lo + d * 32 + pos * 8) = lo;
+            *reinterpret_cast<half8*>(out + KvBlk<3>::v_hi + d * 32 + pos * 8) = hi;
+            *reinterpret_cast<half8*>(out + KvBlk<3>::v_lo + d * 32 + pos * 8) = lo;
         } else {
-            *reinterpret_cast<half8*>(out + Blk<1>::v_hi + d * 32 + pos * 8) = cvt8_rn<KIND>(x);
+            *reinterpret_cast<half8*>(out + KvBlk<1>::v_hi + d * 32 + pos * 8) = cvt8_rn<KIND>(x);
         }
     }
 }
@@ -130,7 +104,7 @@ __global__ __launch_bounds__(256) void kvsplit_to_f32_kernel(const _Float16* __r
     const int b = bh / H, h = bh - b * H;
     const int nblk = (N + 31) / 32;
     const int row = 64 * chunks;
-    const _Float16* in = cache + ((int64_t)bh * nblk + blk) * Blk<TERMS>::halfs;
+    const _Float16* in = cache + ((int64_t)bh * nblk + blk) * KvBlk<TERMS>::halfs;
     auto val = [](half8 hi, half8 lo, int e) -> float {
         if constexpr (TERMS == 3) return (float)hi[e] + (float)lo[e];
         else if constexpr (KIND == kF16) return (float)hi[e];
@@ -140,13 +114,14 @@ __global__ __launch_bounds__(256) void kvsplit_to_f32_kernel(const _Float16* __r
     float* vp = V + (int64_t)b * v_batch + (int64_t)(h / chunks) * v_head + (h % chunks) * 64;
     {   // K: thread -> (key, stored chunk position)
         const int key = threadIdx.x >> 3, pos = threadIdx.x & 7;
+        // c = kv_kswz(key, pos) (kv_layout.hpp; its own inverse), written out: through the helper hipcc orders this kernel differently
         const int c = pos ^ ((key >> 1) & 7), kh = c >> 2, s2 = c & 3;
         const half8 hi = *reinterpret_cast<const half8*>(in + key * 64 + pos * 8);
         half8 lo = hi;
-        if constexpr (TERMS == 3) lo = *reinterpret_cast<const half8*>(in + Blk<3>::k_lo + key * 64 + pos * 8);
+        if constexpr (TERMS == 3) lo = *reinterpret_cast<const half8*>(in + KvBlk<3>::k_lo + key * 64 + pos * 8);
         const int n = blk * 32 + key;
         if (n < N) {
-            const int d0 = 32 * (s2 >> 1) + 16 * (s2 & 1) + 4 * kh;
+            const int d0 = kv_dmap(kh, s2, 0);                         // elements 0..3 at d0, 4..7 at d0 + 8
             float4 a = {val(hi, lo, 0), val(hi, lo, 1), val(hi, lo, 2), val(hi, lo, 3)};
             float4 c4 = {val(hi, lo, 4), val(hi, lo, 5), val(hi, lo, 6), val(hi, lo, 7)};
             *reinterpret_cast<float4*>(kp + (int64_t)n * row + d0) = a;
@@ -155,13 +130,13 @@ __global__ __launch_bounds__(256) void kvsplit_to_f32_kernel(const _Float16* __r
     }
     {   // V: thread -> (d, stored chunk position)
         const int d = threadIdx.x >> 2, pos = threadIdx.x & 3;
-        const int c = pos ^ ((d >> 2) & 3), m = c >> 1, kh = c & 1;
-        const half8 hi = *reinterpret_cast<const half8*>(in + Blk<TERMS>::v_hi + d * 32 + pos * 8);
+        const int c = kv_vswz(d, pos), m = c >> 1, kh = c & 1;
+        const half8 hi = *reinterpret_cast<const half8*>(in + KvBlk<TERMS>::v_hi + d * 32 + pos * 8);
         half8 lo = hi;
-        if constexpr (TERMS == 3) lo = *reinterpret_cast<const half8*>(in + Blk<3>::v_lo + d * 32 + pos * 8);
+        if constexpr (TERMS == 3) lo = *reinterpret_cast<const half8*>(in + KvBlk<3>::v_lo + d * 32 + pos * 8);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const int n = blk * 32 + 16 * m + 4 * kh + (e & 3) + 8 * (e >> 2);
+            const int n = blk * 32 + 16 * m + 4 * kh + (e & 3) + 8 * (e >> 2);      // blk * 32 + kv_kmap(m, kh, e), written out for the same reason
             if (n < N) vp[(int64_t)n * row + d] = val(hi, lo, e);
         }
     }
@@ -184,28 +159,7 @@ constexpr int kRing = 4;
 // softmax work of ANOTHER block to issue behind it (24 MFMAs : ~150 VALU, 6 per MFMA gap), consecutive MFMAs alternate between
 // the S^T accumulator and the two O^T accumulators (few back-to-back dependent pairs), the issue order is fixed by scheduling
 // fences (the sched_group_barrier pipeline was not honoured for this region), and the cross-half reductions use
-// v_permlane32_swap instead of ds_bpermute.  Same cache, same LDS ring / DMA protocol, same partial outputs.
-// v_permlane32_swap exchanges lanes 32..63 of its first operand with lanes 0..31 of its second: fed the same value twice, the first
-// comes back as the low half broadcast to both halves and the second as the high half.  Written as inline asm: with hipcc of
-// ROCm 7.2 the SECOND result of __builtin_amdgcn_permlane32_swap is mis-assigned to the first result's register ("r[0] + r[1]"
-// compiled to v0 + v0 even for unrelated inputs: the row sums came out doubled).  s_nop: VALU write -> permlane read hazard.
-__device__ __forceinline__ void xhalf_swap(float v, float& lo_bcast, float& hi_bcast) {
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    lo_bcast = a;
-    hi_bcast = b;
-}
-__device__ __forceinline__ float xhalf_max(float v) {       // max over the two 32-lane halves, result in every lane
-    float a, b, o;
-    xhalf_swap(v, a, b);
-    asm("v_max_f32 %0, %1, %2" : "=v"(o) : "v"(a), "v"(b));
-    return o;
-}
-__device__ __forceinline__ float xhalf_sum(float v) {
-    float a, b;
-    xhalf_swap(v, a, b);
-    return a + b;
-}
+// v_permlane32_swap instead of ds_bpermute (xhalf_max / xhalf_sum, common.hpp).  Same cache, same LDS ring / DMA protocol, same partial outputs.
 
 // The LDS ring has kRing = 4 slots of one 64-key stage each: a stage is requested one barrier before the barrier that publishes
 // it (three stages are live at any time: V of the previous block, K / V of the current pair, K of the next pair).  A five-slot
@@ -235,8 +189,8 @@ template <int PROBE = 0, int TERMS = 3, int KIND = kF16, bool DROP = false>
 __global__ __launch_bounds__(kNW * 64) void flash_split_pipe_kernel(FlashArgs a, const _Float16* __restrict__ cache) {
     PARQ_TL_KERNEL(kTlFlashSplit);
     extern __shared__ __attribute__((aligned(16))) _Float16 smem_h[];       // [kRing stages][kStageBlks][block]
-    constexpr int kBlkBytes = Blk<TERMS>::bytes;
-    constexpr int kBlkHalfs = Blk<TERMS>::halfs;
+    constexpr int kBlkBytes = KvBlk<TERMS>::bytes;
+    constexpr int kBlkHalfs = KvBlk<TERMS>::halfs;
     constexpr int NT = kNW * 64;
     constexpr int STAGE16 = kStageBlks * kBlkBytes / 16;
     constexpr int LD = STAGE16 / NT;
@@ -260,7 +214,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split_pipe_kernel(FlashArgs a,
         const float* qp = a.q + (int64_t)b * a.q_batch + (int64_t)h * a.q_head + (int64_t)(q < a.Lq ? q : 0) * a.q_row;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const int d0 = 32 * (s >> 1) + 16 * (s & 1) + 4 * kh;
+            const int d0 = kv_dmap(kh, s, 0);
             f32x4 x0 = *reinterpret_cast<const f32x4*>(qp + d0);
             f32x4 x1 = *reinterpret_cast<const f32x4*>(qp + d0 + 8);
             if (q >= a.Lq) { x0 = f32x4{0.f, 0.f, 0.f, 0.f}; x1 = x0; }
@@ -346,7 +300,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split_pipe_kernel(FlashArgs a,
     // to the running maximum (saves a v_sub per score); rewritten only when the reference moves
     f32x16 negm16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     half8 kf[8], vh[2], vl[2];                                             // fragments of the NEXT step, requested at the end of a step
-    const int ksw = (li >> 1) & 7;
+    const int ksw = kv_kswz(li, 0);                                        // this lane's key row: chunk c sits at position c ^ ksw
 
     auto load_k = [&](const _Float16* Kb, half8 (&kf)[8]) {
         if constexpr (PROBE & 16) {
@@ -358,7 +312,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split_pipe_kernel(FlashArgs a,
         for (int s = 0; s < 4; ++s) {
             const int pos = (4 * kh + s) ^ ksw;
             kf[2 * s] = *reinterpret_cast<const half8*>(Kb + li * 64 + pos * 8);
-            if constexpr (TERMS == 3) kf[2 * s + 1] = *reinterpret_cast<const half8*>(Kb + Blk<3>::k_lo + li * 64 + pos * 8);
+            if constexpr (TERMS == 3) kf[2 * s + 1] = *reinterpret_cast<const half8*>(Kb + KvBlk<3>::k_lo + li * 64 + pos * 8);
         }
     };
     // chunks s = S0 .. S0 + 1 only (kf[2 S0] .. kf[2 S0 + 3])
@@ -369,7 +323,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split_pipe_kernel(FlashArgs a,
         for (int s = S0; s < S0 + 2; ++s) {
             const int pos = (4 * kh + s) ^ ksw;
             kf[2 * s] = *reinterpret_cast<const half8*>(Kb + li * 64 + pos * 8);
-            if constexpr (TERMS == 3) kf[2 * s + 1] = *reinterpret_cast<const half8*>(Kb + Blk<3>::k_lo + li * 64 + pos * 8);
+            if constexpr (TERMS == 3) kf[2 * s + 1] = *reinterpret_cast<const half8*>(Kb + KvBlk<3>::k_lo + li * 64 + pos * 8);
         }
     };
     auto load_v = [&](const _Float16* Vb, int m, half8 (&vh)[2], half8 (&vl)[2]) {
@@ -380,9 +334,9 @@ __global__ __launch_bounds__(kNW * 64) void flash_split_pipe_kernel(FlashArgs a,
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
             const int d = dt * 32 + li;
-            const int pos = (2 * m + kh) ^ ((d >> 2) & 3);
-            vh[dt] = *reinterpret_cast<const half8*>(Vb + Blk<TERMS>::v_hi + d * 32 + pos * 8);
-            if constexpr (TERMS == 3) vl[dt] = *reinterpret_cast<const half8*>(Vb + Blk<3>::v_lo + d * 32 + pos * 8);
+            const int pos = kv_vswz(d, 2 * m + kh);
+            vh[dt] = *reinterpret_cast<const half8*>(Vb + KvBlk<TERMS>::v_hi + d * 32 + pos * 8);
+            if constexpr (TERMS == 3) vl[dt] = *reinterpret_cast<const half8*>(Vb + KvBlk<3>::v_lo + d * 32 + pos * 8);
         }
     };
     // max of the 16 scores of this lane (keys of one kh half), then over both halves: the block maximum of query li
@@ -702,7 +656,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split_pipe_kernel(FlashArgs a,
 }  // namespace
 
 size_t kvsplit_cache_bytes(int B, int H, int N, int terms) {
-    return (size_t)B * H * ceil_div(N, kBlkKeys) * (terms == 3 ? Blk<3>::bytes : Blk<1>::bytes);
+    return (size_t)B * H * (size_t)kv_blk_head_bytes(N, terms);
 }
 
 int flash_split_stage_keys() { return kStageBlks * kBlkKeys; }
@@ -760,7 +714,7 @@ hipError_t launch_flash_split(const FlashArgs& a, const void* cache, hipStream_t
 #define PARQ_PIPE_LAUNCH(PROBE, T, K, D)                                                                                                 \
     {                                                                                                                                    \
         static DynLdsOnce once;                                                                                                          \
-        const size_t lds = (size_t)kRing * kStageBlks * Blk<T>::bytes + ((D) ? kNW * 32 * sizeof(uint32_t) : 0);                         \
+        const size_t lds = (size_t)kRing * kStageBlks * KvBlk<T>::bytes + ((D) ? kNW * 32 * sizeof(uint32_t) : 0);                       \
         if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&flash_split_pipe_kernel<PROBE, T, K, D>), lds); e != hipSuccess) return e; \
         hipLaunchKernelGGL((flash_split_pipe_kernel<PROBE, T, K, D>), grid, dim3(kNW * 64), lds, s, b, c16);                             \
         return hipGetLastError();                                                                                                        \

@@ -30,12 +30,10 @@ namespace {
 constexpr int kDH = 256;
 constexpr int kChunks = 4;                          // 64-dim chunks per head
 constexpr int kNWconst = 8;
-// TERMS = 3 (split precision): one 16 KB cache block of a chunk is [K_hi | K_lo | V_hi | V_lo] x 2048 halfs, K (or V) of a stage is
-// [chunk][hi 2048 | lo 2048] halfs = 32 KB.  TERMS = 1 (single fp16 / bf16 products, KIND): blocks of 8 KB [K | V], 16 KB per stage.
+// Cache blocks of a chunk: KvBlk<TERMS> (kv_layout.hpp).  TERMS = 3 (split precision): K (or V) of a stage is [chunk][hi plane | lo plane]
+// = 32 KB.  TERMS = 1 (single fp16 / bf16 products, KIND): [chunk][plane], 16 KB per stage.
 template <int TERMS> struct Lay {
-    static constexpr int sub = TERMS == 3 ? 8192 : 4096;          // halfs per cache block of a chunk
-    static constexpr int xoff = TERMS == 3 ? 4096 : 2048;         // V offset inside a block
-    static constexpr int img = TERMS == 3 ? 4096 : 2048;          // halfs of one chunk's K (or V) image in the ring
+    static constexpr int img = (TERMS == 3 ? 2 : 1) * kKvPlaneHalfs;   // halfs of one chunk's K (or V) image in the ring
     static constexpr int grp = kChunks * img;                     // one ring slot
     static constexpr int ndma = grp * 2 / (kNWconst * 64 * 16);   // DMA instructions per thread and group (4 / 2)
 };
@@ -47,7 +45,7 @@ constexpr float kDeferLog2 = 10.f;
 template <bool DROP, int TERMS, int KIND>
 __global__ __launch_bounds__(kNW * 64) void flash_split256_kernel(FlashArgs a, const _Float16* __restrict__ cache) {
     typedef Lay<TERMS> L;
-    constexpr int kGrpHalfs = L::grp, kSubHalfs = L::sub, kImgH = L::img;
+    constexpr int kGrpHalfs = L::grp, kSubHalfs = KvBlk<TERMS>::halfs, kImgH = L::img;
     extern __shared__ __attribute__((aligned(16))) _Float16 smem_h[];
     _Float16* Kr = smem_h;                                   // [2][kGrpHalfs]
     _Float16* Vr = smem_h + 2 * kGrpHalfs;                   // [2][kGrpHalfs]
@@ -73,7 +71,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split256_kernel(FlashArgs a, c
         for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                const int d0 = 64 * cc + 32 * (s >> 1) + 16 * (s & 1) + 4 * kh;       // dmap(kh, s, e) of flash_split.hip inside the chunk
+                const int d0 = 64 * cc + kv_dmap(kh, s, 0);                            // elements 0..3 at d0, 4..7 at d0 + 8 inside chunk cc
                 f32x4 x0 = *reinterpret_cast<const f32x4*>(qp + d0);
                 f32x4 x1 = *reinterpret_cast<const f32x4*>(qp + d0 + 8);
                 if (q >= a.Lq) { x0 = f32x4{0.f, 0.f, 0.f, 0.f}; x1 = x0; }
@@ -99,7 +97,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split256_kernel(FlashArgs a, c
             // instruction c copies the 8 KB [hi | lo] of chunk c
 #pragma unroll
             for (int c = 0; c < kChunks; ++c) {
-                const _Float16* src = cbase + ((int64_t)c * nblk + t) * kSubHalfs + which * L::xoff + tid * 8;
+                const _Float16* src = cbase + ((int64_t)c * nblk + t) * kSubHalfs + which * KvBlk<TERMS>::v_hi + tid * 8;
                 lds_dma16(src, dst + (c * 512 + wave * 64) * 16);      // asm-issued: hipcc must not answer with vmcnt(0) before LDS reads
             }
         } else {
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split256_kernel(FlashArgs a, c
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int c = 2 * i + (tid >> 8), piece = tid & 255;
-                const _Float16* src = cbase + ((int64_t)c * nblk + t) * kSubHalfs + which * L::xoff + piece * 8;
+                const _Float16* src = cbase + ((int64_t)c * nblk + t) * kSubHalfs + which * KvBlk<TERMS>::v_hi + piece * 8;
                 lds_dma16(src, dst + (c * 256 + (piece >> 6) * 64) * 16);
             }
         }
@@ -135,7 +133,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split256_kernel(FlashArgs a, c
     wait_groups(t_begin + 1 < t_end ? 3 : 1);
     lds_barrier();
 
-    const int ksw = (li >> 1) & 7;
+    const int ksw = kv_kswz(li, 0);                             // this lane's key row: chunk c sits at position c ^ ksw
     for (int t = t_begin; t < t_end; ++t) {
         const int slot = (t - t_begin) & 1;
         const _Float16* Ks = Kr + slot * kGrpHalfs + (2 * half) * kImgH;         // this wave's two chunks: [cc][hi | lo]
@@ -156,7 +154,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split256_kernel(FlashArgs a, c
                     const half8 kfh = *reinterpret_cast<const half8*>(Ks + cc * kImgH + li * 64 + pos * 8);
                     sacc = mfma16<KIND>(kfh, qhi[cc][s], sacc);
                     if constexpr (TERMS == 3) {
-                        const half8 kfl = *reinterpret_cast<const half8*>(Ks + cc * kImgH + 2048 + li * 64 + pos * 8);
+                        const half8 kfl = *reinterpret_cast<const half8*>(Ks + cc * kImgH + kKvPlaneHalfs + li * 64 + pos * 8);
                         sacc = mfma16<KIND>(kfh, qlo[cc][s], sacc);
                         sacc = mfma16<KIND>(kfl, qhi[cc][s], sacc);
                     }
@@ -216,11 +214,11 @@ __global__ __launch_bounds__(kNW * 64) void flash_split256_kernel(FlashArgs a, c
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int cc = j >> 1, d = (j & 1) * 32 + li;
-                    const int pos = (2 * m + kh) ^ ((d >> 2) & 3);
+                    const int pos = kv_vswz(d, 2 * m + kh);
                     const half8 vh = *reinterpret_cast<const half8*>(Vs + cc * kImgH + d * 32 + pos * 8);
                     o[j] = mfma16<KIND>(vh, phi[m], o[j]);
                     if constexpr (TERMS == 3) {
-                        const half8 vl = *reinterpret_cast<const half8*>(Vs + cc * kImgH + 2048 + d * 32 + pos * 8);
+                        const half8 vl = *reinterpret_cast<const half8*>(Vs + cc * kImgH + kKvPlaneHalfs + d * 32 + pos * 8);
                         o[j] = mfma16<KIND>(vl, phi[m], o[j]);
                         o[j] = mfma16<KIND>(vh, plo[m], o[j]);
                     }

@@ -18,14 +18,8 @@
 // on zero operands, ~48 on random ones: tools/bench_src/mfma_operands.hip), the MX instruction at 36 ns for FOUR times the contraction
 // (tools/bench_src/mx_energy.hip).  Matrix work per 32-key block: 8 x 20 + 2 x 36 ns instead of 24 x 20.
 //
-// Cache ("stage" = 64 keys = 24 KB, the LDS image equals the global image; written by kvsplit8_convert_kernel or by the K/V
-// projection), byte offsets inside a stage:
-//       0  K hi16  [2 blocks][32 keys][8 chunks][8 fp16]     chunk swizzle and d order as in the split cache (flash_split.hip)
-//    8192  K hi8   [2 blocks][2 c][2 h][32 keys][16 B]       piece (c, h) of a key: byte 8 m + e <-> d = 32 m + 16 c + 4 h + (e & 3) + 8 (e >> 2)
-//   12288  K lo8   same, e4m3(lo 2^10)
-//   16384  V fp16  [2 blocks][64 d][4 chunks][8 fp16]        round to nearest; layout as the V_hi plane of the split cache
-// The fp8 byte order is the register order of the 32 x 32 accumulator map, so the K/V projection stores its accumulators as 16-byte
-// pieces.  MX operand semantics (lane l: row / column l & 31, 32 k-values; E8M0 scale byte per lane): tools/bench_src/mx_probe.hip.
+// Cache: the mode-4 "stage" cache of kv_layout.hpp (a stage = 64 keys = 24 KB: K hi16 | K hi8 | K lo8 | V fp16; the LDS image equals the
+// global image), written by kvsplit8_convert_kernel or by the K/V projection.
 // Whole stages only: Lk % 64 == 0 (the callers fall back to the fp16 x 3 kernel).
 #include "common.hpp"
 #include <cstdlib>
@@ -36,16 +30,11 @@ namespace parq {
 namespace {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kDH = 64, kNW = 8, kRing = 4;
-constexpr int kStageBytes = kStage8Bytes;
-constexpr int oKh16 = kS8Kh16, oK8hi = kS8K8hi, oK8lo = kS8K8lo, oVh16 = kS8Vh16;
+constexpr int kDH = kKvHeadDim, kNW = 8, kRing = 4;
 constexpr float kDefer8 = 2.f;                       // the reference maximum trails the row maximum by at most 2 (log2 domain): the row sums
                                                      // the peakedness guard reads stay within a factor 4 of the sums relative to the row maximum
 constexpr int kE8One = 127, kE8Lo = 117;             // E8M0 scales: 2^0, 2^-10 (lo parts of K, Q)
-
-__device__ __forceinline__ int dmap(int kh, int s, int e) { return 32 * (s >> 1) + 16 * (s & 1) + 4 * kh + (e & 3) + 8 * (e >> 2); }
 
 // ------------------------------------------------------------------------------------------------
 // fp32 head-major K / V -> stage cache.  One workgroup per (stage, b * h); tests and the stand-alone attention entry point.
@@ -66,58 +55,40 @@ __global__ __launch_bounds__(256) void kvsplit8_convert_kernel(const float* __re
         vs[key][d] = vp[n * v_row + d];
     }
     __syncthreads();
-    unsigned char* out = cache + ((int64_t)bh * nst + st) * kStageBytes;
+    unsigned char* out = cache + ((int64_t)bh * nst + st) * kStage8Bytes;
 #pragma unroll
     for (int b2 = 0; b2 < 2; ++b2) {
         {   // K hi16 (round toward zero: the value the lo part is taken against): 32 keys x 8 chunks
             const int key = tid >> 3, c = tid & 7, kh = c >> 2, s = c & 3;
             float x[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = ks[32 * b2 + key][dmap(kh, s, e)];
-            const int pos = c ^ ((key >> 1) & 7);
+            for (int e = 0; e < 8; ++e) x[e] = ks[32 * b2 + key][kv_dmap(kh, s, e)];
+            const int pos = kv_kswz(key, c);
             half8 hi, lo;
             split8(x, hi, lo);
-            *reinterpret_cast<half8*>(out + oKh16 + b2 * 4096 + (key * 64 + pos * 8) * 2) = hi;
+            *reinterpret_cast<half8*>(out + kS8Kh16 + b2 * kS8Blk16Bytes + (key * 64 + pos * 8) * 2) = hi;
         }
         {   // V fp16 (round to nearest): 64 d x 4 chunks
             const int d = tid >> 2, c = tid & 3, m = c >> 1, kh = c & 1;
             float x[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = vs[32 * b2 + 16 * m + 4 * kh + (e & 3) + 8 * (e >> 2)][d];
-            const int pos = c ^ ((d >> 2) & 3);
-            *reinterpret_cast<half8*>(out + oVh16 + b2 * 4096 + (d * 32 + pos * 8) * 2) = cvt8_rn<kF16>(x);
+            for (int e = 0; e < 8; ++e) x[e] = vs[32 * b2 + kv_kmap(m, kh, e)][d];
+            const int pos = kv_vswz(d, c);
+            *reinterpret_cast<half8*>(out + kS8Vh16 + b2 * kS8Blk16Bytes + (d * 32 + pos * 8) * 2) = cvt8_rn<kF16>(x);
         }
     }
-    {   // K hi8 / lo8: piece id = ((b2 * 2 + c) * 2 + h) * 32 + key = tid
+    {   // K hi8 / lo8: piece kv_piece8(b2, c, h, key) = tid
         const int b2 = tid >> 7, c = (tid >> 6) & 1, hh = (tid >> 5) & 1, key = tid & 31;
         float x[16];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x[8 * m + e] = ks[32 * b2 + key][32 * m + 16 * c + 4 * hh + (e & 3) + 8 * (e >> 2)];
+            for (int e = 0; e < 8; ++e) x[8 * m + e] = ks[32 * b2 + key][kv_dmap(hh, 2 * m + c, e)];
         i32x4 hi8, lo8;
         pieces_e4m3(x, hi8, lo8);
-        *reinterpret_cast<i32x4*>(out + oK8hi + tid * 16) = hi8;
-        *reinterpret_cast<i32x4*>(out + oK8lo + tid * 16) = lo8;
+        *reinterpret_cast<i32x4*>(out + kS8K8hi + tid * kS8PieceBytes) = hi8;
+        *reinterpret_cast<i32x4*>(out + kS8K8lo + tid * kS8PieceBytes) = lo8;
     }
-}
-
-__device__ __forceinline__ void xhalf_swap(float v, float& lo_bcast, float& hi_bcast) {     // see flash_split.hip
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    lo_bcast = a;
-    hi_bcast = b;
-}
-__device__ __forceinline__ float xhalf_max(float v) {
-    float a, b, o;
-    xhalf_swap(v, a, b);
-    asm("v_max_f32 %0, %1, %2" : "=v"(o) : "v"(a), "v"(b));
-    return o;
-}
-__device__ __forceinline__ float xhalf_sum(float v) {
-    float a, b;
-    xhalf_swap(v, a, b);
-    return a + b;
 }
 
 __device__ __forceinline__ f32x16 mx64(i32x8 a, i32x8 b, f32x16 c, int scale_a, int scale_b) {
@@ -140,7 +111,7 @@ __device__ __forceinline__ f32x16 mx64(i32x8 a, i32x8 b, f32x16 c, int scale_a, 
 // DROP: training-time dropout on the probabilities, the counter-based keep mask of FlashArgs::drop_seed exactly as in flash_split_pipe_kernel
 // (common.hpp; the backward kernels rebuild the same mask): the normaliser stays undropped, 1 / (1 - p) is applied once to the partial output.
 // TERMS = 1 (attention modes 2 / 3 on whole 64-key stages): the same step with ONE KIND (fp16 / bf16) product for the scores — Q and K
-// rounded to nearest once, no cross terms — on the single-product cache of flash_split.hip (a stage = two 8 KB blocks [K | V]).
+// rounded to nearest once, no cross terms — on the one-term cache (a stage = two 8 KB blocks [K | V]).
 template <int PROBE = 0, int RING = kRing, bool REV = false, bool DROP = false, int TERMS = 8, int KIND = kF16>
 __global__ __launch_bounds__(kNW * 64) void flash_split8_kernel(FlashArgs a, const unsigned char* __restrict__ cache) {
     PARQ_TL_KERNEL(kTlFlashSplit);
@@ -148,10 +119,11 @@ __global__ __launch_bounds__(kNW * 64) void flash_split8_kernel(FlashArgs a, con
     static_assert(TERMS == 1 || KIND == kF16, "the split is an fp16 split");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];       // [RING stages]
     constexpr bool MX = TERMS == 8;
-    constexpr int kStageBytes = MX ? kStage8Bytes : 16384;                    // (shadows the file-level constant of the mode-4 stage)
+    constexpr int kStageBytes = MX ? kStage8Bytes : 2 * KvBlk<1>::bytes;      // one-term cache: a stage = two blocks
     // byte offset of physical block pb's K / V plane inside a stage
-    auto k16_off = [](int pb) { return MX ? oKh16 + pb * 4096 : pb * 8192; };
-    auto v16_off = [](int pb) { return MX ? oVh16 + pb * 4096 : pb * 8192 + 4096; };
+    constexpr int kK16 = MX ? kS8Kh16 : 0, kV16 = MX ? kS8Vh16 : KvBlk<1>::v_hi * 2, kBlk16 = MX ? kS8Blk16Bytes : KvBlk<1>::bytes;
+    auto k16_off = [](int pb) { return kK16 + pb * kBlk16; };
+    auto v16_off = [](int pb) { return kV16 + pb * kBlk16; };
     constexpr int NT = kNW * 64;
     constexpr int STAGE16 = kStageBytes / 16;
     constexpr int LD = STAGE16 / NT;
@@ -176,7 +148,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split8_kernel(FlashArgs a, con
         const float* qp = a.q + (int64_t)b * a.q_batch + (int64_t)h * a.q_head + (int64_t)(q < a.Lq ? q : 0) * a.q_row;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const int d0 = 32 * (s >> 1) + 16 * (s & 1) + 4 * kh;
+            const int d0 = kv_dmap(kh, s, 0);
             f32x4 x0 = *reinterpret_cast<const f32x4*>(qp + d0);
             f32x4 x1 = *reinterpret_cast<const f32x4*>(qp + d0 + 8);
             if (q >= a.Lq) { x0 = f32x4{0.f, 0.f, 0.f, 0.f}; x1 = x0; }
@@ -188,7 +160,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split8_kernel(FlashArgs a, con
 #pragma unroll
             for (int e = 0; e < 8; e += 2) split_rtz(x[e], x[e + 1], hw[e >> 1], dl[e], dl[e + 1]);
             qh[s] = __builtin_bit_cast(half8, u32x4{hw[0], hw[1], hw[2], hw[3]});
-            // byte 16 c + 8 m + e of the fp8 operands <-> d = 32 m + 16 c + 4 h + (e & 3) + 8 (e >> 2), with s = 2 m + c
+            // byte 16 c + 8 m + e of the fp8 operands <-> d = kv_dmap(kh, 2 m + c, e) (the pieces of kv_layout.hpp), with s = 2 m + c
             const int m = s >> 1, c = s & 1;
             q8h[4 * c + 2 * m] = pack4_e4m3(x[0], x[1], x[2], x[3]);
             q8h[4 * c + 2 * m + 1] = pack4_e4m3(x[4], x[5], x[6], x[7]);
@@ -247,7 +219,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split8_kernel(FlashArgs a, con
     half8 kf[4], vh[2];                                                    // fp16 fragments of the NEXT step
     i32x8 k8h, k8l;
     if constexpr (PROBE & 16) { kf[0] = qh[0]; kf[1] = qh[1]; kf[2] = qh[2]; kf[3] = qh[3]; k8h = q8h; k8l = q8l; vh[0] = qh[0]; vh[1] = qh[1]; }
-    const int ksw = (li >> 1) & 7;
+    const int ksw = kv_kswz(li, 0);                                        // this lane's key row: chunk c sits at position c ^ ksw
 
     auto load_k16 = [&](int n) {
         if constexpr (PROBE & 16) return;
@@ -264,9 +236,9 @@ __global__ __launch_bounds__(kNW * 64) void flash_split8_kernel(FlashArgs a, con
         const int pb = pblk(n);
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-            const int off = (((pb * 2 + c) * 2 + kh) * 32 + li) * 16;
-            const i32x4 hv = *reinterpret_cast<const i32x4*>(st + oK8hi + off);
-            const i32x4 lv = *reinterpret_cast<const i32x4*>(st + oK8lo + off);
+            const int off = kv_piece8(pb, c, kh, li) * kS8PieceBytes;
+            const i32x4 hv = *reinterpret_cast<const i32x4*>(st + kS8K8hi + off);
+            const i32x4 lv = *reinterpret_cast<const i32x4*>(st + kS8K8lo + off);
 #pragma unroll
             for (int w = 0; w < 4; ++w) { k8h[4 * c + w] = hv[w]; k8l[4 * c + w] = lv[w]; }
         }
@@ -277,7 +249,7 @@ __global__ __launch_bounds__(kNW * 64) void flash_split8_kernel(FlashArgs a, con
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
             const int d = dt * 32 + li;
-            const int pos = (2 * m + kh) ^ ((d >> 2) & 3);
+            const int pos = kv_vswz(d, 2 * m + kh);
             vh[dt] = *reinterpret_cast<const half8*>(Vb + d * 32 + pos * 8);
         }
     };
@@ -528,7 +500,7 @@ hipError_t launch_flash_split8(const FlashArgs& a, const void* cache, hipStream_
 #define PARQ_F8_LAUNCH_RR(PROBE, RING, REV)                                                                                    \
     {                                                                                                                          \
         static DynLdsOnce once;                                                                                                \
-        const size_t lds = (size_t)(RING) * kStageBytes;                                                                       \
+        const size_t lds = (size_t)(RING) * kStage8Bytes;                                                                      \
         if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&flash_split8_kernel<PROBE, RING, REV>), lds); e != hipSuccess) return e; \
         hipLaunchKernelGGL((flash_split8_kernel<PROBE, RING, REV>), grid, dim3(kNW * 64), lds, s, b, c8);                       \
         return hipGetLastError();                                                                                              \
@@ -541,7 +513,7 @@ hipError_t launch_flash_split8(const FlashArgs& a, const void* cache, hipStream_
 #define PARQ_F8_LAUNCH_DROP(REV)                                                                                               \
     {                                                                                                                          \
         static DynLdsOnce once;                                                                                                \
-        const size_t lds = (size_t)kRing * kStageBytes;                                                                        \
+        const size_t lds = (size_t)kRing * kStage8Bytes;                                                                       \
         if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&flash_split8_kernel<0, kRing, REV, true>), lds); e != hipSuccess) return e; \
         hipLaunchKernelGGL((flash_split8_kernel<0, kRing, REV, true>), grid, dim3(kNW * 64), lds, s, b, c8);                    \
         return hipGetLastError();                                                                                              \
@@ -568,7 +540,7 @@ hipError_t launch_flash_split8(const FlashArgs& a, const void* cache, hipStream_
 }
 
 // Attention modes 2 / 3 (one fp16 / bf16 product per score and per output) on whole 64-key stages: the step of the kernel above without
-// cross terms, on the single-product cache.  Six 16 KB stages in the ring (the write-through epilogue needs 72 KB of it).
+// cross terms, on the single-product cache.  Six 16 KB stages (two blocks each) in the ring (the write-through epilogue needs 72 KB of it).
 hipError_t launch_flash_single_stage(const FlashArgs& a, const void* cache, hipStream_t s, int kind) {
     if (!flash_split8_supported(a.dh, a.Lk) || a.nsplit < 1 || a.nsplit > 256 || (kind != kF16 && kind != kBF16)) return hipErrorInvalidValue;
     FlashArgs b = a;
@@ -581,7 +553,7 @@ hipError_t launch_flash_single_stage(const FlashArgs& a, const void* cache, hipS
 #define PARQ_F1_LAUNCH(REV, DROP, KIND)                                                                                        \
     {                                                                                                                          \
         static DynLdsOnce once;                                                                                                \
-        const size_t lds = (size_t)kRing1 * 16384;                                                                             \
+        const size_t lds = (size_t)kRing1 * 2 * KvBlk<1>::bytes;                                                               \
         if (hipError_t e = once.ensure(reinterpret_cast<const void*>(&flash_split8_kernel<0, kRing1, REV, DROP, 1, KIND>), lds); e != hipSuccess) return e; \
         hipLaunchKernelGGL((flash_split8_kernel<0, kRing1, REV, DROP, 1, KIND>), grid, dim3(kNW * 64), lds, s, b, c8);          \
         return hipGetLastError();                                                                                              \

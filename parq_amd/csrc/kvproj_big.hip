@@ -1,5 +1,5 @@
 // Hoisted K/V in-projection for LARGE model dims (C > 256: the reference's shipped DEC_DIM 1024), written into the split-fp16
-// "fragment-ready" cache (layout: flash_split.hip; heads of 64 — a 256-dim head is 4 virtual heads, flash_split256.hip).
+// "fragment-ready" cache (layout: kv_layout.hpp; heads of 64 — a 256-dim head is 4 virtual heads, flash_split256.hip).
 //
 // The W-stationary kernel of kvproj_split.hip needs W_kv in registers (C <= 256) and its tiled fallback re-converts every token tile
 // once per 128-column tile (16 times at C = 1024) between two barriers per k-step.  Here the tokens are split into fp16 hi/lo ONCE
@@ -23,7 +23,6 @@ namespace {
 constexpr int kTM = 256, kTN = 256, kTK = 32;
 constexpr int kImg = kTM * kTK;                     // halfs of one [256 rows][32 k] image (16 KB)
 constexpr int kStage = 4 * kImg;                    // A_hi | A_lo | W_hi | W_lo
-constexpr int kBlkHalfs = 8192;                     // one 32-key cache block of a head (16 KB)
 
 struct BigArgs {
     const _Float16* Xhi; const _Float16* Xlo;       // [B*N][C] split tokens
@@ -71,7 +70,7 @@ __global__ __launch_bounds__(512) void kvproj_big_kernel(BigArgs a) {
     constexpr int NIMG = TERMS == 3 ? 4 : 2;                    // operand images per k-step: A_hi | A_lo | W_hi | W_lo, or A | W
     constexpr int kStg = NIMG * kImg;
     constexpr int NDMA = NIMG * 2;                              // DMA instructions per thread and k-step
-    constexpr int kBlkH = TERMS == 3 ? 8192 : 4096;             // halfs of one 32-key cache block of a head
+    constexpr int kBlkH = KvBlk<TERMS>::halfs;                  // halfs of one 32-key cache block of a head
     extern __shared__ __attribute__((aligned(16))) _Float16 lds[];          // [2][kStg]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, kh = lane >> 5;
@@ -185,7 +184,7 @@ __global__ __launch_bounds__(512) void kvproj_big_kernel(BigArgs a) {
     __syncthreads();                                            // the ring is free
     const int nblk = (a.N + 31) / 32;
     bool ovf = false;
-    _Float16* wl = lds + wave * 4096;                           // 8 KB per wave
+    _Float16* wl = lds + wave * (2 * kKvPlaneHalfs);            // 8 KB per wave: [hi plane | lo plane]
     // all bias values of this lane up front (64 for a K wave, 4 for a V wave): between the LDS round trips below each group's loads
     // would otherwise be issued and waited for one after the other (16 dependent L2 round trips per tile)
     float bK[2][2][2][8], bV[2][2];
@@ -199,7 +198,7 @@ __global__ __launch_bounds__(512) void kvproj_big_kernel(BigArgs a) {
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) bK[hh][ct][m][e] = bias[32 * ct + 16 * m + 4 * kh + (e & 3) + 8 * (e >> 2)];
+                    for (int e = 0; e < 8; ++e) bK[hh][ct][m][e] = bias[kv_dmap(kh, 2 * ct + m, e)];
             } else {
                 bV[hh][ct] = bias[32 * ct + li];
             }
@@ -215,10 +214,10 @@ __global__ __launch_bounds__(512) void kvproj_big_kernel(BigArgs a) {
                 for (int m = 0; m < 2; ++m) {
                     const f32x16& A = acc[t][2 * hh + ct];
                     float x[8];
-                    if (isK) {      // lane = key li, registers 8m .. 8m+7 = d 32 ct + 16 m + 4 kh + (e & 3) + 8 (e >> 2)
+                    if (isK) {      // lane = key li, registers 8m .. 8m+7 = d kv_dmap(kh, 2 ct + m, e)
 #pragma unroll
                         for (int e = 0; e < 8; ++e) x[e] = A[8 * m + e] + bK[hh][ct][m][e];
-                    } else {        // lane = d 32 ct + li, registers = keys 16 m + 4 kh + (e & 3) + 8 (e >> 2)
+                    } else {        // lane = d 32 ct + li, registers = keys kv_kmap(m, kh, e)
                         const float bv = bV[hh][ct];
 #pragma unroll
                         for (int e = 0; e < 8; ++e) x[e] = A[8 * m + e] + bv;
@@ -231,14 +230,14 @@ __global__ __launch_bounds__(512) void kvproj_big_kernel(BigArgs a) {
                         for (int e = 0; e < 8; ++e) ovf |= !(fabsf(x[e]) < 60000.f);
                     }
                     if (isK) {
-                        const int pos = (4 * kh + 2 * ct + m) ^ ((li >> 1) & 7);
+                        const int pos = kv_kswz(li, 4 * kh + 2 * ct + m);
                         *reinterpret_cast<half8*>(wl + li * 64 + pos * 8) = hi;
-                        if constexpr (TERMS == 3) *reinterpret_cast<half8*>(wl + 2048 + li * 64 + pos * 8) = lo;
+                        if constexpr (TERMS == 3) *reinterpret_cast<half8*>(wl + kKvPlaneHalfs + li * 64 + pos * 8) = lo;
                     } else {
                         const int d = 32 * ct + li;
-                        const int pos = (2 * m + kh) ^ ((d >> 2) & 3);
+                        const int pos = kv_vswz(d, 2 * m + kh);
                         *reinterpret_cast<half8*>(wl + d * 32 + pos * 8) = hi;
-                        if constexpr (TERMS == 3) *reinterpret_cast<half8*>(wl + 2048 + d * 32 + pos * 8) = lo;
+                        if constexpr (TERMS == 3) *reinterpret_cast<half8*>(wl + kKvPlaneHalfs + d * 32 + pos * 8) = lo;
                     }
                 }
             __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0): same-wave LDS round trip
@@ -246,7 +245,7 @@ __global__ __launch_bounds__(512) void kvproj_big_kernel(BigArgs a) {
             const int blk = (m0 + wr * 64 + t * 32) >> 5;
             if (blk < nblk && blk * 32 < a.row_end) {           // wave-uniform (blocks behind the range: a clean neighbour's, left alone)
                 const int hv = isK ? headcol : headcol - a.VH;
-                _Float16* gout = a.cache + (((int64_t)b * a.VH + hv) * nblk + blk) * kBlkH + (isK ? 0 : kBlkH / 2);
+                _Float16* gout = a.cache + (((int64_t)b * a.VH + hv) * nblk + blk) * kBlkH + (isK ? 0 : KvBlk<TERMS>::v_hi);
                 const uint4* src = reinterpret_cast<const uint4*>(wl);
                 uint4* dst = reinterpret_cast<uint4*>(gout);
 #pragma unroll

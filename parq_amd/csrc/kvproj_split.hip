@@ -1,5 +1,5 @@
 // Hoisted K/V in-projection of the memory tokens, written straight into the split-fp16
-// "fragment-ready" cache consumed by flash_split_pipe_kernel (layout: flash_split.hip header).
+// "fragment-ready" cache consumed by flash_split_pipe_kernel (layout: kv_layout.hpp).
 //
 //   [K | V][b][n][:] = tokens[b][n][:] @ W_kv^T + b_kv        (transformer_parq.py:377-380, hoisted:
 //                                                              SURVEY.md 0.7 — weights shared, memory constant)
@@ -24,7 +24,6 @@ namespace {
 
 constexpr int kBM = 128, kBN = 128, kBK = 64;
 constexpr int kThreads = 256;
-constexpr int kBlkHalfs = 8192;                 // one 32-key cache block (16 KB)
 
 struct KvProjArgs {
     const void* X;             // tokens [B][N][C]: fp32, or 16-bit of the kernel's token type TT
@@ -214,22 +213,22 @@ __global__ __launch_bounds__(kThreads) void kvproj_split_kernel(KvProjArgs a) {
     const int nblk = (a.N + 31) / 32;
     const int h = isK ? headcol : headcol - a.H;
     const float* bias = a.bias + headcol * 64;
-    _Float16* wl = lds + wave * (2 * 4096);                          // 2 blocks x 8 KB per wave = 8192 halfs
+    _Float16* wl = lds + wave * (2 * 2 * kKvPlaneHalfs);              // 2 blocks x 8 KB [hi plane | lo plane] per wave
 #pragma unroll
     for (int rt2 = 0; rt2 < 2; ++rt2) {
-        _Float16* out = wl + rt2 * 4096;                             // [hi 2048 halfs | lo 2048 halfs]
+        _Float16* out = wl + rt2 * (2 * kKvPlaneHalfs);
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
                 float x[8];
                 if (isK) {
-                    // lane = key (li), registers 8m..8m+7 = d = 32ct + 16m + 4kh + (e&3) + 8(e>>2): chunk s = 2ct + m
+                    // lane = key (li), registers 8m..8m+7 = d = kv_dmap(kh, s, e) of chunk s = 2ct + m
 #pragma unroll
                     for (int e = 0; e < 8; ++e)
-                        x[e] = acc[rt2][ct][8 * m + e] + bias[32 * ct + 16 * m + 4 * kh + (e & 3) + 8 * (e >> 2)];
+                        x[e] = acc[rt2][ct][8 * m + e] + bias[kv_dmap(kh, 2 * ct + m, e)];
                 } else {
-                    // lane = d (32ct + li), registers 8m..8m+7 = keys 16m + 4kh + (e&3) + 8(e>>2): chunk (m, kh)
+                    // lane = d (32ct + li), registers 8m..8m+7 = keys kv_kmap(m, kh, e): chunk (m, kh)
                     const float bv = bias[32 * ct + li];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) x[e] = acc[rt2][ct][8 * m + e] + bv;
@@ -240,14 +239,14 @@ __global__ __launch_bounds__(kThreads) void kvproj_split_kernel(KvProjArgs a) {
                 for (int e = 0; e < 8; ++e) ovf |= !(fabsf(x[e]) < 60000.f);
                 if (isK) {
                     const int c = 4 * kh + 2 * ct + m;
-                    const int pos = c ^ ((li >> 1) & 7);
+                    const int pos = kv_kswz(li, c);
                     *reinterpret_cast<half8*>(out + li * 64 + pos * 8) = hi;
-                    *reinterpret_cast<half8*>(out + 2048 + li * 64 + pos * 8) = lo;
+                    *reinterpret_cast<half8*>(out + kKvPlaneHalfs + li * 64 + pos * 8) = lo;
                 } else {
                     const int d = 32 * ct + li;
-                    const int pos = (2 * m + kh) ^ ((d >> 2) & 3);
+                    const int pos = kv_vswz(d, 2 * m + kh);
                     *reinterpret_cast<half8*>(out + d * 32 + pos * 8) = hi;
-                    *reinterpret_cast<half8*>(out + 2048 + d * 32 + pos * 8) = lo;
+                    *reinterpret_cast<half8*>(out + kKvPlaneHalfs + d * 32 + pos * 8) = lo;
                 }
             }
         }
@@ -259,8 +258,8 @@ __global__ __launch_bounds__(kThreads) void kvproj_split_kernel(KvProjArgs a) {
     for (int rt2 = 0; rt2 < 2; ++rt2) {
         const int blk = (m0 + wr * 64 + rt2 * 32) >> 5;
         if (blk >= nblk) continue;                                   // wave-uniform
-        _Float16* gout = a.cache + (((int64_t)b * a.H + h) * nblk + blk) * kBlkHalfs + (isK ? 0 : 4096);
-        const uint4* src = reinterpret_cast<const uint4*>(wl + rt2 * 4096);
+        _Float16* gout = a.cache + (((int64_t)b * a.H + h) * nblk + blk) * KvBlk<3>::halfs + (isK ? 0 : KvBlk<3>::v_hi);
+        const uint4* src = reinterpret_cast<const uint4*>(wl + rt2 * (2 * kKvPlaneHalfs));
         uint4* dst = reinterpret_cast<uint4*>(gout);
 #pragma unroll
         for (int i = 0; i < 8; ++i) dst[i * 64 + lane] = src[i * 64 + lane];
@@ -322,8 +321,8 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
     constexpr bool SPLIT = TERMS != 1;         // three-term products (TERMS = 3, and 8: the same GEMM with the mode-4 epilogue;
     constexpr bool MIX = TERMS == 11;          // 11: each head in the layout of ITS tier, KvProjArgs::safe_mask)
     static_assert((TERMS != 8 && !MIX) || TM == 64, "a tile is one 64-key stage of the mode-4 cache");
-    constexpr int kBlkH = SPLIT ? 8192 : 4096;      // 16-bit units per 32-key cache block
-    constexpr int kVoff = SPLIT ? 4096 : 2048;      // V_hi offset inside a block
+    constexpr int kBlkH = KvBlk<SPLIT ? 3 : 1>::halfs;     // 16-bit units per 32-key cache block
+    constexpr int kVoff = KvBlk<SPLIT ? 3 : 1>::v_hi;      // V_hi offset inside a block
     constexpr int kThr = NWV * 64;
     constexpr int kCols = NWV * 32;
     constexpr int RT = TM / 32;                  // 32-row blocks per tile (accumulators per wave)
@@ -475,7 +474,7 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) bK[8 * m + e] = bias[16 * (2 * m + kh) + 4 * ct + (e & 3) + 8 * (e >> 2)];
+                for (int e = 0; e < 8; ++e) bK[8 * m + e] = bias[kv_dmap(ct, 2 * m + kh, e)];        // the wave's dims: lane half ct of chunks s = 2 m + kh
         } else {
             bK[0] = bias[32 * ct + li];
         }
@@ -561,7 +560,7 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
                 continue;
             }
             _Float16* strip = stg + wave * 1024;
-            const int swz = ISK ? (li >> 1) & 3 : (li >> 2) & 3;     // low bits of the image's chunk swizzle for this lane's row
+            const int swz = ISK ? kv_kswz(li, 0) & 3 : kv_vswz(li, 0);   // low bits of the image's chunk swizzle for this lane's row
 #pragma unroll
             for (int t = 0; t < RT; ++t) {
                 const int blk = (m0 >> 5) + t;
@@ -569,12 +568,12 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
                 _Float16* out = a.cache + (((int64_t)b * a.H + h) * nblk + blk) * kBlkH;          // (= head_bytes apart when MIX)
                 unsigned char* stage = nullptr;
                 if constexpr (F8) {
-                    // mode-4 stage image (flash_split8.hip): this block's fp16 plane at t * 4 KB of the K / V 16-bit region; K lanes also
+                    // mode-4 stage image (kv_layout.hpp): this block's fp16 plane at t * 4 KB of the K / V 16-bit region; K lanes also
                     // store their 16 accumulator registers as ONE 16-byte piece of the hi8 plane and one of the lo8 plane
                     stage = reinterpret_cast<unsigned char*>(a.cache) +
-                            (MIX ? ((int64_t)b * a.H + h) * ((int64_t)nblk * (2 * kBlkHalfs)) + (int64_t)(m0 >> 6) * kStage8Bytes
+                            (MIX ? ((int64_t)b * a.H + h) * ((int64_t)nblk * KvBlk<3>::bytes) + (int64_t)(m0 >> 6) * kStage8Bytes
                                  : (((int64_t)b * a.H + h) * (nblk >> 1) + (m0 >> 6)) * kStage8Bytes);
-                    out = reinterpret_cast<_Float16*>(stage + (ISK ? kS8Kh16 : kS8Vh16 - 2 * kVoff) + t * 4096);
+                    out = reinterpret_cast<_Float16*>(stage + (ISK ? kS8Kh16 : kS8Vh16 - 2 * kVoff) + t * kS8Blk16Bytes);
                 }
                 // ---- the block's values, with the range handling (GUARD: the e4m3 clamps of the stage cache's 8-bit K planes and the
                 // fp16 range compares, per value) or without it; which one runs is decided once per block below
@@ -590,15 +589,15 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
 #endif
                             i32x4 hi8, lo8;
                             pieces_e4m3<GUARD>(x16, hi8, lo8);
-                            const int piece = ((t * 2 + kh) * 2 + ct) * 32 + li;        // piece (c = kh, h = ct) of key li
+                            const int piece = kv_piece8(t, kh, ct, li);                 // piece (c = kh, h = ct) of key li
                             if constexpr (PROBE & 32) {                                  // development: where does the read-back come from?
                                 if (hi8[0] == 0x12345678 && lo8[1] == 0x1234567) stage[tid] = 1;
                             } else if constexpr (PROBE & 256) {                          // non-temporal: the written cache is not read again by this kernel
-                                __builtin_nontemporal_store(hi8, reinterpret_cast<i32x4*>(stage + kS8K8hi + piece * 16));
-                                __builtin_nontemporal_store(lo8, reinterpret_cast<i32x4*>(stage + kS8K8lo + piece * 16));
+                                __builtin_nontemporal_store(hi8, reinterpret_cast<i32x4*>(stage + kS8K8hi + piece * kS8PieceBytes));
+                                __builtin_nontemporal_store(lo8, reinterpret_cast<i32x4*>(stage + kS8K8lo + piece * kS8PieceBytes));
                             } else if constexpr (!(PROBE & 2)) {
-                                *reinterpret_cast<i32x4*>(stage + kS8K8hi + piece * 16) = hi8;
-                                *reinterpret_cast<i32x4*>(stage + kS8K8lo + piece * 16) = lo8;
+                                *reinterpret_cast<i32x4*>(stage + kS8K8hi + piece * kS8PieceBytes) = hi8;
+                                *reinterpret_cast<i32x4*>(stage + kS8K8lo + piece * kS8PieceBytes) = lo8;
                                 if (t == 0) PARQ_KV_STAMP(6);
                             }
                         }
@@ -631,11 +630,11 @@ __global__ __launch_bounds__(512, 1) void kvproj_dma_kernel(KvProjArgs a, int to
                                 if (v[0] == (_Float16)123.f) out[tid] = v[1];
                             } else if constexpr (ISK) {
                                 const int half_row = ct ^ ((row >> 3) & 1);           // bit 2 of the row's swizzle (key >> 1) & 7
-                                half8* dst = reinterpret_cast<half8*>(out + pl * 2048 + row * 64 + ((4 * half_row + pc) << 3));
+                                half8* dst = reinterpret_cast<half8*>(out + pl * kKvPlaneHalfs + row * 64 + ((4 * half_row + pc) << 3));
                                 if constexpr (PROBE & 256) __builtin_nontemporal_store(v, dst);
                                 else *dst = v;
                             } else {
-                                half8* dst = reinterpret_cast<half8*>(out + kVoff + pl * 2048 + (32 * ct + row) * 32 + pc * 8);
+                                half8* dst = reinterpret_cast<half8*>(out + kVoff + pl * kKvPlaneHalfs + (32 * ct + row) * 32 + pc * 8);
                                 if constexpr (PROBE & 256) __builtin_nontemporal_store(v, dst);
                                 else *dst = v;
                             }

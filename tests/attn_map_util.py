@@ -138,7 +138,7 @@ def k_tiers(safe_mask):
 
 def decode_one_term_cache(raw, Bn, heads, N, kind):
     """K of the one-term ("fp16" / "bf16") cache as the device holds it: (B, heads, N, 64) float64 from the raw workspace buffer
-    "kv_cache16" of a handle with shared layers and head dim 64.  Layout (csrc/flash_split.hip header): per (scene, head) 32-key blocks
+    "kv_cache16" of a handle with shared layers and head dim 64.  Layout (csrc/kv_layout.hpp, restated here independently): per (scene, head) 32-key blocks
     of 8 KB [K | V]; K = [32 keys][8 chunk positions][8 elements], chunk c = 4 kh + s sits at position c ^ ((key >> 1) & 7) and holds
     d = 32 (s >> 1) + 16 (s & 1) + 4 kh + (e & 3) + 8 (e >> 2)."""
     nblk = (N + 31) // 32

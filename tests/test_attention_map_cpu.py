@@ -39,7 +39,7 @@ def test_cache_forms_round_keys_as_the_formats_do():
 
 
 def test_one_term_cache_decode_inverts_the_documented_layout():
-    """Written element by element in the order csrc/flash_split.hip documents for a [K | V] block; ragged N, two heads."""
+    """Written element by element in the order csrc/kv_layout.hpp documents for a [K | V] block; ragged N, two heads."""
     Bn, H, N = 1, 2, 70
     K = torch.randn(Bn, H, N, 64, generator=torch.Generator().manual_seed(3)).bfloat16()
     nblk = (N + 31) // 32
