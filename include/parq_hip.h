@@ -715,6 +715,20 @@ int parq_k_project_sample(const float *tokens, const float *T_camera_local, cons
                           int32_t ww, int32_t C, int32_t Q, float *tgt, float *coord_pos,
                           parq_stream stream);
 
+/* The backward of the above, as one call of what parq_backward runs (backward.hip: sample_bwd_kernel; with a scratch
+ * sample_det_records_kernel + sample_det_gather_kernel, the deterministic form of the token gradient).
+ * tokens (B, V*hh*ww, C) of token_type (PARQ_TOKENS_F32 / _F16 / _BF16; read for g_ref only), T_camera_local (B,V,12) float64, as the
+ * training workspace holds it, g_tgt (B,Q,C).  g_tokens (B, V*hh*ww, C) float32 and g_ref (B,Q,3) are ADDED to; either may be NULL.
+ * det_scratch NULL / 0 bytes: the token gradient is scattered with float atomics; else it must hold
+ * parq_k_project_sample_backward_scratch_bytes() (B*Q*V*8 floats) and the gradient is gathered per token in query order.
+ * PARQ_ERR_ARG: the argument checks of parq_k_project_sample, an unknown token type, a scratch that is too small.
+ * (Parenthesised names: see parq_set_batch_invariant; both are typed in _lib.EXTRA_SYMBOLS.) */
+size_t (parq_k_project_sample_backward_scratch_bytes)(int32_t B, int32_t V, int32_t Q);
+int (parq_k_project_sample_backward)(const void *tokens, int32_t token_type, const double *T_camera_local, const float *camera,
+                                     const float *ref, const float *scale6_host, int32_t B, int32_t V, int32_t hh, int32_t ww,
+                                     int32_t C, int32_t Q, const float *g_tgt, float *g_tokens, float *g_ref, void *det_scratch,
+                                     size_t det_scratch_bytes, parq_stream stream);
+
 /* T_camera_local = T_cp ∘ (inv(T_wp) ∘ T_wl)  (transformer_parq.py:298-300). */
 int parq_k_camera_local(const float *T_cp, const float *T_wp, const float *T_wl, int32_t B, int32_t V,
                         float *T_cl, parq_stream stream);

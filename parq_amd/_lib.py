@@ -146,6 +146,9 @@ EXTRA_SYMBOLS = {
     "parq_tracks_store_bytes": (_sz, [_i32, _i32]),
     "parq_tracks_update_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "parq_tracks_update": (C.c_int, [_vp, _i32, _i32, C.POINTER(_i32), _i32, _vp, _vp, _vp, _i32, _i32, _f, _f, _vp, _sz, _vp, _vp, _vp]),
+    "parq_k_project_sample_backward_scratch_bytes": (_sz, [_i32, _i32, _i32]),
+    "parq_k_project_sample_backward": (C.c_int, [_vp, _i32, _vp, _vp, _vp, C.POINTER(_f), _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                                 _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -2270,6 +2270,34 @@ int parq_k_project_sample(const float* tokens, const float* T_cl, const float* c
     return PARQ_OK;
 }
 
+size_t parq_k_project_sample_backward_scratch_bytes(int32_t B, int32_t V, int32_t Q) {
+    if (B < 1 || V < 1 || Q < 1) return 0;
+    return (size_t)B * Q * V * 8 * sizeof(float);
+}
+
+int parq_k_project_sample_backward(const void* tokens, int32_t token_type, const double* T_cl, const float* camera, const float* ref,
+                                   const float* scale6_host, int32_t B, int32_t V, int32_t hh, int32_t ww, int32_t C, int32_t Q,
+                                   const float* g_tgt, float* g_tokens, float* g_ref, void* det_scratch, size_t det_scratch_bytes,
+                                   parq_stream stream) {
+    if (!tokens || !T_cl || !camera || !ref || !scale6_host || !g_tgt) return fail(PARQ_ERR_ARG, "NULL argument");
+    if (B < 1 || V < 1 || hh < 2 || ww < 2 || Q < 1 || C % 4 != 0 || C > 1024) return fail(PARQ_ERR_ARG, "bad dims");
+    if (token_type != kTokF32 && token_type != kTokF16 && token_type != kTokBF16)
+        return fail(PARQ_ERR_ARG, "token type must be 0 (fp32), 1 (fp16) or 2 (bf16), not %d", token_type);
+    if ((det_scratch == nullptr) != (det_scratch_bytes == 0)) return fail(PARQ_ERR_ARG, "det_scratch and det_scratch_bytes: both or neither");
+    if (det_scratch && (det_scratch_bytes < parq_k_project_sample_backward_scratch_bytes(B, V, Q) ||
+                        (reinterpret_cast<uintptr_t>(det_scratch) & 3u)))
+        return fail(PARQ_ERR_ARG, "det_scratch: B * Q * V * 8 floats, 4-byte aligned");
+    ScaleBox sb;
+    for (int i = 0; i < 3; ++i) { sb.lo[i] = scale6_host[2 * i]; sb.hi[i] = scale6_host[2 * i + 1]; }
+    if (det_scratch) {                 // launch_sample_bwd takes the gather form while a DetScope is alive on this thread
+        DetScope det(static_cast<float*>(det_scratch), (int64_t)(det_scratch_bytes / sizeof(float)));
+        HIPCHK(launch_sample_bwd(tokens, T_cl, camera, ref, sb, B, V, hh, ww, C, Q, g_tgt, g_tokens, g_ref, (hipStream_t)stream, token_type));
+        return PARQ_OK;
+    }
+    HIPCHK(launch_sample_bwd(tokens, T_cl, camera, ref, sb, B, V, hh, ww, C, Q, g_tgt, g_tokens, g_ref, (hipStream_t)stream, token_type));
+    return PARQ_OK;
+}
+
 int parq_k_linear(const float* X, const float* X2, const float* W, const float* bias, const float* R, float* Y,
                   int32_t M, int32_t N, int32_t K, int32_t relu, parq_stream stream) {
     if (!X || !W || !Y || M < 1 || N < 1 || K < 32 || K % 32 != 0) return fail(PARQ_ERR_ARG, "bad argument (K must be a multiple of 32)");
