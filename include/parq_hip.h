@@ -705,6 +705,45 @@ int parq_set_loss_flags(const float *pred_logits, const float *center_unnormaliz
                         const float *row_weight, const float *class_weight, const float *loss_weight4_host, float *terms, float *g_logits,
                         float *g_center, float *g_size, float *g_ortho6d, int32_t *class_scratch, int32_t flags, parq_stream stream);
 
+/* ---- the matching of the set loss on the device (utils/matcher.py:31-115), one enqueue of four launches -------------------------
+ * For all S = I * B (iteration, scene) problems at once, with nothing read back: the inputs of parq_set_loss_flags (pairs, pair_coef,
+ * row_weight, with P = I*B*Q) from the decoder outputs and the padded targets.  NumPy statement: tests/set_match_cases.py.
+ * pred_logits (I,B,Q,num_classes), coord_pos (I,B,Q,3) float32; t_center (B,nmax,3) float32, t_label (B,nmax) int32, t_count (B)
+ * int32 on the DEVICE: the boxes of scene b are the first n = t_count[b] of its nmax slots (a count outside [0, nmax] counts as 0).
+ *  a. Cost, per row (k, b, q), in float32 with every operation rounded once (no contraction):
+ *       prob = softmax of the row's logits: subtract the maximum, expf, sum in index order, divide;
+ *       l1[j] = (|x - cx_j| + |y - cy_j|) + |z - cz_j| for j < n;   near[q][j] = l1[j] < ratio;
+ *       m[q][j] = -(cost_bbox * l1[j] - cost_class * prob[t_label[b][j]]), a label outside [0, num_classes) reading probability 0;
+ *       a non-finite m (the outputs of a forward that left the fp16 range are NaN) is written as -3.0e38f.
+ *  b. parq_assign_max's assignment on the S matrices (Q x n): row_to_col (I,B,Q) int32, the box assigned to each prediction or -1.
+ *  c. Extras.  For box j the neighbours are {q : near[q][j]}; if there are more than max_padding, only the max_padding of smallest
+ *     (key, q), key = H(seed_lo, seed_hi, step, k, b, j, q) in uint32 arithmetic:
+ *       mix(h): h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16
+ *       h = 0x9e3779b9; for w in (seed_lo, seed_hi, step, k, b, j, q): h = mix((h ^ w) + 0x9e3779b9);   key = h
+ *     (the reference draws np.random.choice here: a uniform subset either way, and the one difference from the host matcher).
+ *     One box per prediction: g[q] = row_to_col[q] where the assignment gave q a box, else the lowest j that chose q, else -1 — the
+ *     host's np.unique over [Hungarian rows | extras by box, then query].  punish[q] = !near[q][n-1] || chosen(q, n-1): the mask of
+ *     the LAST box, as in the reference (all ones for n = 0).
+ *  d. Outputs, dense: pairs [4][I*B*Q] int32 = iteration, scene, query, g (parq_set_loss_flags skips a pair whose box is -1);
+ *     cnt(k,b) = number of q with g >= 0, valid(k,b) = cnt > 0, valid_bs = number of valid segments;
+ *     pair_coef [I*B*Q] = 1.0f / ((float)cnt(k,b) * (float)valid_bs), 0 where cnt = 0;
+ *     row_weight [I*B*Q] = (((float)punish / (float)sum_q punish) * valid(k,b)) / (float)valid_bs, correctly rounded divisions;
+ *     valid_bs = 0 gives all-zero pair_coef and row_weight; stats (I*B + 1) int32 = cnt of every segment, then valid_bs.
+ * cost_out (I,B,Q,nmax) float32 and near_out (I,B,Q,nmax) bytes, NULL in normal use: for tests, m and near (columns j >= n are not
+ * written).  No atomics: two calls give the same bits.  Every number read from device memory is checked before it indexes anything.
+ * workspace: parq_set_match_workspace_bytes(I, B, Q, nmax) bytes (0 for arguments this entry refuses), 16-byte aligned; the library
+ * allocates nothing and does not synchronise.  I = 0 or B = 0 is valid and launches nothing.  PARQ_ERR_ARG, with nothing launched:
+ * Q or nmax outside [1, 2048], num_classes < 2, a negative count, I*B*Q above 2^28, a NULL pointer (cost_out and near_out excepted),
+ * a workspace too small or misaligned.
+ * (Parenthesised names: see parq_set_batch_invariant; both are typed in _lib.MATCH_SYMBOLS.) */
+size_t (parq_set_match_workspace_bytes)(int32_t I, int32_t B, int32_t Q, int32_t nmax);
+int (parq_set_match)(const float *pred_logits, const float *coord_pos, int32_t I, int32_t B, int32_t Q, int32_t num_classes,
+                     const float *t_center, const int32_t *t_label, const int32_t *t_count, int32_t nmax, float cost_class,
+                     float cost_bbox, float ratio, int32_t max_padding, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
+                     void *workspace, size_t workspace_bytes, int32_t *row_to_col, int32_t *pairs, float *pair_coef,
+                     float *row_weight, int32_t *stats, float *cost_out /*NULL in normal use*/,
+                     unsigned char *near_out /*NULL in normal use*/, parq_stream stream);
+
 /* ---- single kernels (parity tests, roofline measurements) --------------------------- */
 
 /* K4+K5: project (B,Q,3) normalised reference points into every view and bilinearly

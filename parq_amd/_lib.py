@@ -151,6 +151,14 @@ EXTRA_SYMBOLS = {
                                                  _vp, _sz, _vp]),
 }
 
+# the matcher of the set loss (include/parq_hip.h parq_set_match): a third table, the sizes of the two above being pinned by tests
+_u32 = C.c_uint32
+MATCH_SYMBOLS = {
+    "parq_set_match_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "parq_set_match": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _f, _f, _f, _i32, _u32, _u32, _u32, _vp, _sz,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -177,7 +185,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(EXTRA_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(EXTRA_SYMBOLS.items()) + list(MATCH_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

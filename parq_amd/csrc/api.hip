@@ -2761,6 +2761,34 @@ int parq_tracks_update(void* store, int32_t S_cap, int32_t max_tracks, const int
     return PARQ_OK;
 }
 
+size_t parq_set_match_workspace_bytes(int32_t I, int32_t B, int32_t Q, int32_t nmax) {
+    if (I < 0 || B < 0 || Q < 1 || Q > 2048 || nmax < 1 || nmax > 2048 || (int64_t)I * B * Q > (int64_t)(1 << 28)) return 0;
+    return set_match_workspace_bytes(I, B, Q, nmax);
+}
+
+int parq_set_match(const float* pred_logits, const float* coord_pos, int32_t I, int32_t B, int32_t Q, int32_t num_classes,
+                   const float* t_center, const int32_t* t_label, const int32_t* t_count, int32_t nmax, float cost_class, float cost_bbox,
+                   float ratio, int32_t max_padding, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, void* workspace,
+                   size_t workspace_bytes, int32_t* row_to_col, int32_t* pairs, float* pair_coef, float* row_weight, int32_t* stats,
+                   float* cost_out, unsigned char* near_out, parq_stream stream) {
+    if (I < 0 || B < 0 || max_padding < 0) return fail(PARQ_ERR_ARG, "parq_set_match: negative count");
+    if (Q < 1 || Q > 2048 || nmax < 1 || nmax > 2048 || num_classes < 2)
+        return fail(PARQ_ERR_ARG, "parq_set_match: Q = %d, nmax = %d, num_classes = %d; 1 <= Q, nmax <= 2048 and num_classes >= 2", Q, nmax,
+                    num_classes);
+    if ((int64_t)I * B * Q > (int64_t)(1 << 28)) return fail(PARQ_ERR_ARG, "parq_set_match: I * B * Q above 2^28");
+    if (I == 0 || B == 0) return PARQ_OK;                               // no problem: no launch
+    if (!pred_logits || !coord_pos || !t_center || !t_label || !t_count || !workspace || !row_to_col || !pairs || !pair_coef || !row_weight ||
+        !stats)
+        return fail(PARQ_ERR_ARG, "parq_set_match: NULL argument");
+    const size_t need = parq_set_match_workspace_bytes(I, B, Q, nmax);
+    if (workspace_bytes < need) return fail(PARQ_ERR_ARG, "parq_set_match: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 15) return fail(PARQ_ERR_ARG, "parq_set_match: the workspace must be 16-byte aligned");
+    HIPCHK(launch_set_match(pred_logits, coord_pos, I, B, Q, num_classes, t_center, t_label, t_count, nmax, cost_class, cost_bbox, ratio,
+                            max_padding, seed_lo, seed_hi, step, workspace, row_to_col, pairs, pair_coef, row_weight, stats, cost_out,
+                            near_out, (hipStream_t)stream));
+    return PARQ_OK;
+}
+
 size_t parq_draw_boxes_workspace_bytes(int32_t B, int32_t T, int32_t M) {
     if (B < 1 || T < 1 || M < 0 || M > (1 << 24) || (int64_t)B * T > 65535) return 0;
     return draw_minmax_bytes(B, T) + (size_t)B * T * M * 12 * 8;

@@ -784,6 +784,14 @@ size_t tracks_update_workspace_bytes(int B, int Q, int max_tracks);
 hipError_t launch_tracks_update(int32_t* store, int max_tracks, const int32_t* slots_host, int b0, int nb, const float* corners_world,
                                 const float* prob, const unsigned char* mask, int Q, int K, float conf, float iou_thresh, void* ws,
                                 int32_t* track_id, float* iou_out, hipStream_t s);
+// setmatch.hip: the set loss's matcher for all I * B (iteration, scene) problems (cost, launch_assign_max, pairs, finish: four
+// launches; I * B >= 1, Q and nmax in [1, 2048]); ws: set_match_workspace_bytes, 16-byte aligned
+size_t set_match_workspace_bytes(int I, int B, int Q, int nmax);
+hipError_t launch_set_match(const float* logits, const float* coord, int I, int B, int Q, int ncls, const float* t_center,
+                            const int32_t* t_label, const int32_t* t_count, int nmax, float cost_class, float cost_bbox, float ratio,
+                            int max_padding, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, void* ws, int32_t* row_to_col,
+                            int32_t* pairs, float* coef, float* row_weight, int32_t* stats, float* cost_out, unsigned char* near_out,
+                            hipStream_t st);
 // draw.hip: boxes drawn into the normalised views.  Workspace = the min / max parts (draw_minmax_bytes, a multiple of 16 bytes)
 // followed by the (B, T, M, 12) edge slots of 8 bytes each
 size_t draw_minmax_bytes(int B, int T);

@@ -1,7 +1,9 @@
 // Set loss of the decoder outputs on the device, given the matching (model/parq_decoder.py:264-370; host mirror: parq_amd/loss.py
-// decoder_loss_batched, whose tail this replaces for device tensors).  The matcher (scipy LSAP + the np.random.choice cap) stays on the
-// host as in the reference; what remains is ~40 tiny torch launches forward and ~60 in autograd per step, 4 ms in which the device
-// idles.  Here: three launches produce the four loss terms AND d term / d output for the four differentiable outputs — each term
+// decoder_loss_batched, whose tail this replaces for device tensors).  The matching comes from the host as in the reference (scipy LSAP
+// + the np.random.choice cap, uploaded in one buffer) or, with PARQDecoder.match_on_device, from setmatch.hip, which writes the same
+// pairs / pair_coef / row_weight on the device, dense over (iteration, scene, query) with box -1 for an unmatched prediction.  What
+// remained of the loss was ~40 tiny torch launches forward and ~60 in autograd per step, 4 ms in which the device idled.  Here: three
+// launches produce the four loss terms AND d term / d output for the four differentiable outputs — each term
 // depends on exactly one output tensor (centre <- center_unnormalized, size <- size_unnormalized, rotation <- ortho6d, class <-
 // pred_logits), so the backward of the autograd node is four scalings.
 //

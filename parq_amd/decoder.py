@@ -410,6 +410,16 @@ class PARQDecoder(_Tracked, nn.Module):
                                           # augmentation between dec(...) and dec.loss(...)): the loss's side stream then waits for the
                                           # whole main stream before it reads them (correct, no overlap with the forward's iterations)
         self._train_pending = None        # deferred range check of the last training forward: callable -> True if it re-ran
+        # loss(): match predictions to boxes on the device (include/parq_hip.h parq_set_match) instead of on host copies with scipy:
+        # no iteration is waited for, nothing is read back between forward and backward, and the step's only host wait is the one
+        # the range policy needs.  Where a box has more than 10 reference points within its neighbourhood, the 10 kept are chosen by a
+        # hash of (match_seed, step counter, iteration, scene, box, query) instead of np.random.choice — the one difference from the
+        # host matcher, and independent of the process-wide NumPy generator.  Taken when loss_batched is on, the outputs are float32
+        # CUDA tensors, Q and the box count are at most 2048 and no scene of the batch is empty; otherwise the host path, as before.
+        # Off by default (profiles/set_match_ab.json).
+        self.match_on_device = False
+        self.match_seed = 0               # 64 bits; with _match_step (one per loss() call on the device path) it keys the capped draw
+        self._match_step = 0
         self.max_workspaces = 2           # inference workspaces (each holds a K/V cache) kept alive, least recently used first out
         self._mean_dev = None
         # fp16-operand attention modes ("split", "split8", "fp16"): what to do when a token / K / V element leaves the fp16 range
@@ -1575,7 +1585,8 @@ class PARQDecoder(_Tracked, nn.Module):
     # ------------------------------------------------------------------ next-tier rows
     def loss(self, out_dict_list, obbs_padded, T_world_local, sym=None, *argv):
         """Hungarian-matched set loss, model/parq_decoder.py:264-370 (host-side torch + scipy as in the reference;
-        parq_amd/loss.py).  Under autograd its gradient reaches the weights through the HIP backward chain."""
+        parq_amd/loss.py; with ``match_on_device`` the matcher runs on the device and nothing is read back).  Under autograd its
+        gradient reaches the weights through the HIP backward chain."""
         from .loss import HungarianMatcherModified, decoder_loss, decoder_loss_batched
         if self._matcher is None:
             self._matcher = HungarianMatcherModified(cost_class=2, cost_bbox=0.25)          # parq_decoder.py:71
@@ -1592,8 +1603,18 @@ class PARQDecoder(_Tracked, nn.Module):
             ready = self._train_ready                      # these ARE the outputs of the training forward in flight
         else:
             self._resolve_train_range()
-        return decoder_loss_batched(out_dict_list, obbs_padded, T_world_local, sym, ready=ready,
-                                    targets_ready=self._train_entry_event if (ready is not None and not self.loss_targets_late) else None, **kw)
+        targets_ready = self._train_entry_event if (ready is not None and not self.loss_targets_late) else None
+        if self.match_on_device:
+            from .loss import decoder_loss_device_matched, device_match_inputs_ok
+            if device_match_inputs_ok(out_dict_list):
+                # matching and loss are enqueued behind the forward in flight; its deferred range check is resolved afterwards, once
+                res = decoder_loss_device_matched(out_dict_list, obbs_padded, T_world_local, sym, seed=self.match_seed, step=self._match_step,
+                                                  resolve=self._train_resolve_enqueued if ready is not None else None,
+                                                  targets_ready=targets_ready, **kw)
+                if res is not None:
+                    self._match_step += 1
+                    return res
+        return decoder_loss_batched(out_dict_list, obbs_padded, T_world_local, sym, ready=ready, targets_ready=targets_ready, **kw)
 
     def wait_iteration(self, k):
         """Block the host until iteration k of the last training forward has written its outputs (parq_wait_iteration)."""
@@ -1606,6 +1627,15 @@ class PARQDecoder(_Tracked, nn.Module):
             return False
         if (int(self._range_mirror[0]) & 3) == 0 and k + 1 < self.num_layers:
             return False                                   # nothing raised so far
+        self.wait_iteration(self.num_layers - 1)           # the whole forward, then the pinned word is final
+        pending, self._train_pending = self._train_pending, None
+        return bool(pending(True))
+
+    def _train_resolve_enqueued(self):
+        """loss() with the matching on the device, after matching and loss are enqueued: the one host wait of the step.  True = the
+        forward was re-run (range fallback) and what was enqueued on its first outputs must be enqueued again."""
+        if self._train_pending is None:
+            return False
         self.wait_iteration(self.num_layers - 1)           # the whole forward, then the pinned word is final
         pending, self._train_pending = self._train_pending, None
         return bool(pending(True))

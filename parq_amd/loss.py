@@ -2,7 +2,8 @@
 its matcher (utils/matcher.py:31-115) and the 6-D rotation helpers (utils/ortho6d_transforms.py).
 
 All arithmetic is plain torch on whatever device the decoder outputs live on (the tensors are (B, Q, <=10): this is not a
-hot path); the linear-sum-assignment runs in scipy on the host exactly as in the reference.  The reference's quirks are kept,
+hot path); the linear-sum-assignment runs in scipy on the host exactly as in the reference — or, with PARQDecoder.match_on_device, the
+whole matcher runs on the device (``decoder_loss_device_matched``: parq_set_match + parq_set_loss).  The reference's quirks are kept,
 because a drop-in must give the same numbers:
   * the matcher works on ``coord_pos`` (the INPUT reference points of the iteration), not on the predicted centres (:58);
   * besides the Hungarian pairs every prediction whose reference point lies within L1 < 0.2 of a ground-truth centre is
@@ -291,6 +292,108 @@ def _side_stream(dev):
     return _SIDE_STREAMS[key]
 
 
+def _padded_targets(targets, sym, class_weight, B, nmax, dev):
+    """Sizes, rotations, labels, symmetry classes of the boxes padded to (B, nmax, ·), and the class weights, as parq_set_loss reads them."""
+    t_size = torch.zeros(B, nmax, 3, device=dev); t_rot = torch.zeros(B, nmax, 3, 3, device=dev)
+    t_lab = torch.zeros(B, nmax, dtype=torch.int32, device=dev)
+    for b, t in enumerate(targets):
+        n = len(t["labels"])
+        t_size[b, :n] = t["size"]; t_rot[b, :n] = t["T_rig_object"][:, :3, :3]; t_lab[b, :n] = t["labels"].to(torch.int32)
+    t_sym = raw(sym).to(dev)[:, :nmax].to(torch.int32).contiguous() if sym is not None else None
+    cw_dev = class_weight.to(device=dev, dtype=torch.float32).contiguous()
+    return t_size, t_rot, t_lab, t_sym, cw_dev
+
+
+MATCH_MAX_SIDE = 2048         # parq_set_match: queries per scene and boxes per scene
+
+
+def device_match_inputs_ok(out_dict_list):
+    """What can be told before the targets are parsed: float32 CUDA outputs of one shape, Q within parq_set_match's limit."""
+    if not DEVICE_SET_LOSS or not out_dict_list:
+        return False
+    lg = out_dict_list[0]["pred_logits"]
+    keys = _DIFF_KEYS + ("coord_pos",)
+    return (lg.dim() == 3 and 1 <= lg.shape[1] <= MATCH_MAX_SIDE and lg.shape[2] >= 2 and
+            all(o[k].is_cuda and o[k].dtype == torch.float32 and o[k].shape[:2] == lg.shape[:2] for o in out_dict_list for k in keys))
+
+
+def decoder_loss_device_matched(out_dict_list, obbs_padded, T_world_local, sym=None, *, matcher, loss_weight, num_semcls, class_weight,
+                                seed=0, step=0, resolve=None, targets_ready=None):
+    """``decoder_loss_batched`` with the matching on the device (parq_set_match, parq_amd/csrc/setmatch.hip): cost, assignment,
+    neighbourhood extras and the constants of the loss are computed for all (iteration, scene) pairs behind the forward, and
+    parq_set_loss consumes them where they lie — nothing is read back, and no iteration is waited for.  The target preparation is the
+    one of ``decoder_loss_batched`` (its single host read gives the box counts).  Where a box has more than ``matcher.max_padding``
+    neighbours the kept ones are those of smallest hash key of (seed, step, iteration, scene, box, query) instead of an
+    np.random.choice draw: a function of the outputs and (seed, step) alone.
+
+    ``resolve`` (PARQDecoder.loss on the outputs of its own training forward in flight): called once AFTER everything is enqueued; it
+    waits for the forward, and returns True if the forward had to be re-run (fp16 range fallback), in which case matching and loss are
+    enqueued again on the rewritten outputs, with the same ``step``.  The targets are then prepared on the side stream, ordered by
+    ``targets_ready`` as in ``decoder_loss_batched``.
+
+    Returns None — the caller takes the host path — when a scene has no box (the reference's mis-indexing of such batches is not
+    reproduced here) or more than 2048."""
+    import ctypes as C
+    from . import _lib
+    X = raw(obbs_padded)
+    assert X.ndim == 3, tuple(X.shape)
+    I, B = len(out_dict_list), X.shape[0]
+    dev = out_dict_list[-1]["pred_logits"].device
+    Q, ncls = out_dict_list[-1]["pred_logits"].shape[1:]
+    assert num_semcls + 1 == ncls
+    main = torch.cuda.current_stream(dev) if resolve is not None else None
+    side = _side_stream(dev) if main is not None else None
+    on_side = (lambda: torch.cuda.stream(side)) if side is not None else contextlib.nullcontext
+    if side is not None:
+        if targets_ready is not None:
+            side.wait_event(targets_ready)
+        else:
+            side.wait_stream(main)
+    with on_side():
+        targets = parse_target(obbs_padded, T_world_local)
+        counts = [len(t["labels"]) for t in targets]
+        if B == 0 or min(counts) == 0 or max(counts) > MATCH_MAX_SIDE:
+            return None
+        nmax = max(counts)
+        tc = torch.zeros(B, nmax, 3, device=dev, dtype=torch.float32)
+        for b, t in enumerate(targets):
+            tc[b, :counts[b]] = t["center"]
+        t_size, t_rot, t_lab, t_sym, cw_dev = _padded_targets(targets, sym, class_weight, B, nmax, dev)
+        t_cnt = torch.tensor(counts, dtype=torch.int32).to(dev)
+    consts = [tc, t_size, t_rot, t_lab, cw_dev, t_cnt] + ([t_sym] if t_sym is not None else [])
+    if main is not None:
+        main.wait_stream(side)                             # the target tensors were produced on the side stream
+        for t_ in consts:
+            t_.record_stream(main)
+    lib = _lib.load()
+    S, P = I * B, I * B * Q
+    need = lib.parq_set_match_workspace_bytes(I, B, Q, nmax)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def enqueue():
+        with torch.no_grad():
+            lg = _stacked(out_dict_list, "pred_logits").detach().contiguous()
+            cp = _stacked(out_dict_list, "coord_pos").detach().contiguous()
+        packed = torch.empty(6 * P, dtype=torch.int32, device=dev)        # pairs [4][P] | pair_coef [P] | row_weight [P]
+        r2c = torch.empty(P, dtype=torch.int32, device=dev)
+        stats = torch.empty(S + 1, dtype=torch.int32, device=dev)
+        ws = torch.empty(need // 4, dtype=torch.int32, device=dev)
+        base = packed.data_ptr()
+        _lib.check(lib.parq_set_match(p(lg), p(cp), I, B, Q, ncls, p(tc), p(t_lab), p(t_cnt), nmax, float(matcher.cost_class),
+                                      float(matcher.cost_bbox), float(matcher.ratio), int(matcher.max_padding), seed & 0xFFFFFFFF, seed >> 32,
+                                      int(step) & 0xFFFFFFFF, p(ws), need, p(r2c), C.c_void_p(base), C.c_void_p(base + 16 * P),
+                                      C.c_void_p(base + 20 * P), p(stats), None, None, _lib.stream_ptr()), "parq_set_match")
+        matcher.last_device_match = {"packed": packed, "row_to_col": r2c, "stats": stats, "step": int(step)}     # introspection for tests
+        aux = {"P": P, "packed": packed, "loss_weight": loss_weight, "t_center": tc, "t_size": t_size, "t_rot": t_rot, "t_lab": t_lab,
+               "t_sym": t_sym, "nmax": int(nmax), "class_weight": cw_dev}
+        return _SetLossFn.apply(*[_stacked(out_dict_list, key) for key in _DIFF_KEYS], aux)
+    c, s_, r, k = enqueue()
+    if resolve is not None and resolve():                  # the step's one host wait; the forward was re-run: match its new outputs
+        c, s_, r, k = enqueue()
+    return {"center_loss": c, "size_loss": s_, "rot_loss": r, "cat_loss": k, "total_loss": c + s_ + r + k}
+
+
 # ---------------------------------------------------------------- batched evaluation (same numbers, ~40 launches per step)
 def decoder_loss_batched(out_dict_list, obbs_padded, T_world_local, sym=None, *, matcher, loss_weight, num_semcls, class_weight,
                          ready=None, targets_ready=None):
@@ -330,13 +433,7 @@ def decoder_loss_batched(out_dict_list, obbs_padded, T_world_local, sym=None, *,
         ids_np = [t["labels"].cpu().numpy() for t in targets]
         fused = DEVICE_SET_LOSS and dev.type == "cuda" and all(o[k].dtype == torch.float32 for o in out_dict_list for k in _DIFF_KEYS)
         if fused:                                          # padded targets of the device loss (parq_set_loss), built off the main stream
-            t_size = torch.zeros(B, nmax, 3, device=dev); t_rot = torch.zeros(B, nmax, 3, 3, device=dev)
-            t_lab = torch.zeros(B, nmax, dtype=torch.int32, device=dev)
-            for b, t in enumerate(targets):
-                n = len(t["labels"])
-                t_size[b, :n] = t["size"]; t_rot[b, :n] = t["T_rig_object"][:, :3, :3]; t_lab[b, :n] = t["labels"].to(torch.int32)
-            t_sym = raw(sym).to(dev)[:, :nmax].to(torch.int32).contiguous() if sym is not None else None
-            cw_dev = class_weight.to(device=dev, dtype=torch.float32).contiguous()
+            t_size, t_rot, t_lab, t_sym, cw_dev = _padded_targets(targets, sym, class_weight, B, nmax, dev)
             tc = tc.to(torch.float32)
     Q = out_dict_list[-1]["pred_logits"].shape[1]
 

@@ -58,6 +58,16 @@ class PARQ(_Base):
     def batch_invariant(self, on):
         self.box3d_decoder.batch_invariant = bool(on)
 
+    @property
+    def match_on_device(self):
+        """The decoder's training loss matches predictions to boxes on the device (``PARQDecoder.match_on_device``; the draw of a
+        capped neighbourhood is then keyed by ``box3d_decoder.match_seed`` and the decoder's step counter)."""
+        return self.box3d_decoder.match_on_device
+
+    @match_on_device.setter
+    def match_on_device(self, on):
+        self.box3d_decoder.match_on_device = bool(on)
+
     def view_window(self, B, V, h, w, T_world_local):
         """A streaming window of V view slots (parq_amd.ViewWindow) that also encodes: ``win.put_features(slot, features or
         (levels, layer), camera, T_camera_pseudoCam, T_world_pseudoCam)`` tokenises the put views only, with the window's
