@@ -678,6 +678,60 @@ int (parq_frames_resize)(const unsigned char *frames, int32_t N, int32_t H_in, i
                        int32_t pad_right, int32_t pad_bottom, const int32_t *plan_x, const int32_t *plan_y, int32_t H_out,
                        int32_t W_out, void *out, int32_t out_uint8, parq_stream stream);
 
+/* ---- a snippet's training targets from depth and poses (scripts/scannet_preprocessing/generate_scannet_anno_snippet.py:189-256,
+ * 317-329 over processing_utils.py:132-154,206-263,304-336: the reference's offline annotation pass), two launches ----------------
+ * Which boxes of a scene does a snippet of T frames see well enough to train on?  Per (scene, frame, box): the number of depth
+ * points inside the box and the share of the box's 2-D extent inside the colour image; per (scene, box): their maxima over the
+ * frames, a level, a valid flag; per scene: the valid rows compacted to the front of obbs_padded / sym.  The operations below and
+ * their order are the rule; nothing is contracted into a fused multiply-add.  Sums written a + b + c are ((a + b) + c).
+ * 1. Points, float32, per frame.  For the pixel (x, y) of depth value u (uint16):  d = (float)u / depth_scale, ONE correctly rounded
+ *    division;  v = ((float)x * d, (float)y * d, d, 1);  with Ki = depth_intrinsics_inv (B, 4, 4), the inverse of the scene's 4 x 4
+ *    depth intrinsics as numpy.linalg.inv gives it on the float32 matrix, made by the caller:
+ *      p_i = Ki[i][0] * v0 + Ki[i][1] * v1 + Ki[i][2] * v2 + Ki[i][3]      for i = 0, 1, 2  (row 3 is not used, as in the reference).
+ *    The pixel counts only if p_2 > 0.
+ * 2. Boxes in the camera frame, float64, per frame.  Corner k of a box, in the order of Obb3D.bb3corners_object (the reference's
+ *    get_corner_by_dims): (sx, sy, sz) = (0,0,0) (1,0,0) (1,1,0) (0,1,0) (0,0,1) (1,0,1) (1,1,1) (0,1,1) picks min / max of the row
+ *    [xmin xmax ymin ymax zmin zmax | R (9, row-major) t (3) | sem_id].  In the world frame, with the row's float32 values widened:
+ *      w_i = R[i][0] * cx + R[i][1] * cy + R[i][2] * cz + t_i,
+ *    or corners_world (B, N, 8, 3) float64 where that is given (not NULL).  T_world_camera (B, T, 12) float64 = R (9) t (3) is
+ *    inverted as a GENERAL affine matrix (ScanNet's pose files are orthonormal to six printed digits only): with c_ij the cofactors
+ *      c00 = a11 a22 - a12 a21,  c01 = a10 a22 - a12 a20,  c02 = a10 a21 - a11 a20,  det = a00 c00 - a01 c01 + a02 c02,
+ *      Ri = [ c00, a02 a21 - a01 a22, a01 a12 - a02 a11;  a12 a20 - a10 a22, a00 a22 - a02 a20, a02 a10 - a00 a12;
+ *             c02, a01 a20 - a00 a21, a00 a11 - a01 a10 ] / det  (each entry divided),   ti_i = -(Ri[i][0] t0 + Ri[i][1] t1 + Ri[i][2] t2),
+ *    the bottom row taken as 0 0 0 1;  camera corner  q_i = Ri[i][0] w0 + Ri[i][1] w1 + Ri[i][2] w2 + ti_i.
+ * 3. Inside test, float64 on the float32 points.  o = corner 4; edges e_a = corner 5 - o, e_b = corner 0 - o, e_c = corner 7 - o;
+ *    vv_e = e.x e.x + e.y e.y + e.z e.z;  r = (double)p - o;  m_e = r.x e.x + r.y e.y + r.z e.z.  The point is inside when
+ *    0 < m_e < vv_e for all three edges, both inequalities strict.  A padding row (all 19 values -1) holds no point.
+ * 4. Truncation ratio, float32, with Kc = color_intrinsics (B, 4, 4) and the colour image's (color_h, color_w).  Per corner
+ *    (x, y, z) = (float)q:  P_i = Kc[i][0] x + Kc[i][1] y + Kc[i][2] z + Kc[i][3];  zc = P_2 > 1 ? P_2 : 1 (the reference's own clamp,
+ *    kept with what it does to boxes nearer than 1 m);  u = P_0 / zc, v = P_1 / zc, correctly rounded.  Over the 8 corners in order
+ *    xmin, xmax, ymin, ymax (m = u < m ? u : m);  area = (xmax - xmin) * (ymax - ymin);  clip(a, hi) = a < 0 ? 0 : (a > hi ? hi : a)
+ *    of the x extents to color_w - 1 and of the y extents to color_h - 1;  inside = (cxmax - cxmin) * (cymax - cymin);
+ *    ratio = inside / (area > 1 ? area : 1).  A padding row has ratio 0.
+ * 5. Snippet level.  Per box the maximum over the T frames of the count and of the ratio.  level = the first i < n_levels with
+ *    count > level_counts[i] AND ratio > level_ratios[i] (both strict, float32 ratios), else n_levels; the reference's pairs are
+ *    (1000, 0.85) (500, 0.70) (100, 0.50).  valid = not a padding row and level < max_level (the reference's 3).
+ * 6. Output rows.  The valid boxes' rows, in their order, at the front of obbs_padded (B, max_box, 19), the rest -1; those beyond
+ *    max_box are dropped.  sym (B, S), entry n belonging to box n, 4-byte elements (sym_is_int: int32, else float32), is compacted
+ *    the same way into sym_out (B, S), -1 behind (and for a kept box n >= S); S = 0 and NULL: no sym.  num_valid (B) int32 = rows
+ *    written.  frame_points / frame_truncation (B, T, N), points_inside / truncation / difficulty / valid (B, N): int32 and float32.
+ * depth (B, T, Hd, Wd) uint16, contiguous, 2-byte aligned at least (rows of any length; 8-byte loads where a word lies inside the
+ * buffer).  workspace: parq_snippet_targets_workspace bytes (0 for sizes it refuses), 16-byte aligned, caller-owned: one int32
+ * partial per (frame, tile of 2048 pixels, box), summed in tile order.  Nothing is allocated, nothing synchronises, no atomics: the
+ * outputs are a pure function of the inputs.  level_counts / level_ratios are HOST arrays of n_levels entries.
+ * PARQ_ERR_ARG, with nothing launched: a NULL pointer (corners_world may be NULL; sym and sym_out with S = 0), B < 1 or above 1023,
+ * T outside [1, 64], N outside [1, 128], a depth or colour side outside [1, 8192], max_box < 1, S < 0, n_levels outside [1, 8],
+ * max_level outside [0, n_levels], depth_scale not above 0, an odd depth address, a workspace too small or not 16-byte aligned.
+ * (Parenthesised names: see parq_set_batch_invariant; the two are typed in _lib.EXTRA_SYMBOLS.) */
+size_t (parq_snippet_targets_workspace)(int32_t B, int32_t T, int32_t Hd, int32_t Wd, int32_t N);
+int (parq_snippet_targets)(const uint16_t *depth, int32_t B, int32_t T, int32_t Hd, int32_t Wd, const float *depth_intrinsics_inv,
+                         const float *color_intrinsics, int32_t color_h, int32_t color_w, const double *T_world_camera,
+                         const float *obbs, const double *corners_world /*NULL = from the rows*/, const void *sym, int32_t sym_is_int,
+                         int32_t S, int32_t N, int32_t max_box, const int32_t *level_counts_host, const float *level_ratios_host,
+                         int32_t n_levels, int32_t max_level, float depth_scale, void *workspace, size_t workspace_bytes,
+                         float *obbs_padded, void *sym_out, int32_t *num_valid, int32_t *frame_points, float *frame_truncation,
+                         int32_t *points_inside, float *truncation, int32_t *difficulty, int32_t *valid, parq_stream stream);
+
 /* ---- set loss for a given matching (model/parq_decoder.py:264-370), three launches --------------------------------------------
  * The reference matches predictions to boxes per (iteration, scene) on the host (utils/matcher.py: scipy LSAP + a capped random
  * neighbourhood) and then evaluates ~100 tiny tensor operations per step, forward and in autograd.  Given the matching, this entry

@@ -11,6 +11,8 @@ Public surface mirrors the reference (ymingxie/PARQ):
                  snippets in a device-resident track store: one enqueue per snippet batch returns a track id per query
     FramePrep, resize_frames, resized_intrinsics, gravity_aligned, snippet_local (datasets/transforms.py:211 ScanNetBaseTransform)
                  raw uint8 frames, intrinsics and T_world_camera prepared on the device into the batch PARQ.forward reads
+    SnippetTargets, select_views (scripts/scannet_preprocessing/generate_scannet_anno_snippet.py, the offline annotation pass)
+                 a snippet's obbs_padded / sym / num_valid from depth frames, intrinsics, poses and the scene's boxes, on the device
     ResnetFPN    (model/resnet_fpn.py:16)       wrapper of a user-supplied ResNet-FPN; its neck is fused into the tokenisation
 The compute lives in ``parq_amd/_C/libparq_hip.so`` (C ABI: include/parq_hip.h).
 """
@@ -46,4 +48,7 @@ def __getattr__(name):
     if name in ("FramePrep", "resize_frames", "resized_intrinsics", "gravity_aligned", "snippet_local"):
         from . import frames
         return getattr(frames, name)
+    if name in ("SnippetTargets", "select_views"):
+        from . import snippets
+        return getattr(snippets, name)
     raise AttributeError(name)

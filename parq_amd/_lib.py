@@ -159,6 +159,16 @@ MATCH_SYMBOLS = {
                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# a snippet's training targets (include/parq_hip.h parq_snippet_targets): a fourth table, for the same reason
+SNIPPET_SYMBOLS = {
+    "parq_snippet_targets_workspace": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "parq_snippet_targets": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
+                                       C.POINTER(_i32), C.POINTER(_f), _i32, _i32, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp]),
+}
+
+ALL_TABLES = (SYMBOLS, EXTRA_SYMBOLS, MATCH_SYMBOLS, SNIPPET_SYMBOLS)
+
 _lib = None
 
 
@@ -185,7 +195,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(EXTRA_SYMBOLS.items()) + list(MATCH_SYMBOLS.items()):
+    for name, (res, args) in [kv for table in ALL_TABLES for kv in table.items()]:
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -2833,6 +2833,45 @@ int parq_frames_resize(const unsigned char* frames, int32_t N, int32_t H_in, int
     return PARQ_OK;
 }
 
+size_t parq_snippet_targets_workspace(int32_t B, int32_t T, int32_t Hd, int32_t Wd, int32_t N) {
+    if (!snippet_sizes_ok(B, T, Hd, Wd, N)) return 0;
+    return snippet_workspace_bytes(B, T, Hd, Wd, N);
+}
+
+int parq_snippet_targets(const uint16_t* depth, int32_t B, int32_t T, int32_t Hd, int32_t Wd, const float* depth_intrinsics_inv,
+                         const float* color_intrinsics, int32_t color_h, int32_t color_w, const double* T_world_camera, const float* obbs,
+                         const double* corners_world, const void* sym, int32_t sym_is_int, int32_t S, int32_t N, int32_t max_box,
+                         const int32_t* level_counts_host, const float* level_ratios_host, int32_t n_levels, int32_t max_level,
+                         float depth_scale, void* workspace, size_t workspace_bytes, float* obbs_padded, void* sym_out, int32_t* num_valid,
+                         int32_t* frame_points, float* frame_truncation, int32_t* points_inside, float* truncation, int32_t* difficulty,
+                         int32_t* valid, parq_stream stream) {
+    if (!depth || !depth_intrinsics_inv || !color_intrinsics || !T_world_camera || !obbs || !level_counts_host || !level_ratios_host ||
+        !workspace || !obbs_padded || !num_valid || !frame_points || !frame_truncation || !points_inside || !truncation || !difficulty || !valid)
+        return fail(PARQ_ERR_ARG, "parq_snippet_targets: NULL argument");
+    if (S < 0 || (S > 0 && (!sym || !sym_out))) return fail(PARQ_ERR_ARG, "parq_snippet_targets: S = %d with sym %p, sym_out %p", S, sym, sym_out);
+    if (!snippet_sizes_ok(B, T, Hd, Wd, N))
+        return fail(PARQ_ERR_ARG, "parq_snippet_targets: B = %d scenes of T = %d frames of %d x %d (W x H), N = %d boxes: 1 <= B <= 1023, "
+                    "1 <= T <= 64, 1 <= N <= 128, every side in [1, 8192]", B, T, Wd, Hd, N);
+    if (color_h < 1 || color_w < 1 || color_h > 8192 || color_w > 8192)
+        return fail(PARQ_ERR_ARG, "parq_snippet_targets: colour image of %d x %d (W x H): every side in [1, 8192]", color_w, color_h);
+    if (max_box < 1 || max_box > (1 << 20)) return fail(PARQ_ERR_ARG, "parq_snippet_targets: max_box = %d", max_box);
+    if (S > (1 << 20)) return fail(PARQ_ERR_ARG, "parq_snippet_targets: S = %d", S);
+    if (sym_is_int != 0 && sym_is_int != 1) return fail(PARQ_ERR_ARG, "parq_snippet_targets: sym_is_int must be 0 or 1");
+    if (n_levels < 1 || n_levels > 8 || max_level < 0 || max_level > n_levels)
+        return fail(PARQ_ERR_ARG, "parq_snippet_targets: n_levels = %d, max_level = %d: 1 <= n_levels <= 8, 0 <= max_level <= n_levels", n_levels,
+                    max_level);
+    if (!(depth_scale > 0.0f)) return fail(PARQ_ERR_ARG, "parq_snippet_targets: depth_scale must be above 0");
+    if ((uintptr_t)depth & 1) return fail(PARQ_ERR_ARG, "parq_snippet_targets: the depth must be 2-byte aligned");
+    const size_t need = parq_snippet_targets_workspace(B, T, Hd, Wd, N);
+    if (workspace_bytes < need) return fail(PARQ_ERR_ARG, "parq_snippet_targets: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 15) return fail(PARQ_ERR_ARG, "parq_snippet_targets: the workspace must be 16-byte aligned");
+    HIPCHK(launch_snippet_targets(depth, B, T, Hd, Wd, depth_intrinsics_inv, color_intrinsics, color_h, color_w, T_world_camera, obbs,
+                                  corners_world, sym, sym_is_int, S, N, max_box, level_counts_host, level_ratios_host, n_levels, max_level,
+                                  depth_scale, workspace, obbs_padded, sym_out, num_valid, frame_points, frame_truncation, points_inside,
+                                  truncation, difficulty, valid, (hipStream_t)stream));
+    return PARQ_OK;
+}
+
 int parq_set_loss(const float* pred_logits, const float* center_unnormalized, const float* size_unnormalized, const float* ortho6d,
                   int32_t I, int32_t B, int32_t Q, int32_t num_classes, const float* t_center, const float* t_size, const float* t_rot,
                   const int32_t* t_label, const int32_t* t_sym, int32_t nmax, const int32_t* pairs, const float* pair_coef, int32_t P,

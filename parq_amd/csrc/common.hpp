@@ -805,6 +805,15 @@ hipError_t launch_draw_raster(const float* images, const void* parts, const void
 bool frames_sizes_ok(int N, int H_in, int W_in, int pl, int pt, int pr, int pb, int H_out, int W_out);
 hipError_t launch_frames_resize(const unsigned char* frames, int N, int H_in, int W_in, int pl, int pt, int pr, int pb, const int32_t* plan_x,
                                 const int32_t* plan_y, int H_out, int W_out, void* out, int out_uint8, hipStream_t s);
+// snippets.hip: a snippet's training targets from depth and poses (count + finalise: two launches).  ws: snippet_workspace_bytes
+bool snippet_sizes_ok(int B, int T, int Hd, int Wd, int N);
+size_t snippet_workspace_bytes(int B, int T, int Hd, int Wd, int N);
+hipError_t launch_snippet_targets(const uint16_t* depth, int B, int T, int Hd, int Wd, const float* kinv, const float* kcolor, int color_h,
+                                  int color_w, const double* poses, const float* obbs, const double* corners, const void* sym, int sym_is_int,
+                                  int S, int N, int max_box, const int32_t* level_counts, const float* level_ratios, int n_levels,
+                                  int max_level, float depth_scale, void* ws, float* obbs_out, void* sym_out, int32_t* num_valid,
+                                  int32_t* frame_points, float* frame_trunc, int32_t* points, float* trunc, int32_t* difficulty,
+                                  int32_t* valid, hipStream_t s);
 hipError_t launch_gemm_split(const float* X, int64_t ldx, const void* Whi, const void* Wlo, const float* bias, float* Y,
                              int64_t ldy, int M, int N, int K, int relu, const float* feat, int hw, hipStream_t s,
                              const float* scale_dev = nullptr, float scale_mul = 1.f, const float* xscale_dev = nullptr,
