@@ -822,7 +822,53 @@ int (parq_k_project_sample_backward)(const void *tokens, int32_t token_type, con
                                      int32_t C, int32_t Q, const float *g_tgt, float *g_tokens, float *g_ref, void *det_scratch,
                                      size_t det_scratch_bytes, parq_stream stream);
 
-/* T_camera_local = T_cp ∘ (inv(T_wp) ∘ T_wl)  (transformer_parq.py:298-300). */
+/* The attention backward (attn_bwd.hip), one launcher call at a time: D = rowsum(dO * O) by launch_attn_bwd_rowdot, then ONE call of
+ * launch_attn_bwd (parq_k_attention_backward) or of launch_attn_bwd_batched over n_it iterations that share K / V
+ * (parq_k_attention_backward_batched), with the strides parq_backward uses.  All tensors fp32; C = H * dh; lse is the forward's
+ * log-sum-exp in the log2 domain, [B*H][pad32(Lq)] per iteration (pad32 = rounded up to 32).
+ *   single, layout PARQ_ATTN_BWD_LAYOUT_SELF: q / k / v and gq / gk / gv are column blocks of packed [B][rows][3C] buffers (row stride
+ *     3C; Lq rows for q, Lk for k and v) — pass base, base + C, base + 2C.  PARQ_ATTN_BWD_LAYOUT_CROSS: q, gq [B][Lq][C]; k, v
+ *     head-major [B][H][Lk][dh]; gk = g, gv = g + C of a token-major [B][Lk][2C] buffer.  dO, O [B][Lq][C] in both.
+ *     gq is ADDED to (the caller zeroes it); gk / gv are written, or added to with accumulate_kv = 1.  use_absmax = 1 passes the
+ *     8-byte gradient-scale scratch: at head dim 64 and Lk >= 2048 that selects the split-precision kernel over the exact one.
+ *     det_scratch NULL / 0 bytes, or (head dim 64 only) B * H * ceil(Lk / 64) * pad32(Lq) * 64 floats, 16-byte aligned: the call
+ *     runs with the deterministic forms selected, as under parq_set_deterministic.
+ *   batched: q, dO, O, gq [n_it][B][Lq][C], lse [n_it][B*H][pad32(Lq)], k, v head-major [B][H][Lk][dh], gkv [B][Lk][2C] (written),
+ *     seeds[n_it] on the HOST (may be NULL when drop_p = 0).  Head dim 64 with Lk >= 2048, or head dim 256.  cache_terms 0: the
+ *     kernel reads the fp32 K / V; 3 / 1 / 8 (head dim 64): the entry converts K / V into the forward's split, single-product
+ *     (cache_kind 0 fp16, 1 bf16) or mode-4 stage cache inside the scratch and the kernel reads that.  gq is ADDED to.
+ * `scratch` holds parq_k_attention_backward_scratch_bytes(..., n_it, cache_terms) bytes (n_it = 0: the single call), 16-byte aligned:
+ * D, the scale words, the dQ partial slots, the packed tile images, the materialised / head-dim-256 scratch and the cache.
+ * Optional outputs (NULL to skip): D_out, the D rows ([n_it][B*H][pad32(Lq)]); masks_out ([n_it][B*H*Lq][Lk], drop_p > 0 only), the
+ * dropout keep-masks as a dropout of ones (1 / (1 - p) kept, 0 dropped) from launch_dropout_apply with row index bh * Lq + i; plan,
+ * four int32: the kernel family (PARQ_ATTN_BWD_*), key blocks per workgroup, dQ partial slots per (scene, head), QP (the padded query
+ * rows of the head-dim-256 composition; else 0), from the size functions the launchers themselves call.  With plan given and q NULL
+ * the entry fills the plan and returns without touching a device.
+ * PARQ_ERR_ARG: bad dims / layout / flags / cache combination, a NULL tensor, a det_scratch that is too small; PARQ_ERR_WORKSPACE:
+ * scratch too small or misaligned.  Every refusal comes before the first device call.
+ * (Parenthesised names: see parq_set_batch_invariant; the three are typed in _lib.EXTRA_SYMBOLS.) */
+enum { PARQ_ATTN_BWD_LAYOUT_SELF = 0, PARQ_ATTN_BWD_LAYOUT_CROSS = 1 };
+enum { PARQ_ATTN_BWD_VALU32 = 1,        /* attn_bwd_kernel<32> */
+       PARQ_ATTN_BWD_MFMA2 = 2,         /* attn_bwd_mfma_kernel<2>: head dim 64, Lk < 2048 */
+       PARQ_ATTN_BWD_MFMA8 = 3,         /* attn_bwd_mfma_kernel<8>: head dim 64, Lk >= 2048, no scale scratch */
+       PARQ_ATTN_BWD_SPLIT = 4,         /* attn_bwd_split_kernel */
+       PARQ_ATTN_BWD_MATERIALISED = 5,  /* head dims 128 / 256, single call */
+       PARQ_ATTN_BWD_SPLIT2 = 6,        /* attn_bwd_split2_kernel (batched, head dim 64) */
+       PARQ_ATTN_BWD_BATCHED256 = 7 };  /* attn_bwd_batched_256 */
+size_t (parq_k_attention_backward_scratch_bytes)(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t dh, int32_t n_it,
+                                                 int32_t cache_terms);
+int (parq_k_attention_backward)(const float *q, const float *k, const float *v, const float *dO, const float *O, const float *lse,
+                                int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t dh, int32_t layout, int32_t accumulate_kv,
+                                int32_t use_absmax, float drop_p, uint32_t seed, float *gq, float *gk, float *gv, void *scratch,
+                                size_t scratch_bytes, void *det_scratch, size_t det_scratch_bytes, float *D_out, float *masks_out,
+                                int32_t *plan, parq_stream stream);
+int (parq_k_attention_backward_batched)(const float *q, const float *k, const float *v, const float *dO, const float *O,
+                                        const float *lse, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t dh, int32_t n_it,
+                                        int32_t cache_terms, int32_t cache_kind, float drop_p, const uint32_t *seeds, float *gq,
+                                        float *gkv, void *scratch, size_t scratch_bytes, float *D_out, float *masks_out,
+                                        int32_t *plan, parq_stream stream);
+
+/* T_camera_local =T_cp ∘ (inv(T_wp) ∘ T_wl)  (transformer_parq.py:298-300). */
 int parq_k_camera_local(const float *T_cp, const float *T_wp, const float *T_wl, int32_t B, int32_t V,
                         float *T_cl, parq_stream stream);
 

@@ -149,6 +149,11 @@ EXTRA_SYMBOLS = {
     "parq_k_project_sample_backward_scratch_bytes": (_sz, [_i32, _i32, _i32]),
     "parq_k_project_sample_backward": (C.c_int, [_vp, _i32, _vp, _vp, _vp, C.POINTER(_f), _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                                  _vp, _sz, _vp]),
+    "parq_k_attention_backward_scratch_bytes": (_sz, [_i32] * 7),
+    "parq_k_attention_backward": (C.c_int, [_vp] * 6 + [_i32] * 8 + [_f, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp,
+                                                                    C.POINTER(_i32), _vp]),
+    "parq_k_attention_backward_batched": (C.c_int, [_vp] * 6 + [_i32] * 8 + [_f, C.POINTER(C.c_uint32), _vp, _vp, _vp, _sz, _vp, _vp,
+                                                                            C.POINTER(_i32), _vp]),
 }
 
 # the matcher of the set loss (include/parq_hip.h parq_set_match): a third table, the sizes of the two above being pinned by tests

@@ -2298,6 +2298,170 @@ int parq_k_project_sample_backward(const void* tokens, int32_t token_type, const
     return PARQ_OK;
 }
 
+// ------------------------------------------------------------------ the attention backward, one launcher call at a time
+// Float offsets of the parts of the one scratch both entries carve (each part a multiple of 64 floats); n_it = 0: the single call.
+namespace {
+struct AttnBwdCarve { int64_t D, absmax, kvmax, part, pack, mat, flag, cache, total; };
+AttnBwdCarve attn_bwd_carve(int B, int H, int Lq, int Lk, int dh, int n_it, int cache_terms) {
+    AttnBwdCarve c;
+    int64_t off = 0;
+    auto take = [&](int64_t n) { const int64_t o = off; off += (n + 63) / 64 * 64; return o; };
+    const int nt = n_it > 0 ? n_it : 1;
+    c.D = take((int64_t)nt * B * H * flash_lq_pad(Lq));
+    c.absmax = take(2);                                   // bits of max |dO|, the derived scale
+    c.kvmax = take(n_it > 0 ? 2 : 0);
+    c.part = take((int64_t)nt * (int64_t)attn_bwd_dq_partial_floats(B, H, Lq, Lk, dh, n_it > 0));
+    c.pack = take(n_it > 0 && dh == 64 ? (int64_t)attn_bwd_pack_floats(B, H, Lq, n_it) : 0);
+    if (n_it > 0) c.mat = take(dh == 256 ? (int64_t)attn_bwd_batched256_scratch_floats(n_it, Lq, Lk) : 0);
+    else c.mat = take(dh != 64 && dh != 32 ? (int64_t)attn_bwd_mat_scratch_floats(Lq, Lk, dh) : 0);
+    c.flag = take(cache_terms ? 64 : 0);                  // overflow flag of the cache conversion
+    c.cache = take(cache_terms ? (int64_t)(kvsplit_cache_bytes(B, H, Lk, cache_terms == 1 ? 1 : 3) / sizeof(float)) : 0);
+    c.total = off;
+    return c;
+}
+bool attn_bwd_dims_ok(int B, int H, int Lq, int Lk, int dh) {
+    return B >= 1 && H >= 1 && Lq >= 1 && Lk >= 1 && (dh == 32 || dh == 64 || dh == 128 || dh == 256) &&
+           (int64_t)B * H * Lq * (int64_t)Lk < ((int64_t)1 << 40) && (int64_t)B * H * flash_lq_pad(Lq) < INT32_MAX;
+}
+// keep-masks [B*H*Lq][Lk] of stream `seed`: a dropout of ones (1 / (1 - p) where kept, 0 where dropped), row index bh * Lq + i
+hipError_t attn_bwd_hook_masks(float* out, int B, int H, int Lq, int Lk, float p, uint32_t seed, hipStream_t s) {
+    hipError_t e = launch_fill(out, 1.f, (int64_t)B * H * Lq * Lk, s);
+    if (e != hipSuccess) return e;
+    return launch_dropout_apply(out, out, B * H * Lq, Lk, p, seed, s);
+}
+}  // namespace
+
+size_t parq_k_attention_backward_scratch_bytes(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t dh, int32_t n_it, int32_t cache_terms) {
+    if (!attn_bwd_dims_ok(B, H, Lq, Lk, dh) || n_it < 0 || n_it > 16) return 0;
+    if (!(cache_terms == 0 || cache_terms == 1 || cache_terms == 3 || cache_terms == 8) || (cache_terms && (n_it == 0 || dh != 64))) return 0;
+    return (size_t)attn_bwd_carve(B, H, Lq, Lk, dh, n_it, cache_terms).total * sizeof(float);
+}
+
+int parq_k_attention_backward(const float* q, const float* k, const float* v, const float* dO, const float* O, const float* lse,
+                              int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t dh, int32_t layout, int32_t accumulate_kv,
+                              int32_t use_absmax, float drop_p, uint32_t seed, float* gq, float* gk, float* gv, void* scratch,
+                              size_t scratch_bytes, void* det_scratch, size_t det_scratch_bytes, float* D_out, float* masks_out,
+                              int32_t* plan, parq_stream stream) {
+    if (!attn_bwd_dims_ok(B, H, Lq, Lk, dh)) return fail(PARQ_ERR_ARG, "bad dims (head dim 32 / 64 / 128 / 256)");
+    if (layout != PARQ_ATTN_BWD_LAYOUT_SELF && layout != PARQ_ATTN_BWD_LAYOUT_CROSS) return fail(PARQ_ERR_ARG, "layout must be 0 (packed q | k | v) or 1 (cross-attention), not %d", layout);
+    if ((accumulate_kv != 0 && accumulate_kv != 1) || (use_absmax != 0 && use_absmax != 1)) return fail(PARQ_ERR_ARG, "accumulate_kv and use_absmax must be 0 or 1");
+    if (!(drop_p >= 0.f && drop_p < 1.f)) return fail(PARQ_ERR_ARG, "drop_p must be in [0, 1)");
+    if ((det_scratch == nullptr) != (det_scratch_bytes == 0)) return fail(PARQ_ERR_ARG, "det_scratch and det_scratch_bytes: both or neither");
+    if (det_scratch && dh != 64) return fail(PARQ_ERR_ARG, "the deterministic form exists at head dim 64 only");
+    if (det_scratch && (det_scratch_bytes < (size_t)det_attn_dq_floats(B, H, Lq, Lk) * sizeof(float) || (reinterpret_cast<uintptr_t>(det_scratch) & 15u)))
+        return fail(PARQ_ERR_ARG, "det_scratch: B * H * ceil(Lk / 64) * pad32(Lq) * 64 floats, 16-byte aligned");
+    const int Lq_pad = flash_lq_pad(Lq);
+    const AttnBwdCarve cv = attn_bwd_carve(B, H, Lq, Lk, dh, 0, 0);
+    // the kernel family: the order of the tests in launch_attn_bwd (attn_bwd.hip); the slot count from the size functions it uses
+    if (plan) {
+        const bool long_keys = Lk >= 2048;
+        int fam = PARQ_ATTN_BWD_VALU32;
+        if (dh != 64 && dh != 32) fam = PARQ_ATTN_BWD_MATERIALISED;
+        else if (dh == 64 && long_keys && use_absmax) fam = PARQ_ATTN_BWD_SPLIT;
+        else if (dh == 64) fam = long_keys ? PARQ_ATTN_BWD_MFMA8 : PARQ_ATTN_BWD_MFMA2;
+        const int64_t slot = (int64_t)B * H * Lq_pad * 64;
+        int64_t slots = (int64_t)attn_bwd_dq_partial_floats(B, H, Lq, Lk, dh, false) / slot;
+        if (fam == PARQ_ATTN_BWD_MFMA2) slots = det_scratch ? det_attn_dq_floats(B, H, Lq, Lk) / slot : 0;
+        plan[0] = fam; plan[1] = 1; plan[2] = (int32_t)slots; plan[3] = 0;
+        if (!q) return PARQ_OK;                            // the plan alone: no device is touched
+    }
+    if (!q || !k || !v || !dO || !O || !lse || !gq || !gk || !gv || !scratch) return fail(PARQ_ERR_ARG, "NULL argument");
+    if (masks_out && !(drop_p > 0.f)) return fail(PARQ_ERR_ARG, "masks_out needs drop_p > 0");
+    if (scratch_bytes < (size_t)cv.total * sizeof(float) || (reinterpret_cast<uintptr_t>(scratch) & 15u))
+        return fail(PARQ_ERR_WORKSPACE, "scratch: parq_k_attention_backward_scratch_bytes(), 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    float* sp = static_cast<float*>(scratch);
+    const int64_t C = (int64_t)H * dh;
+    float* D = sp + cv.D;
+    HIPCHK(launch_attn_bwd_rowdot(dO, O, (int64_t)Lq * C, C, B, H, Lq, dh, D, s));
+    // self-attention: every operand a column block of a packed [B][rows][3C] buffer; cross-attention: q token-major, K / V head-major,
+    // gK | gV the two halves of a token-major [B][Lk][2C] buffer (the strides of do_backward_iter's two calls)
+    const bool self = layout == PARQ_ATTN_BWD_LAYOUT_SELF;
+    const int64_t qb = self ? (int64_t)Lq * 3 * C : (int64_t)Lq * C, qr = self ? 3 * C : C;
+    const int64_t kb = self ? (int64_t)Lk * 3 * C : (int64_t)H * Lk * dh, kh = self ? dh : (int64_t)Lk * dh, kr = self ? 3 * C : dh;
+    const int64_t gb = self ? (int64_t)Lk * 3 * C : (int64_t)Lk * 2 * C, gr = self ? 3 * C : 2 * C;
+    float* part = attn_bwd_dq_partial_floats(B, H, Lq, Lk, dh) ? sp + cv.part : nullptr;
+    unsigned int* absmax = use_absmax ? reinterpret_cast<unsigned int*>(sp + cv.absmax) : nullptr;
+    float* mat = (dh == 64 || dh == 32) ? nullptr : sp + cv.mat;
+    auto run = [&]() {
+        return launch_attn_bwd(q, qb, dh, qr, k, kb, kh, kr, v, kb, kh, kr, dO, (int64_t)Lq * C, dh, C, lse, D, gq, qb, dh, qr, gk, gb, dh, gr,
+                               gv, gb, dh, gr, B, H, Lq, Lk, dh, accumulate_kv, s, part, drop_p, seed, absmax, mat);
+    };
+    if (det_scratch) {                 // launch_attn_bwd takes its fixed-order forms while a DetScope is alive on this thread
+        DetScope det(static_cast<float*>(det_scratch), (int64_t)(det_scratch_bytes / sizeof(float)));
+        HIPCHK(run());
+    } else {
+        HIPCHK(run());
+    }
+    if (D_out) HIPCHK(hipMemcpyAsync(D_out, D, (size_t)B * H * Lq_pad * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (masks_out) HIPCHK(attn_bwd_hook_masks(masks_out, B, H, Lq, Lk, drop_p, seed, s));
+    return PARQ_OK;
+}
+
+int parq_k_attention_backward_batched(const float* q, const float* k, const float* v, const float* dO, const float* O, const float* lse,
+                                      int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t dh, int32_t n_it, int32_t cache_terms,
+                                      int32_t cache_kind, float drop_p, const uint32_t* seeds, float* gq, float* gkv, void* scratch,
+                                      size_t scratch_bytes, float* D_out, float* masks_out, int32_t* plan, parq_stream stream) {
+    if (!attn_bwd_dims_ok(B, H, Lq, Lk, dh)) return fail(PARQ_ERR_ARG, "bad dims");
+    if (n_it < 1 || n_it > 16) return fail(PARQ_ERR_ARG, "1 <= n_it <= 16");
+    if (!(dh == 256 || (dh == 64 && Lk >= 2048))) return fail(PARQ_ERR_ARG, "the batched backward serves head dim 64 with Lk >= 2048, and head dim 256");
+    if (!(cache_terms == 0 || cache_terms == 1 || cache_terms == 3 || cache_terms == 8)) return fail(PARQ_ERR_ARG, "cache_terms must be 0, 1, 3 or 8");
+    if (cache_terms && dh != 64) return fail(PARQ_ERR_ARG, "the backward reads the 16-bit cache at head dim 64 only");
+    if (cache_terms == 8 && !flash_split8_supported(64, Lk)) return fail(PARQ_ERR_ARG, "cache_terms 8 needs a key count that is a multiple of 64");
+    if (cache_kind != kF16 && cache_kind != kBF16) return fail(PARQ_ERR_ARG, "cache_kind must be 0 (fp16) or 1 (bf16)");
+    if (cache_kind == kBF16 && cache_terms != 1) return fail(PARQ_ERR_ARG, "bf16 is a single-product cache (cache_terms 1)");
+    if (!(drop_p >= 0.f && drop_p < 1.f)) return fail(PARQ_ERR_ARG, "drop_p must be in [0, 1)");
+    if (drop_p > 0.f && !seeds) return fail(PARQ_ERR_ARG, "drop_p > 0 needs seeds[n_it]");
+    const int Lq_pad = flash_lq_pad(Lq);
+    const AttnBwdCarve cv = attn_bwd_carve(B, H, Lq, Lk, dh, n_it, cache_terms);
+    if (plan) {
+        const int64_t slot = (int64_t)B * H * Lq_pad * 64;
+        plan[0] = dh == 256 ? PARQ_ATTN_BWD_BATCHED256 : PARQ_ATTN_BWD_SPLIT2;
+        plan[1] = dh == 256 ? 1 : attn_bwd_kb_group(B, H, Lk);
+        plan[2] = (int32_t)((int64_t)attn_bwd_dq_partial_floats(B, H, Lq, Lk, dh, true) / slot);
+        // QP out of the scratch size: attn_bwd_batched256_scratch_floats = QP (2 Lk + 1281) + 1040
+        plan[3] = dh == 256 ? (int32_t)(((int64_t)attn_bwd_batched256_scratch_floats(n_it, Lq, Lk) - 1040) / (2 * (int64_t)Lk + 1281)) : 0;
+        if (!q) return PARQ_OK;                            // the plan alone: no device is touched
+    }
+    if (!q || !k || !v || !dO || !O || !lse || !gq || !gkv || !scratch) return fail(PARQ_ERR_ARG, "NULL argument");
+    if (masks_out && !(drop_p > 0.f)) return fail(PARQ_ERR_ARG, "masks_out needs drop_p > 0");
+    if (scratch_bytes < (size_t)cv.total * sizeof(float) || (reinterpret_cast<uintptr_t>(scratch) & 15u))
+        return fail(PARQ_ERR_WORKSPACE, "scratch: parq_k_attention_backward_scratch_bytes(), 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    float* sp = static_cast<float*>(scratch);
+    const int64_t C = (int64_t)H * dh, MC = (int64_t)B * Lq * C, D_it = (int64_t)B * H * Lq_pad;
+    float* D = sp + cv.D;
+    int64_t q_off[16], lse_off[16];
+    for (int t = 0; t < n_it; ++t) {
+        q_off[t] = t * MC;
+        lse_off[t] = t * D_it;
+        HIPCHK(launch_attn_bwd_rowdot(dO + t * MC, O + t * MC, (int64_t)Lq * C, C, B, H, Lq, dh, D + t * D_it, s));
+    }
+    const void* cache = nullptr;
+    if (cache_terms) {                 // the cache as the forward's projection leaves it, built from the fp32 K / V
+        char* cb = reinterpret_cast<char*>(sp + cv.cache);
+        const int64_t kb = (int64_t)H * Lk * dh, kh = (int64_t)Lk * dh;
+        if (cache_terms == 8) {
+            HIPCHK(launch_kvsplit8_convert(k, v, kb, kh, dh, kb, kh, dh, B, H, Lk, cb, s));
+        } else {
+            int* flag = reinterpret_cast<int*>(sp + cv.flag);
+            HIPCHK(hipMemsetAsync(flag, 0, 256, s));
+            HIPCHK(launch_kvsplit_convert(k, v, kb, kh, dh, kb, kh, dh, B, H, Lk, cb, flag, s, cache_terms, cache_kind));
+        }
+        cache = cb;
+    }
+    HIPCHK(launch_attn_bwd_batched(q, q_off, (int64_t)Lq * C, dh, C, k, (int64_t)H * Lk * dh, (int64_t)Lk * dh, dh, v, (int64_t)H * Lk * dh,
+                                   (int64_t)Lk * dh, dh, dO, MC, (int64_t)Lq * C, dh, C, lse, lse_off, D, D_it, gq, MC, (int64_t)Lq * C, dh, C,
+                                   gkv, (int64_t)Lk * 2 * C, dh, 2 * C, gkv + C, (int64_t)Lk * 2 * C, dh, 2 * C, B, H, Lq, Lk, dh, n_it, s,
+                                   dh == 64 ? sp + cv.part : nullptr, drop_p, seeds, reinterpret_cast<unsigned int*>(sp + cv.absmax),
+                                   reinterpret_cast<unsigned int*>(sp + cv.kvmax), dh == 64 ? sp + cv.pack : nullptr,
+                                   dh == 256 ? sp + cv.mat : nullptr, cache, cache_terms, cache_kind));
+    if (D_out) HIPCHK(hipMemcpyAsync(D_out, D, (size_t)n_it * D_it * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (masks_out)
+        for (int t = 0; t < n_it; ++t) HIPCHK(attn_bwd_hook_masks(masks_out + (int64_t)t * B * H * Lq * Lk, B, H, Lq, Lk, drop_p, seeds[t], s));
+    return PARQ_OK;
+}
+
 int parq_k_linear(const float* X, const float* X2, const float* W, const float* bias, const float* R, float* Y,
                   int32_t M, int32_t N, int32_t K, int32_t relu, parq_stream stream) {
     if (!X || !W || !Y || M < 1 || N < 1 || K < 32 || K % 32 != 0) return fail(PARQ_ERR_ARG, "bad argument (K must be a multiple of 32)");

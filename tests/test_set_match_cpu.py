@@ -207,7 +207,7 @@ def test_header_declares_the_entry_points_and_the_binding_types_them():
             kind = C.c_void_p if "*" in p else {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "float": C.c_float, "size_t": C.c_size_t,
                                                 "parq_stream": C.c_void_p}[p.split()[0]]
             assert a is kind, (name, p)
-    assert len(_lib.SYMBOLS) == 71 and len(_lib.EXTRA_SYMBOLS) == 14 and len(_lib.MATCH_SYMBOLS) == 2
+    assert len(_lib.SYMBOLS) == 71 and len(_lib.EXTRA_SYMBOLS) == 17 and len(_lib.MATCH_SYMBOLS) == 2
     assert "87" in open(os.path.join(ROOT, "README.md")).read()
 
 
