@@ -618,6 +618,61 @@ int (parq_tracks_update)(void *store, int32_t S_cap, int32_t max_tracks, const i
                        float conf_thresh, float iou_thresh, void *workspace, size_t workspace_bytes, int32_t *track_id,
                        float *iou_out /*NULL in normal use*/, parq_stream stream);
 
+/* ---- the evaluator's ground-truth tracks on the device (utils/f1_eval.py:354-370, 416-471 make_gt_list + matching_gt) ------------
+ * A second track store, of the layout above, fed with LABELLED boxes: parq_tracks_update's rule with another step 1.
+ * Per call: slots_host (B) as above; visits_host (B) int32 on the HOST: how many ground-truth updates the scene's slot has had
+ * before this one (the caller counts them; >= 0); corners_world (B,P,8,3) float32; labels (B,P) int32; valid (B,P) bytes; iou_out
+ * (B,P,max_tracks) float32 or NULL, as above.
+ *  1. Selection.  The rows with valid != 0, in row order: D of them.  Row r, the p-th of them (p from 0), becomes a detection with
+ *     label labels[r] (stored as it is, in range or not), score 1.0f and the corners of row r moved by ONE scalar, the jitter:
+ *       stored = (float) ((double) corner + jitter)            for all 24 coordinates of the box; the rounding is part of the rule.
+ *     The reference draws that scalar from N(0, 1e-6) with NumPy's global generator, box by box; a device store cannot, so the
+ *     jitter here is a hash (the ONE documented difference from the reference's evaluator).  With mix and the chaining of
+ *     parq_set_match's keys,
+ *       h = 0x9e3779b9; for w in (seed_lo, seed_hi, slot, visit, p): h = mix((h ^ w) + 0x9e3779b9);
+ *       w0 = mix((h ^ 0) + 0x9e3779b9);   w1 = mix((h ^ 1) + 0x9e3779b9);                     (the word index, 0 or 1, is the sixth word)
+ *       u = (w0 & 0xffff) + (w0 >> 16) + (w1 & 0xffff) + (w1 >> 16) - 131070;                   an integer in [-131070, 131070]
+ *       jitter = (double) u * 2.6428997918226275e-08             (the float64 nearest 1.7320508075688772e-3 / 65536: one product)
+ *     seed_lo / seed_hi are the halves of `seed`, slot is slots_host[b], visit is visits_host[b].  The sum of four uniform 16-bit
+ *     fields has mean 0 and standard deviation 65536 / sqrt(3) to within 1e-9 of it, so the jitter has mean 0, standard deviation
+ *     1e-3 and |jitter| <= 3.4641e-3.  Integer operations and one float64 product: NumPy and the kernel give the same bits
+ *     (tests/f1_device_cases.py gt_jitter; parq_amd/f1_eval.py hash_jitter is the host calculator's copy).
+ *  2-5. As parq_tracks_update: IoU on the jittered corners, the assignment, a match unless IoU < iou_thresh, births in row order,
+ *     overflow into `dropped`.  Scores are 1 on both sides, so a matched track is never replaced (1 < 1 is false), as on the host.
+ *     The three later kernels are parq_tracks_update's own.
+ * The same promises: no atomics, nothing allocated, the call only enqueues, a slot whose count is outside [0, max_tracks] is left
+ * untouched.  workspace: parq_gt_tracks_update_workspace_bytes(B, P, max_tracks) bytes, 16-byte aligned (it also holds the jittered
+ * corners).  B = 0 is valid and launches nothing.  PARQ_ERR_ARG, with nothing launched: P or max_tracks outside [1, 2048], a
+ * negative count or visit, a NULL pointer (iou_out excepted), a slot outside [0, S_cap) or listed twice, a workspace too small or
+ * misaligned.  (Parenthesised names, as above; the four entries of this section and the next are typed in _lib.EVAL_SYMBOLS.) */
+size_t (parq_gt_tracks_update_workspace_bytes)(int32_t B, int32_t P, int32_t max_tracks);
+int (parq_gt_tracks_update)(void *store, int32_t S_cap, int32_t max_tracks, const int32_t *slots_host, const int32_t *visits_host,
+                          int32_t B, const float *corners_world, const int32_t *labels, const unsigned char *valid, int32_t P,
+                          float iou_thresh, uint64_t seed, void *workspace, size_t workspace_bytes,
+                          float *iou_out /*NULL in normal use*/, parq_stream stream);
+
+/* ---- the evaluator's end-of-epoch counts on the device (utils/f1_eval.py:36-62, 473-502 count_matches over all scenes), two launches
+ * pred_store / gt_store: two track stores (capacities pred_max_tracks / gt_max_tracks) in which slot s < S is the same scene.
+ * thresholds_host (T) float64 on the HOST, 1 <= T <= 8; K care classes, 1 <= K <= 32 (the evaluator's 9).
+ * counts (2 + T, K) int64 on the device: row 0 the ground-truth tracks of each class, row 1 the prediction tracks, row 2 + t the
+ * true positives at thresholds_host[t].  invalid (2) int64: ground-truth / prediction tracks whose label is outside [0, K), which
+ * are counted nowhere else.  best_iou (S, gt_max_tracks) float64 or NULL: for tests, best[i] of every ground-truth track (rows from
+ * a slot's count on are not written).
+ * The rule.  The reference's count does not consume a prediction at its first match, so it does not depend on any order: per scene
+ *   best[i] = max over the scene's prediction tracks j with label_j == label_i of iou3d(canon(gt i), canon(pred j)),
+ * iou3d and canon as in parq_tracks_update's step 2 (float64 from the stores' float32 corners, the ground truth as the first box),
+ * 0 where there is no such prediction; a NaN never raises the maximum.  A ground-truth track i of class c in [0, K) is a true
+ * positive at threshold t when best[i] > thresholds_host[t], a float64 comparison, strict.  Pairs of different labels are skipped
+ * before the clip; one IoU pass serves every threshold.  A slot whose count is outside [0, capacity] counts as empty.
+ * No atomics (int32 partials per scene and block of rows in the workspace, summed by the second launch), nothing allocated, the
+ * call only enqueues.  workspace: parq_f1_counts_workspace_bytes(S, gt_max_tracks, T, K) bytes, 16-byte aligned.  S = 0 is valid:
+ * counts and invalid are zeroed.  PARQ_ERR_ARG, with nothing launched: S negative or above 65535, a capacity outside [1, 2048], T
+ * outside [1, 8], K outside [1, 32], a NULL pointer (best_iou excepted), a workspace too small or misaligned. */
+size_t (parq_f1_counts_workspace_bytes)(int32_t S, int32_t gt_max_tracks, int32_t T, int32_t K);
+int (parq_f1_counts)(const void *pred_store, int32_t pred_max_tracks, const void *gt_store, int32_t gt_max_tracks, int32_t S,
+                   const double *thresholds_host, int32_t T, int32_t K, void *workspace, size_t workspace_bytes, int64_t *counts,
+                   int64_t *invalid, double *best_iou /*NULL in normal use*/, parq_stream stream);
+
 /* ---- boxes drawn into the normalised input views (utils/parq_utils.py:141-211 draw_detections), three launches ------------------
  * images (B,T,3,H,W) float32; camera (B,T,6) = [w, h, fx, fy, cx, cy]; T_camera_pseudoCam, T_world_pseudoCam (B,T,12) = [R row-major |
  * t]; corners_world (B,M,8,3) float32 in Obb3D.bb3corners_object order; labels (B,M) int32; keep (B,M) bytes or NULL (all);

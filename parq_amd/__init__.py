@@ -9,6 +9,8 @@ Public surface mirrors the reference (ymingxie/PARQ):
     draw_boxes, box_colors (utils/parq_utils.py:134,141 get_colors / draw_detections)  boxes drawn into the views on the device
     SceneTracks  (utils/f1_eval.py:293 matching_pred, there on the host and inside the evaluator only)  detections followed across
                  snippets in a device-resident track store: one enqueue per snippet batch returns a track id per query
+    f1_counts    (utils/f1_eval.py:36 count_matches over all scenes)  the evaluator's per-class counts from a prediction and a
+                 ground-truth SceneTracks, on the device
     FramePrep, resize_frames, resized_intrinsics, gravity_aligned, snippet_local (datasets/transforms.py:211 ScanNetBaseTransform)
                  raw uint8 frames, intrinsics and T_world_camera prepared on the device into the batch PARQ.forward reads
     SnippetTargets, select_views (scripts/scannet_preprocessing/generate_scannet_anno_snippet.py, the offline annotation pass)
@@ -42,9 +44,9 @@ def __getattr__(name):
     if name in ("draw_boxes", "box_colors"):
         from . import draw
         return getattr(draw, name)
-    if name == "SceneTracks":
-        from .scene_tracks import SceneTracks
-        return SceneTracks
+    if name in ("SceneTracks", "f1_counts"):
+        from . import scene_tracks
+        return getattr(scene_tracks, name)
     if name in ("FramePrep", "resize_frames", "resized_intrinsics", "gravity_aligned", "snippet_local"):
         from . import frames
         return getattr(frames, name)

@@ -174,6 +174,16 @@ SNIPPET_SYMBOLS = {
 
 ALL_TABLES = (SYMBOLS, EXTRA_SYMBOLS, MATCH_SYMBOLS, SNIPPET_SYMBOLS)
 
+# the evaluator's ground-truth store and end-of-epoch counts (include/parq_hip.h parq_gt_tracks_update, parq_f1_counts): typed by load()
+# like the tables above, but not a member of ALL_TABLES, whose total tests/test_snippets_cpu.py pins
+EVAL_SYMBOLS = {
+    "parq_gt_tracks_update_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "parq_gt_tracks_update": (C.c_int, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _vp, _vp, _i32, _f, C.c_uint64, _vp, _sz,
+                                        _vp, _vp]),
+    "parq_f1_counts_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "parq_f1_counts": (C.c_int, [_vp, _i32, _vp, _i32, _i32, C.POINTER(C.c_double), _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -200,7 +210,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in [kv for table in ALL_TABLES for kv in table.items()]:
+    for name, (res, args) in [kv for table in ALL_TABLES + (EVAL_SYMBOLS,) for kv in table.items()]:
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

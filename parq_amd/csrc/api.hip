@@ -2925,6 +2925,70 @@ int parq_tracks_update(void* store, int32_t S_cap, int32_t max_tracks, const int
     return PARQ_OK;
 }
 
+size_t parq_gt_tracks_update_workspace_bytes(int32_t B, int32_t P, int32_t max_tracks) {
+    if (B < 0 || P < 1 || P > 2048 || max_tracks < 1 || max_tracks > 2048) return 0;
+    return gt_tracks_update_workspace_bytes(B, P, max_tracks);
+}
+
+int parq_gt_tracks_update(void* store, int32_t S_cap, int32_t max_tracks, const int32_t* slots_host, const int32_t* visits_host, int32_t B,
+                          const float* corners_world, const int32_t* labels, const unsigned char* valid, int32_t P, float iou_thresh,
+                          uint64_t seed, void* workspace, size_t workspace_bytes, float* iou_out, parq_stream stream) {
+    if (B < 0 || S_cap < 0) return fail(PARQ_ERR_ARG, "parq_gt_tracks_update: negative count");
+    if (P < 1 || P > 2048 || max_tracks < 1 || max_tracks > 2048)
+        return fail(PARQ_ERR_ARG, "parq_gt_tracks_update: P = %d, max_tracks = %d; 1 <= P, max_tracks <= 2048", P, max_tracks);
+    if (B == 0) return PARQ_OK;                                         // no scene: no launch
+    if (!store || !slots_host || !visits_host || !corners_world || !labels || !valid || !workspace)
+        return fail(PARQ_ERR_ARG, "parq_gt_tracks_update: NULL argument");
+    {
+        std::vector<char> seen((size_t)S_cap, 0);
+        for (int b = 0; b < B; ++b) {
+            const int32_t sl = slots_host[b];
+            if (sl < 0 || sl >= S_cap) return fail(PARQ_ERR_ARG, "parq_gt_tracks_update: slot %d of scene %d outside [0, %d)", sl, b, S_cap);
+            if (seen[(size_t)sl]) return fail(PARQ_ERR_ARG, "parq_gt_tracks_update: slot %d listed twice in one call", sl);
+            if (visits_host[b] < 0) return fail(PARQ_ERR_ARG, "parq_gt_tracks_update: visit %d of scene %d is negative", visits_host[b], b);
+            seen[(size_t)sl] = 1;
+        }
+    }
+    const size_t need = parq_gt_tracks_update_workspace_bytes(B, P, max_tracks);
+    if (workspace_bytes < need) return fail(PARQ_ERR_ARG, "parq_gt_tracks_update: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 15) return fail(PARQ_ERR_ARG, "parq_gt_tracks_update: the workspace must be 16-byte aligned");
+    for (int b0 = 0; b0 < B; b0 += kTrackChunk)
+        HIPCHK(launch_gt_tracks_update(static_cast<int32_t*>(store), max_tracks, slots_host, visits_host, b0, std::min(B - b0, (int)kTrackChunk), B,
+                                       corners_world, labels, valid, P, iou_thresh, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32),
+                                       workspace, iou_out, (hipStream_t)stream));
+    return PARQ_OK;
+}
+
+size_t parq_f1_counts_workspace_bytes(int32_t S, int32_t gt_max_tracks, int32_t T, int32_t K) {
+    if (S < 0 || S > 65535 || gt_max_tracks < 1 || gt_max_tracks > 2048 || T < 1 || T > kF1MaxThresholds || K < 1 || K > kF1MaxClasses) return 0;
+    return f1_counts_workspace_bytes(S, gt_max_tracks, T, K);
+}
+
+int parq_f1_counts(const void* pred_store, int32_t pred_max_tracks, const void* gt_store, int32_t gt_max_tracks, int32_t S,
+                   const double* thresholds_host, int32_t T, int32_t K, void* workspace, size_t workspace_bytes, int64_t* counts,
+                   int64_t* invalid, double* best_iou, parq_stream stream) {
+    if (S < 0) return fail(PARQ_ERR_ARG, "parq_f1_counts: negative count");
+    if (S > 65535 || pred_max_tracks < 1 || pred_max_tracks > 2048 || gt_max_tracks < 1 || gt_max_tracks > 2048 || T < 1 || T > kF1MaxThresholds ||
+        K < 1 || K > kF1MaxClasses)
+        return fail(PARQ_ERR_ARG, "parq_f1_counts: S = %d, capacities %d / %d, T = %d, K = %d; S <= 65535, 1 <= capacity <= 2048, 1 <= T <= %d, "
+                    "1 <= K <= %d", S, pred_max_tracks, gt_max_tracks, T, K, kF1MaxThresholds, kF1MaxClasses);
+    if (!thresholds_host || !counts || !invalid) return fail(PARQ_ERR_ARG, "parq_f1_counts: NULL argument");
+    if (S == 0) {                                                       // no scene: the counts are zero
+        HIPCHK(hipMemsetAsync(counts, 0, (size_t)(2 + T) * K * 8, (hipStream_t)stream));
+        HIPCHK(hipMemsetAsync(invalid, 0, 16, (hipStream_t)stream));
+        return PARQ_OK;
+    }
+    if (!pred_store || !gt_store || !workspace) return fail(PARQ_ERR_ARG, "parq_f1_counts: NULL argument");
+    const size_t need = parq_f1_counts_workspace_bytes(S, gt_max_tracks, T, K);
+    if (workspace_bytes < need) return fail(PARQ_ERR_ARG, "parq_f1_counts: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 15) return fail(PARQ_ERR_ARG, "parq_f1_counts: the workspace must be 16-byte aligned");
+    F1Thresholds thr;
+    for (int t = 0; t < kF1MaxThresholds; ++t) thr.thr[t] = t < T ? thresholds_host[t] : 0.0;
+    HIPCHK(launch_f1_counts(static_cast<const int32_t*>(pred_store), pred_max_tracks, static_cast<const int32_t*>(gt_store), gt_max_tracks, S,
+                            thr, T, K, workspace, counts, invalid, best_iou, (hipStream_t)stream));
+    return PARQ_OK;
+}
+
 size_t parq_set_match_workspace_bytes(int32_t I, int32_t B, int32_t Q, int32_t nmax) {
     if (I < 0 || B < 0 || Q < 1 || Q > 2048 || nmax < 1 || nmax > 2048 || (int64_t)I * B * Q > (int64_t)(1 << 28)) return 0;
     return set_match_workspace_bytes(I, B, Q, nmax);

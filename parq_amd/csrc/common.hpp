@@ -259,6 +259,9 @@ __host__ __device__ constexpr uint32_t rng_mix(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
     return x;
 }
+// The chained hash of the matcher's keys (setmatch.hip) and of the ground-truth jitter (tracks.hip): h = 0x9e3779b9, then one
+// hash_absorb per 32-bit word.  tests/set_match_cases.py mix32 is rng_mix.
+__host__ __device__ constexpr uint32_t hash_absorb(uint32_t h, uint32_t w) { return rng_mix((h ^ w) + 0x9e3779b9U); }
 __host__ __device__ inline uint32_t rng_stream(uint32_t base, uint32_t stream) { return rng_mix(base ^ rng_mix(stream * 0x9e3779b9U + 0x85ebca6bU)); }
 // The index space of a dropout site is 2-D, (row, col): activations (m, n); attention probabilities (bh * Lq + q, key).  The row
 // part of the hash is computed once per row (per lane in the forward attention kernels, per query tile in the backward ones),
@@ -784,6 +787,22 @@ size_t tracks_update_workspace_bytes(int B, int Q, int max_tracks);
 hipError_t launch_tracks_update(int32_t* store, int max_tracks, const int32_t* slots_host, int b0, int nb, const float* corners_world,
                                 const float* prob, const unsigned char* mask, int Q, int K, float conf, float iou_thresh, void* ws,
                                 int32_t* track_id, float* iou_out, hipStream_t s);
+// the ground-truth store's update (parq_gt_tracks_update): a select launch of its own (valid rows, jittered corners, score 1), then
+// launch_tracks_update's IoU and assignment launches.  ws: gt_tracks_update_workspace_bytes, 16-byte aligned
+size_t gt_tracks_update_workspace_bytes(int B, int P, int max_tracks);
+hipError_t launch_gt_tracks_update(int32_t* store, int max_tracks, const int32_t* slots_host, const int32_t* visits_host, int b0, int nb, int B,
+                                   const float* corners_world, const int32_t* labels, const unsigned char* valid, int P, float iou_thresh,
+                                   uint32_t seed_lo, uint32_t seed_hi, void* ws, float* iou_out, hipStream_t s);
+// f1_counts.hip: per-class ground-truth / prediction / true-positive counts of S scenes from a prediction and a ground-truth track
+// store (two launches); ws: f1_counts_workspace_bytes
+constexpr int kF1MaxThresholds = 8, kF1MaxClasses = 32;
+size_t f1_counts_workspace_bytes(int S, int gt_max_tracks, int T, int K);
+struct F1Thresholds {
+    double thr[kF1MaxThresholds];
+};
+hipError_t launch_f1_counts(const int32_t* pred_store, int pred_max_tracks, const int32_t* gt_store, int gt_max_tracks, int S,
+                            const F1Thresholds& thr, int T, int K, void* ws, int64_t* counts, int64_t* invalid, double* best_iou,
+                            hipStream_t s);
 // setmatch.hip: the set loss's matcher for all I * B (iteration, scene) problems (cost, launch_assign_max, pairs, finish: four
 // launches; I * B >= 1, Q and nmax in [1, 2048]); ws: set_match_workspace_bytes, 16-byte aligned
 size_t set_match_workspace_bytes(int I, int B, int Q, int nmax);

@@ -1,5 +1,6 @@
 // The per-pair routine of the tracker's oriented-box IoU, shared by obb_iou.hip (parq_obb_iou: float64 canonical corners) and
-// tracks.hip (parq_tracks_update: float32 world corners made canonical on the fly): ONE text, so the two entries cannot drift.
+// tracks.hip / f1_counts.hip (parq_tracks_update, parq_f1_counts: float32 world corners made canonical on the fly, load_canonical
+// below): ONE text, so the entries cannot drift.
 //   boxes: the 8 corners f1_eval.canonical() produces, float64; footprint polygon = corners 3, 2, 1, 0 in (x, z);
 //   Sutherland-Hodgman clip of footprint A against footprint B with the host routine's strict inside test and crossing formula in
 //   the same operation order, shoelace area, overlap height min(y of corner 0) - max(y of corner 4), volumes from three edges.
@@ -33,6 +34,28 @@ __device__ __forceinline__ bool load_box(const double* p, Corners& c) {
         if (i < 15) c.v[i] = x;
     }
     return nan;
+}
+
+constexpr double kCosHalfPi = 6.123233995736766e-17;
+
+// f1_eval.canonical() of float32 world corners (a track store's, or a batch's): corners [4,0,1,5,7] (the first five of the
+// re-ordering, all the routine reads), (x, y, z) -> (x, c y - z, y + c z); true when any of the 24 values is not finite
+__device__ __forceinline__ bool load_canonical(const float* p, Corners& c) {
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < 24; ++i) {
+        const float x = p[i];
+        bad |= !(fabsf(x) <= 3.402823466e38f);
+    }
+    constexpr int face[5] = {4, 0, 1, 5, 7};
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const double x = (double)p[3 * face[i]], y = (double)p[3 * face[i] + 1], z = (double)p[3 * face[i] + 2];
+        c.v[3 * i] = x;
+        c.v[3 * i + 1] = kCosHalfPi * y - z;
+        c.v[3 * i + 2] = y + kCosHalfPi * z;
+    }
+    return bad;
 }
 
 __device__ __forceinline__ double edge_len(const Corners& c, int i, int j) {

@@ -52,16 +52,8 @@ __device__ __forceinline__ int box_count(const SetMatchArgs& a, int b) {
     return (n < 0 || n > a.nmax) ? 0 : n;
 }
 
-__device__ __forceinline__ uint32_t mix32(uint32_t h) {
-    h ^= h >> 16;
-    h *= 0x7feb352du;
-    h ^= h >> 15;
-    h *= 0x846ca68bu;
-    h ^= h >> 16;
-    return h;
-}
-
-__device__ __forceinline__ uint32_t absorb(uint32_t h, uint32_t w) { return mix32((h ^ w) + 0x9e3779b9u); }
+// one word into the key: common.hpp hash_absorb, the text the ground-truth jitter shares (tracks.hip)
+__device__ __forceinline__ uint32_t absorb(uint32_t h, uint32_t w) { return hash_absorb(h, w); }
 
 __global__ __launch_bounds__(kMatchThreads) void setmatch_cost_kernel(SetMatchArgs a) {
     const int64_t row = (int64_t)blockIdx.x * kMatchThreads + threadIdx.x;

@@ -10,6 +10,8 @@
 // index; the reduction compares (cost, assigned << 16 | index) lexicographically, so its result does not depend on its order.
 // No atomics.  The workgroup is one wave, so __syncthreads() is a compiler / LDS ordering point, not a hardware barrier between
 // waves.  Compiled with floating-point contraction off (obb_pair.hpp), as the IoU is.
+// The evaluator's ground-truth store (parq_gt_tracks_update) is the same store and the same launches 2 and 3 behind a select
+// kernel of its own (gt_tracks_select_kernel).
 #include "obb_pair.hpp"
 
 #include <climits>
@@ -21,6 +23,8 @@ namespace parq {
 namespace {
 
 constexpr int kCapSmall = 512, kCapLarge = 2048;
+// the ground-truth jitter per hash unit: sqrt(3) * 1e-3 / 2^16 (the division by a power of two is exact)
+constexpr double kGtJitterUnit = 1.7320508075688772e-3 / 65536.0;
 
 template <int CAP>
 struct AssignLds {
@@ -221,26 +225,45 @@ __global__ __launch_bounds__(kWave) void tracks_select_kernel(SlotChunk slots, i
     }
 }
 
-constexpr double kCosHalfPi = 6.123233995736766e-17;
-
-// f1_eval.canonical() of float32 world corners: corners [4,0,1,5,7] (the first five of the re-ordering, all the routine reads),
-// (x, y, z) -> (x, c y - z, y + c z); true when any of the 24 values is not finite
-__device__ __forceinline__ bool load_canonical(const float* p, Corners& c) {
-    bool bad = false;
+// launch 1 of the ground-truth store (parq_gt_tracks_update): the valid rows of each scene, compacted in row order, with label
+// labels[row] and score 1; their corners, each box moved by its hashed jitter (include/parq_hip.h: the rule in full), go to
+// `jittered` (B,P,8,3), which stands in for corners_world in launches 2 and 3.  `visits`: updates the scene's slot has had before.
+__global__ __launch_bounds__(kWave) void gt_tracks_select_kernel(SlotChunk slots, SlotChunk visits, int b0, int32_t* __restrict__ store, int mt,
+                                                                 const float* __restrict__ corners_world, const int32_t* __restrict__ labels,
+                                                                 const unsigned char* __restrict__ valid, int P, uint32_t seed_lo,
+                                                                 uint32_t seed_hi, void* __restrict__ ws, float* __restrict__ jittered) {
+    const int lane = threadIdx.x, b = b0 + blockIdx.x;
+    const int32_t slot = slots.slot[blockIdx.x];
+    const int32_t cnt = slot_base(store, slot, mt)[0];
+    const int n = (cnt >= 0 && cnt <= mt) ? cnt : -1;
+    const SceneWs w = scene_ws(ws, b, P, mt);
+    const uint32_t h_scene = hash_absorb(hash_absorb(hash_absorb(hash_absorb(0x9e3779b9u, seed_lo), seed_hi), (uint32_t)slot),
+                                         (uint32_t)visits.slot[blockIdx.x]);
+    int D = 0;
+    for (int q0 = 0; q0 < P; q0 += kWave) {
+        const int q = q0 + lane;
+        const bool det = q < P && n >= 0 && valid[(int64_t)b * P + q] != 0;
+        const unsigned long long votes = __ballot(det);
+        if (det) {
+            const int pos = D + __popcll(votes & ((1ull << lane) - 1ull));
+            w.det_q[pos] = q;
+            w.det_label[pos] = labels[(int64_t)b * P + q];
+            w.det_score[pos] = 1.0f;
+            const uint32_t h = hash_absorb(h_scene, (uint32_t)pos);
+            const uint32_t w0 = hash_absorb(h, 0u), w1 = hash_absorb(h, 1u);
+            const int u = (int)((w0 & 0xffffu) + (w0 >> 16) + (w1 & 0xffffu) + (w1 >> 16)) - 131070;
+            const double jitter = (double)u * kGtJitterUnit;
+            const float* src = corners_world + ((int64_t)b * P + q) * 24;
+            float* dst = jittered + ((int64_t)b * P + q) * 24;
 #pragma unroll
-    for (int i = 0; i < 24; ++i) {
-        const float x = p[i];
-        bad |= !(fabsf(x) <= 3.402823466e38f);
+            for (int i = 0; i < 24; ++i) dst[i] = (float)((double)src[i] + jitter);
+        }
+        D += __popcll(votes);
     }
-    constexpr int face[5] = {4, 0, 1, 5, 7};
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const double x = (double)p[3 * face[i]], y = (double)p[3 * face[i] + 1], z = (double)p[3 * face[i] + 2];
-        c.v[3 * i] = x;
-        c.v[3 * i + 1] = kCosHalfPi * y - z;
-        c.v[3 * i + 2] = y + kCosHalfPi * z;
+    if (lane == 0) {
+        w.hdr[0] = D;
+        w.hdr[1] = n;
     }
-    return bad;
 }
 
 // launch 2: IoU of every (detection, track) pair, one lane per pair
@@ -353,6 +376,39 @@ hipError_t launch_tracks_update(int32_t* store, int max_tracks, const int32_t* s
     else
         hipLaunchKernelGGL(tracks_assign_update_kernel<kCapLarge>, dim3((unsigned)nb), dim3(kWave), 0, s, slots, b0, store, max_tracks,
                            corners_world, Q, iou_thresh, ws, track_id);
+    return hipGetLastError();
+}
+
+// workspace of the ground-truth update: the B scene regions of launch_tracks_update, a (B,P) track_id nobody reads, the jittered corners
+static size_t gt_ws_id_words(int B, int P) { return ((size_t)B * (size_t)P + 3) & ~(size_t)3; }
+
+size_t gt_tracks_update_workspace_bytes(int B, int P, int max_tracks) {
+    return ((size_t)B * (size_t)scene_ws_words(P, max_tracks) + gt_ws_id_words(B, P) + (size_t)B * (size_t)P * 24) * 4;
+}
+
+hipError_t launch_gt_tracks_update(int32_t* store, int max_tracks, const int32_t* slots_host, const int32_t* visits_host, int b0, int nb, int B,
+                                   const float* corners_world, const int32_t* labels, const unsigned char* valid, int P, float iou_thresh,
+                                   uint32_t seed_lo, uint32_t seed_hi, void* ws, float* iou_out, hipStream_t s) {
+    if (nb < 1 || nb > kTrackChunk || b0 < 0 || b0 + nb > B || P < 1 || P > kCapLarge || max_tracks < 1 || max_tracks > kCapLarge)
+        return hipErrorInvalidValue;
+    SlotChunk slots, visits;
+    for (int i = 0; i < kTrackChunk; ++i) {
+        slots.slot[i] = i < nb ? slots_host[b0 + i] : 0;
+        visits.slot[i] = i < nb ? visits_host[b0 + i] : 0;
+    }
+    int32_t* track_id = static_cast<int32_t*>(ws) + (size_t)B * (size_t)scene_ws_words(P, max_tracks);
+    float* jittered = reinterpret_cast<float*>(track_id + gt_ws_id_words(B, P));
+    hipLaunchKernelGGL(gt_tracks_select_kernel, dim3((unsigned)nb), dim3(kWave), 0, s, slots, visits, b0, store, max_tracks, corners_world,
+                       labels, valid, P, seed_lo, seed_hi, ws, jittered);
+    const unsigned pair_blocks = (unsigned)(((int64_t)P * max_tracks + kWave - 1) / kWave);
+    hipLaunchKernelGGL(tracks_iou_kernel, dim3(pair_blocks, (unsigned)nb), dim3(kWave), 0, s, slots, b0, store, max_tracks,
+                       (const float*)jittered, P, ws, iou_out);
+    if (P <= kCapSmall && max_tracks <= kCapSmall)
+        hipLaunchKernelGGL(tracks_assign_update_kernel<kCapSmall>, dim3((unsigned)nb), dim3(kWave), 0, s, slots, b0, store, max_tracks,
+                           (const float*)jittered, P, iou_thresh, ws, track_id);
+    else
+        hipLaunchKernelGGL(tracks_assign_update_kernel<kCapLarge>, dim3((unsigned)nb), dim3(kWave), 0, s, slots, b0, store, max_tracks,
+                           (const float*)jittered, P, iou_thresh, ws, track_id);
     return hipGetLastError();
 }
 

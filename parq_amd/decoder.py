@@ -313,9 +313,15 @@ class PARQDecoder(_Tracked, nn.Module):
     metrics_on_device = False
     # True (only read while metrics_on_device is on): the trackers keep their prediction tracks in a device-resident SceneTracks
     # (parq_amd/scene_tracks.py), fed from the device tensors, so update_metrics no longer copies the outputs to the host; it still
-    # synchronises once per step for the ground truth, whose store stays on the host.  Same tracks and metrics; switch it between
-    # reset_metrics() and the first update_metrics(), not in mid-run (the two stores do not see each other).
+    # synchronises once per step for the ground truth, whose store stays on the host (unless gt_tracks_on_device).  Same tracks and
+    # metrics; switch it between reset_metrics() and the first update_metrics(), not in mid-run (the two stores do not see each other).
     tracks_on_device = False
+    # True (only read while metrics_on_device and tracks_on_device are on): the ground-truth tracks live in a second SceneTracks too.
+    # update_metrics builds the padded array's world corners, labels and validity on the device and only enqueues (no parse_target,
+    # no host wait); compute_metrics takes the per-class counts from parq_f1_counts with one small copy.  The ground-truth jitter
+    # is then the hashed one (F1Calculator gt_jitter="hash"), not NumPy's draw: the metrics are those of the host calculator in
+    # that mode.  Switch it between reset_metrics() and the first update_metrics(), as tracks_on_device.
+    gt_tracks_on_device = False
     # True (on the class or on one module): log_images draws the predicted / ground-truth boxes of scene 0 into the RGB views on the
     # device (parq_amd/draw.py).  False: log_images returns {} and costs nothing, as before the drawing existed.
     draw_images = False
@@ -1685,19 +1691,32 @@ class PARQDecoder(_Tracked, nn.Module):
     def update_metrics(self, out_dict, obbs_padded, T_world_local, scene_name=None):
         """model/parq_decoder.py:426-459: boxes + keep-mask of the last iteration (``parse_pred``, on the device), box corners
         in world coordinates, then one step of every tracker (parq_amd/f1_eval.py: tracks and assignment on the host, the
-        oriented-box IoU matrices there too, or from one parq_obb_iou launch per step when ``metrics_on_device``)."""
+        oriented-box IoU matrices there too, or from one parq_obb_iou launch per step when ``metrics_on_device``).  With
+        ``gt_tracks_on_device`` on top of the other two flags nothing of this waits for the device: the ground truth goes to the
+        trackers as padded device tensors and into a device-resident store (parq_gt_tracks_update)."""
         from .loss import parse_target
-        from .wrappers import Pose, raw
+        from .wrappers import Obb3D, Pose, raw
         assert raw(obbs_padded).ndim == 3, tuple(raw(obbs_padded).shape)
         out = self.parse_pred(out_dict)
-        targets = parse_target(obbs_padded, T_world_local)
         obbs = out["obbs_pred"]
+        gt_on_device = self._gt_tracks_on_device()
+        if gt_on_device:
+            # parse_target's ground-truth world corners and labels and _draw_log_images' validity, on the padded array: nothing is read back
+            gt = Obb3D(raw(obbs_padded).to(obbs.device))
+            targets = {"labels": gt.sem_id.squeeze(-1).long(), "gt_corners_world": gt.T_world_object.transform(gt.bb3corners_object),
+                       "valid": ~torch.all(raw(gt) == -1, dim=-1)}
+        else:
+            targets = parse_target(obbs_padded, T_world_local)
         out["scene_name"] = scene_name
         out["pred_corners_world"] = Pose(raw(T_world_local)).transform(obbs.T_world_object.transform(obbs.bb3corners_object))
         for calc in self.metrics_calculator:
             calc.iou_device = obbs.device if self.metrics_on_device else None
             calc.track_store = "device" if (self.metrics_on_device and self.tracks_on_device) else "host"
+            calc.gt_store = "device" if gt_on_device else "host"
             calc.step(out, targets)
+
+    def _gt_tracks_on_device(self):
+        return bool(self.metrics_on_device and self.tracks_on_device and self.gt_tracks_on_device)
 
     @torch.no_grad()
     def track(self, out_dict, T_world_local, scene_name, tracks):
@@ -1759,6 +1778,7 @@ class PARQDecoder(_Tracked, nn.Module):
             elif calc.iou_device is None:                              # no update_metrics yet in this mode: the module's device
                 calc.iou_device = next(self.parameters()).device
             calc.track_store = "device" if (self.metrics_on_device and self.tracks_on_device) else "host"
+            calc.gt_store = "device" if self._gt_tracks_on_device() else "host"
             metrics.update(calc.compute_metrics())
         return metrics
 

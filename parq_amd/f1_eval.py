@@ -15,7 +15,10 @@ packs the (detections, tracks) pairs of every scene of the batch, predictions an
 default) is the host loop.  With ``track_store="device"`` on top of ``iou_device`` the prediction tracks do not live here at all
 but in a ``SceneTracks`` (parq_amd/scene_tracks.py): ``step`` hands it the outputs as device tensors in one enqueue, nothing of the
 predictions is copied to the host, and ``compute_metrics`` reads the tracks back once.  The ground-truth store stays on the host
-(its jitter draws from NumPy's generator box by box), so ``step`` still synchronises once for the ground truth.  The device side
+(its jitter draws from NumPy's generator box by box), so ``step`` still synchronises once for the ground truth.  With
+``gt_store="device"`` on top of that the ground truth lives in a second ``SceneTracks`` (``update_labelled``), its jitter a hash
+stated in include/parq_hip.h (``gt_jitter="hash"`` is the same rule on the host, and the oracle of that path), ``step`` only
+enqueues, and ``compute_metrics`` reads the per-class counts of ``parq_f1_counts`` with one small copy.  The device side
 of the rest of the evaluation path (box building, validity window, NMS) is ``PARQDecoder.parse_pred``.
 
 The oriented IoU follows the reference's convention (utils/f1_eval.py:46-48,77-107): corners are re-ordered with
@@ -270,6 +273,39 @@ class DeviceIoU:
         return (m3, split_matrices(host[1], table)) if footprint else m3
 
 
+# ---- the hashed ground-truth jitter (include/parq_hip.h parq_gt_tracks_update, step 1: the rule in full) ----------------------------
+_GOLDEN = np.uint32(0x9E3779B9)
+GT_JITTER_UNIT = 1.7320508075688772e-3 / 65536              # one float64 constant; the division by 2^16 is exact
+
+
+def _mix32(h):
+    h = h ^ (h >> np.uint32(16))
+    h = h * np.uint32(0x7FEB352D)
+    h = h ^ (h >> np.uint32(15))
+    h = h * np.uint32(0x846CA68B)
+    return h ^ (h >> np.uint32(16))
+
+
+def hash_jitter(seed, slot, visit, n):
+    """float64 (n,): the jitter of the boxes at positions 0..n-1 of visit `visit` of the scene in slot `slot`.  Integer
+    arithmetic and one float64 product: zero mean, standard deviation 1e-3, |jitter| <= 3.4641e-3."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    with np.errstate(over="ignore"):
+        h = np.full(n, _GOLDEN, np.uint32)
+        for w in (seed & 0xFFFFFFFF, seed >> 32, int(slot) & 0xFFFFFFFF, int(visit) & 0xFFFFFFFF):
+            h = _mix32((h ^ np.uint32(w)) + _GOLDEN)
+        h = _mix32((h ^ np.arange(n, dtype=np.uint32)) + _GOLDEN)
+        w0, w1 = _mix32((h ^ np.uint32(0)) + _GOLDEN), _mix32((h ^ np.uint32(1)) + _GOLDEN)
+    u = ((w0 & np.uint32(0xFFFF)).astype(np.int64) + (w0 >> np.uint32(16)).astype(np.int64)
+         + (w1 & np.uint32(0xFFFF)).astype(np.int64) + (w1 >> np.uint32(16)).astype(np.int64) - 131070)
+    return u.astype(np.float64) * GT_JITTER_UNIT
+
+
+def apply_jitter(corners_f32, jitter):
+    """float32((double) corner + jitter), one scalar per box: (n,8,3) float32, (n,) float64 -> (n,8,3) float32."""
+    return (np.asarray(corners_f32, np.float32).astype(np.float64) + np.asarray(jitter, np.float64)[:, None, None]).astype(np.float32)
+
+
 class F1Calculator:
     """Accumulates per-scene prediction and ground-truth tracks over snippets; ``compute_metrics`` returns
     {"<thr>_accuracy", "<thr>_recall", "<thr>_f1"} for thr in f1_iou_thresh.
@@ -278,18 +314,37 @@ class F1Calculator:
     ``compute_metrics`` take them from one ``parq_obb_iou`` launch each (see the module docstring).  ``iou_backend``: any
     callable [(A, B) canonical corner stacks] -> [float64 (n_a, n_b)] to run the batched path on instead (``host_iou_backend``).
     ``track_store``: "host" (default), or "device" (needs ``iou_device``): the prediction tracks live in a ``SceneTracks`` of
-    ``track_capacity`` tracks per scene and ``preds`` is filled from it by ``compute_metrics`` (or ``pull_tracks``)."""
+    ``track_capacity`` tracks per scene and ``preds`` is filled from it by ``compute_metrics`` (or ``pull_tracks``).
+    ``gt_jitter``: "numpy" (default) draws the reference's ground-truth jitter from NumPy's global generator, box by box;
+    "hash" takes it from ``hash_jitter(gt_seed, slot, visit, position)``: slot = the order in which the scene's name first
+    appeared since ``reset``, visit = the ground-truth updates the scene has had before, position = the box's rank in the scene.
+    ``gt_store``: "host" (default), or "device" (needs ``track_store="device"``; the jitter is then the hash): the ground truth
+    lives in a second ``SceneTracks`` fed by ``update_labelled``, ``step`` waits for nothing, and ``compute_metrics`` takes the
+    per-class counts from ``parq_f1_counts`` with one small copy.  ``step`` then takes the ground truth as the list of per-scene
+    dicts or as one padded dict {"labels" (B,P), "gt_corners_world" (B,P,8,3), "valid" (B,P)}."""
 
     track_capacity = 2048
 
     def __init__(self, conf_thresh, f1_iou_thresh=(0.25, 0.5, 0.7), verbose=False, iou_device=None, iou_backend=None,
-                 track_store="host"):
+                 track_store="host", gt_jitter="numpy", gt_seed=0, gt_store="host"):
         if track_store not in ("host", "device"):
             raise ValueError("track_store must be 'host' or 'device', got %r" % (track_store,))
         if track_store == "device" and iou_device is None:
             raise ValueError("track_store='device' needs iou_device (a CUDA device)")
+        if gt_jitter not in ("numpy", "hash"):
+            raise ValueError("gt_jitter must be 'numpy' or 'hash', got %r" % (gt_jitter,))
+        if gt_store not in ("host", "device"):
+            raise ValueError("gt_store must be 'host' or 'device', got %r" % (gt_store,))
+        if gt_store == "device" and track_store != "device":
+            raise ValueError("gt_store='device' needs track_store='device'")
         self.track_store = track_store
+        self.gt_store = gt_store
+        self.gt_jitter = "hash" if gt_store == "device" else gt_jitter
+        self.gt_seed = int(gt_seed)
         self._tracks = None
+        self._gt_tracks = None
+        self.count_launches = 0                # parq_f1_counts calls so far
+        self.count_copies = 0                  # device-to-host copies compute_metrics made on the gt_store="device" path
         self.f1_iou_thresh = list(f1_iou_thresh)
         self.conf_thresh = conf_thresh
         self.iou_thresh = 0.1
@@ -315,12 +370,26 @@ class F1Calculator:
     def reset(self):
         self.preds = {}
         self.gts = {}
-        if getattr(self, "_tracks", None) is not None:
-            self._tracks.reset()
+        self._gt_slots = {}                    # scene name -> order of first appearance (gt_jitter="hash")
+        self._gt_visits = {}                   # scene name -> ground-truth updates so far
+        for tracks in (getattr(self, "_tracks", None), getattr(self, "_gt_tracks", None)):
+            if tracks is not None:
+                tracks.reset()
 
     @property
     def on_device_tracks(self):
         return self.track_store == "device" and self._iou_device is not None
+
+    @property
+    def on_device_gt(self):
+        return self.gt_store == "device" and self.on_device_tracks
+
+    def _device_gt_tracks(self):
+        if self._gt_tracks is None:
+            from .scene_tracks import SceneTracks
+            self._gt_tracks = SceneTracks(max_tracks=self.track_capacity, conf_thresh=self.conf_thresh, iou_thresh=self.iou_thresh,
+                                          num_classes=_NON_OBJECT + 1, device=self._iou_device)
+        return self._gt_tracks
 
     def _device_tracks(self, num_classes):
         if self._tracks is None:
@@ -333,7 +402,8 @@ class F1Calculator:
         return self._tracks
 
     def pull_tracks(self):
-        """track_store="device": fill ``preds`` from the device store (one copy, synchronises); a full store is an error."""
+        """track_store="device": fill ``preds`` from the device store (one copy, synchronises); a full store is an error.  With
+        gt_store="device" also ``gts``, as entries (class, corners, 1), for inspection."""
         if self._tracks is None:
             return
         lost = {n: k for n, k in self._tracks.dropped().items() if k}
@@ -341,6 +411,12 @@ class F1Calculator:
             raise RuntimeError("F1Calculator: the device track store (track_capacity = %d per scene) dropped detections: %r"
                                % (self.track_capacity, lost))
         self.preds = self._tracks.to_host()
+        if self.on_device_gt and self._gt_tracks is not None:
+            lost = {n: k for n, k in self._gt_tracks.dropped().items() if k}
+            if lost:
+                raise RuntimeError("F1Calculator: the device ground-truth store (track_capacity = %d per scene) dropped boxes: %r"
+                                   % (self.track_capacity, lost))
+            self.gts = {n: [(e[0], e[1], 1) for e in trks] for n, trks in self._gt_tracks.to_host().items()}
 
     # ---- one snippet batch ------------------------------------------------------------------------------------------
     def step(self, outputs, gt_list):
@@ -353,9 +429,14 @@ class F1Calculator:
             corners, prob, mask = (torch.as_tensor(getattr(outputs[k], "_data", outputs[k])).to(dev)
                                    for k in ("pred_corners_world", "sem_cls_prob", "pred_mask"))
             self._device_tracks(prob.shape[-1]).update(names, corners, prob, mask)
-            return self._step_batched([], self.make_gt_list(gt_list), names)
+            if self.on_device_gt:
+                gt_c, gt_l, gt_v = self._padded_gt(gt_list, dev)
+                self._device_gt_tracks().update_labelled(names, gt_c, gt_l, gt_v, seed=self.gt_seed)
+                assert self._gt_tracks._slots == self._tracks._slots, "the two device stores must number the scenes alike"
+                return
+            return self._step_batched([], self._gt_entries(gt_list, names), names)
         dets = self.parse_predictions(outputs, self.conf_thresh)
-        gts = self.make_gt_list(gt_list)
+        gts = self._gt_entries(gt_list, names)
         if self.iou_backend is not None:
             return self._step_batched(dets, gts, names)
         self.matching_pred(dets, names)
@@ -405,6 +486,42 @@ class F1Calculator:
         for g in gt_list:
             labels, corners = _np(g["labels"]), _np(g["gt_corners_world"])
             out.append([(labels[j].item(), corners[j] + np.random.randn(1) * 0.001, 1) for j in range(corners.shape[0])])
+        return out
+
+    @staticmethod
+    def _padded_gt(gt_list, dev):
+        """The ground truth of one batch as device tensors (corners (B,P,8,3) float32, labels (B,P) int32, valid (B,P) uint8), from
+        the padded dict as it is, or from the list of per-scene dicts padded with lengths read from the shapes: no host wait."""
+        import torch
+        if isinstance(gt_list, dict):
+            return (torch.as_tensor(gt_list["gt_corners_world"]).to(dev, torch.float32), torch.as_tensor(gt_list["labels"]).to(dev, torch.int32),
+                    torch.as_tensor(gt_list["valid"]).to(dev).to(torch.uint8))
+        ns = [int(g["gt_corners_world"].shape[0]) for g in gt_list]
+        B, P = len(ns), max(ns + [1])
+        corners = torch.zeros(B, P, 8, 3, dtype=torch.float32, device=dev)
+        labels = torch.zeros(B, P, dtype=torch.int32, device=dev)
+        valid = torch.from_numpy(np.array([[j < n for j in range(P)] for n in ns], np.uint8).reshape(B, P)).to(dev, non_blocking=True)
+        for b, (g, n) in enumerate(zip(gt_list, ns)):
+            if n:
+                corners[b, :n] = torch.as_tensor(g["gt_corners_world"]).to(dev, torch.float32)
+                labels[b, :n] = torch.as_tensor(g["labels"]).to(dev, torch.int32)
+        return corners, labels, valid
+
+    def _gt_entries(self, gt_list, names):
+        """The batch's ground-truth entries for the host store: ``make_gt_list`` (gt_jitter="numpy"), or the hashed jitter."""
+        if isinstance(gt_list, dict):                                  # the padded form: its valid rows, in row order
+            lab, cor, ok = _np(gt_list["labels"]), _np(gt_list["gt_corners_world"]), _np(gt_list["valid"]).astype(bool)
+            gt_list = [{"labels": lab[b][ok[b]], "gt_corners_world": cor[b][ok[b]]} for b in range(cor.shape[0])]
+        if self.gt_jitter == "numpy":
+            return self.make_gt_list(gt_list)
+        out = []
+        for g, name in zip(gt_list, names):
+            labels, corners = _np(g["labels"]), _np(g["gt_corners_world"])
+            slot = self._gt_slots.setdefault(name, len(self._gt_slots))
+            visit = self._gt_visits.get(name, 0)
+            self._gt_visits[name] = visit + 1
+            moved = apply_jitter(corners.reshape(-1, 8, 3), hash_jitter(self.gt_seed, slot, visit, corners.shape[0]))
+            out.append([(labels[j].item(), moved[j], 1) for j in range(corners.shape[0])])
         return out
 
     def matching_pred(self, detections, scene_names, ious=None):
@@ -457,8 +574,46 @@ class F1Calculator:
         mats = self.iou_backend([(canonical_stack(self.gts[s]), canonical_stack(self.preds[s])) for s in scenes]) if scenes else []
         return dict(zip(scenes, mats))
 
+    def device_counts(self):
+        """gt_store="device": (gts, preds, [tps per threshold]) as lists over the care classes, from one parq_f1_counts call and
+        ONE copy that also brings both stores' `dropped` columns and the labels outside the care classes; either is an error."""
+        import torch
+        from .scene_tracks import f1_counts
+        K, T = len(CARE_CLASSES), len(self.f1_iou_thresh)
+        if self._tracks is None or self._gt_tracks is None or not self._tracks._slots:
+            return [0] * K, [0] * K, [[0] * K for _ in range(T)]
+        assert self._gt_tracks._slots == self._tracks._slots, "the two device stores must number the scenes alike"
+        S, n = len(self._tracks._slots), (2 + T) * K + 2
+        with torch.cuda.device(self._tracks.device):
+            buf = torch.empty(n + 2 * S, dtype=torch.int64, device=self._tracks.device)
+            f1_counts(self._tracks, self._gt_tracks, self.f1_iou_thresh, K, out=buf)
+            self.count_launches += 1
+            buf[n:n + S] = self._tracks._store[:S, 1]
+            buf[n + S:] = self._gt_tracks._store[:S, 1]
+            host = buf.cpu().numpy()
+            self.count_copies += 1
+        names = list(self._tracks._slots)
+        for what, col in (("detections", host[n:n + S]), ("ground-truth boxes", host[n + S:])):
+            lost = {names[s]: int(k) for s, k in enumerate(col) if k}
+            if lost:
+                raise RuntimeError("F1Calculator: a device track store (track_capacity = %d per scene) dropped %s: %r"
+                                   % (self.track_capacity, what, lost))
+        if host[n - 2] or host[n - 1]:
+            raise RuntimeError("F1Calculator: %d ground-truth and %d prediction tracks carry a label outside the %d care classes"
+                               % (host[n - 2], host[n - 1], K))
+        counts = host[:n - 2].reshape(2 + T, K)
+        return [int(x) for x in counts[0]], [int(x) for x in counts[1]], [[int(x) for x in counts[2 + t]] for t in range(T)]
+
     def compute_metrics(self):
         metrics = {}
+        if self.on_device_gt:
+            gts, preds, tps = self.device_counts()
+            for t, thr in enumerate(self.f1_iou_thresh):
+                acc, rec, f1 = f1_from_counts(gts, preds, tps[t], self.verbose)
+                metrics["{}_accuracy".format(thr)] = acc
+                metrics["{}_recall".format(thr)] = rec
+                metrics["{}_f1".format(thr)] = f1
+            return metrics
         if self.on_device_tracks:
             self.pull_tracks()
         ious = self.scene_ious() if self.iou_backend is not None else None           # every threshold reads the same matrices

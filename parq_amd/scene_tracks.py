@@ -9,6 +9,10 @@ per query comes back as a device tensor.  The rule, stated in full, is in the he
 tests/scene_tracks_cases.py.  One difference from the reference: tracks born in the same step are numbered in query order (the
 reference puts never-assigned detections before assigned-under-threshold ones), so their ids can be permuted among themselves; the
 set of tracks, and every metric, is the same.
+
+The evaluator's ground truth can live in a second store: ``update_labelled`` (parq_gt_tracks_update) follows labelled boxes under
+the same rule, and ``f1_counts`` (parq_f1_counts, csrc/f1_counts.hip) turns a prediction and a ground-truth store into the
+per-class counts of the F1 metrics; their NumPy statements are tests/f1_device_cases.py.
 """
 from __future__ import annotations
 
@@ -41,6 +45,23 @@ def check_tracks_args(corners_world, sem_cls_prob, pred_mask, n_names, num_class
     return B, Q
 
 
+def check_labelled_args(corners_world, labels, valid, n_names):
+    """Shapes / dtypes of one ground-truth update (ValueError before anything touches the GPU); returns (B, P)."""
+    if not (torch.is_tensor(corners_world) and corners_world.ndim == 4 and tuple(corners_world.shape[2:]) == (8, 3)
+            and corners_world.is_floating_point()):
+        raise ValueError("corners_world must be a floating-point (B, P, 8, 3) tensor, got %s" % (tuple(getattr(corners_world, "shape", ())),))
+    B, P = corners_world.shape[:2]
+    if not (torch.is_tensor(labels) and tuple(labels.shape) == (B, P) and not labels.is_floating_point() and labels.dtype != torch.bool):
+        raise ValueError("labels must be an integer (B, P) tensor for B = %d, P = %d" % (B, P))
+    if not (torch.is_tensor(valid) and tuple(valid.shape) == (B, P) and valid.dtype in (torch.bool, torch.uint8)):
+        raise ValueError("valid must be a bool or uint8 (B, P) tensor for B = %d, P = %d" % (B, P))
+    if n_names != B:
+        raise ValueError("%d scene names for a batch of %d scenes" % (n_names, B))
+    if not 1 <= P <= MAX_SIDE:
+        raise ValueError("P = %d: the store takes 1 to %d labelled boxes per scene" % (P, MAX_SIDE))
+    return B, P
+
+
 class SceneTracks:
     """A device-resident track store: ``update`` follows the detections of a snippet batch, ``boxes`` / ``to_host`` read the scenes'
     objects.  ``max_tracks`` is the capacity per scene (at most 2048): a detection that would open a track beyond it gets id -2 and
@@ -63,7 +84,8 @@ class SceneTracks:
         self._slots = {}                       # scene name -> slot
         self._store = None                     # (S_cap, words) int32
         self._ws = None
-        self.enqueues = 0                      # parq_tracks_update calls so far
+        self._visits = {}                      # slot -> update_labelled visits so far (a word of the jitter's key)
+        self.enqueues = 0                      # parq_tracks_update / parq_gt_tracks_update calls so far
 
     # ---- the store -----------------------------------------------------------------------------------------------------
     def _grow(self, need):
@@ -147,6 +169,61 @@ class SceneTracks:
                         iou_out.index_copy_(0, idx, i_w)
         return track_id
 
+    @torch.no_grad()
+    def update_labelled(self, scene_names, corners_world, labels, valid, seed=0, iou_out=None):
+        """The evaluator's ground-truth side (include/parq_hip.h parq_gt_tracks_update): scene_names [B]; corners_world (B,P,8,3);
+        labels (B,P) integers; valid (B,P) bool / uint8.  Every valid row is a detection of score 1 with its own label, its corners
+        moved by the hashed jitter of (seed, slot, visit, rank among the valid rows); the rest is ``update``'s rule.  A name listed
+        k times is processed in k enqueues, and each counts as a visit of its scene.  Returns nothing and does not synchronise.
+        ``iou_out`` (tests): a float32 (B, P, max_tracks) device tensor that receives the IoU matrices."""
+        names = list(scene_names)
+        B, P = check_labelled_args(corners_world, labels, valid, len(names))
+        if self.device.index is None and corners_world.is_cuda:
+            self.device = corners_world.device
+        for t in (corners_world, labels, valid):
+            if t.device != self.device:
+                raise RuntimeError("parq_amd.SceneTracks: tensors must be on %s, got %s (no CPU fallback)" % (self.device, t.device))
+        if B == 0:
+            return
+        corners = corners_world.detach().to(torch.float32).contiguous()
+        lab = labels.to(torch.int32).contiguous()
+        ok = (valid.view(torch.uint8) if valid.dtype == torch.bool else valid).contiguous()
+        slots = [self._slot(n) for n in names]
+        self._grow(len(self._slots))
+        seen, waves = {}, []
+        for b, s in enumerate(slots):
+            k = seen.get(s, 0)
+            seen[s] = k + 1
+            if k == len(waves):
+                waves.append([])
+            waves[k].append(b)
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            stream = _lib.stream_ptr()
+            for wave in waves:
+                whole = len(wave) == B
+                if whole:
+                    c_w, l_w, v_w, i_w = corners, lab, ok, iou_out
+                else:
+                    idx = torch.tensor(wave, dtype=torch.int64).to(self.device, non_blocking=True)
+                    c_w, l_w, v_w = corners.index_select(0, idx), lab.index_select(0, idx), ok.index_select(0, idx)
+                    i_w = None if iou_out is None else torch.zeros(len(wave), P, self.max_tracks, dtype=torch.float32, device=self.device)
+                need = lib.parq_gt_tracks_update_workspace_bytes(len(wave), P, self.max_tracks)
+                if self._ws is None or self._ws.numel() < need:
+                    self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                arr = (C.c_int32 * len(wave))(*[slots[b] for b in wave])
+                visits = (C.c_int32 * len(wave))(*[self._visits.get(slots[b], 0) for b in wave])
+                _lib.check(lib.parq_gt_tracks_update(C.c_void_p(self._store.data_ptr()), self._store.shape[0], self.max_tracks, arr, visits,
+                                                     len(wave), _lib.ptr(c_w), C.c_void_p(l_w.data_ptr()), C.c_void_p(v_w.data_ptr()), P,
+                                                     self.iou_thresh, int(seed) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(self._ws.data_ptr()),
+                                                     self._ws.numel(), None if i_w is None else _lib.ptr(i_w), stream),
+                           "parq_gt_tracks_update")
+                self.enqueues += 1
+                for b in wave:
+                    self._visits[slots[b]] = self._visits.get(slots[b], 0) + 1
+                if not whole and iou_out is not None:
+                    iou_out.index_copy_(0, idx, i_w)
+
     # ---- reading ----------------------------------------------------------------------------------------------------------
     def boxes(self, name):
         """Device views of one scene's tracks, nothing copied: {"count" (0-dim int32), "corners" (max_tracks,8,3), "labels"
@@ -189,7 +266,58 @@ class SceneTracks:
         """Forget every scene, or empty one scene's slot (its name keeps the slot)."""
         if name is None:
             self._slots = {}
+            self._visits = {}
             if self._store is not None:
                 self._store.zero_()
         elif name in self._slots:
+            self._visits.pop(self._slots[name], None)
             self._store[self._slots[name], :2].zero_()
+
+
+F1_MAX_THRESHOLDS = 8
+
+
+def f1_counts(pred_tracks, gt_tracks, thresholds, num_classes=9, best_iou_out=None, out=None):
+    """The evaluator's end-of-epoch counts from two ``SceneTracks`` with the same scenes in the same slots (include/parq_hip.h
+    parq_f1_counts): (counts (2 + T, num_classes) int64, invalid (2) int64), both on the device.  counts[0] / counts[1]: the
+    ground-truth / prediction tracks per class, counts[2 + t]: the ground-truth tracks whose best same-class prediction has
+    IoU > thresholds[t]; invalid: tracks of either side with a label outside [0, num_classes).  Only enqueues.
+    ``best_iou_out`` (tests): a float64 (scenes, gt_tracks.max_tracks) device tensor.  ``out``: an int64 device tensor of at least
+    (2 + T) * num_classes + 2 elements to place both results in (counts first), for callers that copy them back with more."""
+    thr = [float(t) for t in thresholds]
+    T = len(thr)
+    if not 1 <= T <= F1_MAX_THRESHOLDS:
+        raise ValueError("f1_counts takes 1 to %d thresholds, got %d" % (F1_MAX_THRESHOLDS, T))
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 1 <= num_classes <= 32:
+        raise ValueError("num_classes must be an integer in [1, 32], got %r" % (num_classes,))
+    if not (isinstance(pred_tracks, SceneTracks) and isinstance(gt_tracks, SceneTracks)):
+        raise TypeError("f1_counts takes two SceneTracks")
+    if pred_tracks._slots != gt_tracks._slots:
+        raise ValueError("f1_counts: the two stores do not hold the same scenes in the same slots (feed both with the same names)")
+    if pred_tracks.device != gt_tracks.device:
+        raise RuntimeError("f1_counts: the stores are on %s and %s" % (pred_tracks.device, gt_tracks.device))
+    dev = pred_tracks.device
+    S = len(pred_tracks._slots)
+    n = (2 + T) * num_classes
+    if out is None:
+        out = torch.empty(n + 2, dtype=torch.int64, device=dev)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() >= n + 2
+    counts, invalid = out[:n].view(2 + T, num_classes), out[n:n + 2]
+    if S == 0:
+        out[:n + 2].zero_()
+        return counts, invalid
+    if best_iou_out is not None:
+        assert best_iou_out.is_cuda and best_iou_out.dtype == torch.float64 and best_iou_out.is_contiguous()
+        assert tuple(best_iou_out.shape) == (S, gt_tracks.max_tracks), tuple(best_iou_out.shape)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        need = lib.parq_f1_counts_workspace_bytes(S, gt_tracks.max_tracks, T, num_classes)
+        if gt_tracks._ws is None or gt_tracks._ws.numel() < need:
+            gt_tracks._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = gt_tracks._ws
+        _lib.check(lib.parq_f1_counts(C.c_void_p(pred_tracks._store.data_ptr()), pred_tracks.max_tracks, C.c_void_p(gt_tracks._store.data_ptr()),
+                                      gt_tracks.max_tracks, S, (C.c_double * T)(*thr), T, num_classes, C.c_void_p(ws.data_ptr()), ws.numel(),
+                                      C.c_void_p(counts.data_ptr()), C.c_void_p(invalid.data_ptr()),
+                                      None if best_iou_out is None else C.c_void_p(best_iou_out.data_ptr()), _lib.stream_ptr()),
+                   "parq_f1_counts")
+    return counts, invalid
