@@ -584,7 +584,7 @@ int (parq_assign_max)(const float *m, int64_t m_total, const int64_t *segments, 
  * store: parq_tracks_store_bytes(S_cap, max_tracks) bytes of DEVICE memory, zero-filled by the caller before first use; S_cap scene
  * slots of 2 + 26 * max_tracks 32-bit words each: count (int32), dropped (int32), labels[max_tracks] (int32), scores[max_tracks]
  * (float32), corners[max_tracks][8][3] (float32, world frame, Obb3D.bb3corners_object order).  A track's id is its position in its
- * slot; tracks are never removed.
+ * slot; tracks are never removed (by this entry: parq_tracks_retire, below, is the one that removes).
  * Per call: slots_host (B) int32 on the HOST, the slot of each scene of the batch, each in [0, S_cap) and listed once;
  * corners_world (B,Q,8,3) float32; sem_cls_prob (B,Q,K) float32; pred_mask (B,Q) bytes.  track_id (B,Q) int32 out; iou_out
  * (B,Q,max_tracks) float32 or NULL: for tests, row d of scene b receives the IoUs of that scene's d-th detection with its tracks
@@ -672,6 +672,53 @@ size_t (parq_f1_counts_workspace_bytes)(int32_t S, int32_t gt_max_tracks, int32_
 int (parq_f1_counts)(const void *pred_store, int32_t pred_max_tracks, const void *gt_store, int32_t gt_max_tracks, int32_t S,
                    const double *thresholds_host, int32_t T, int32_t K, void *workspace, size_t workspace_bytes, int64_t *counts,
                    int64_t *invalid, double *best_iou /*NULL in normal use*/, parq_stream stream);
+
+/* ---- a life for the tracks of a store: hits, age, stable ids and retirement (csrc/track_life.hip), one launch each ---------------
+ * The track store above never removes a track and keeps no history.  A stream needs both, so a store may have a second, parallel
+ * record, the LIFE: parq_tracks_life_bytes(S_cap, max_tracks) = S_cap * (4 + 4 * max_tracks) * 4 bytes of DEVICE memory (0 for
+ * arguments the entries refuse), zero-filled by the caller before first use.  Per scene slot, int32 words: step (updates noted so
+ * far for this slot), known (tracks that have a life), next_uid, retired (tracks removed so far), then uid[max_tracks],
+ * hits[max_tracks], first[max_tracks], last[max_tracks].  A scene's clock is its own `step`: a scene that receives no update does
+ * not age.  The store's layout is not changed, and parq_tracks_update, parq_gt_tracks_update, parq_f1_counts and parq_draw_boxes
+ * know nothing of the life.
+ *
+ * parq_tracks_note, one launch behind each parq_tracks_update: store (read only), life, slots_host (B) as above, track_id (B,Q)
+ * int32 as the update wrote it; uid_out, hits_out (B,Q) int32 or NULL.  The rule, per scene, with n = the store's count,
+ * k = known and t0 = step:
+ *  0. The slot is valid when 0 <= n <= max_tracks, 0 <= k <= n, 0 <= t0 < INT32_MAX, next_uid >= 0 and next_uid + (n - k) does not
+ *     exceed INT32_MAX.  An invalid slot is left untouched and its rows of uid_out / hits_out are written as -1 / 0, as
+ *     parq_tracks_update treats a count it cannot trust.
+ *  1. seen[t], 0 <= t < n: some query of the scene has track_id == t.  Ids outside [0, n) are ignored.
+ *  2. For t < k: if seen[t], hits[t] = min(hits[t] + 1, INT32_MAX) and last[t] = t0.
+ *  3. For k <= t < n, the births of this update in the store's own order: uid[t] = next_uid + (t - k), hits[t] = seen[t] ? 1 : 0,
+ *     first[t] = last[t] = t0.
+ *  4. next_uid += n - k, then known = n, then step = t0 + 1.
+ *  5. For every query: uid_out = uid[id] for 0 <= id < n, the id itself for -1 and -2, -1 for anything else; hits_out = hits[id]
+ *     after step 2 or 3, or 0.  A uid is never reused within a slot until the caller zeroes the slot's life.
+ *
+ * parq_tracks_retire: store, life, slots_host (B) as above; min_hits >= 1; max_age, tentative_age (negative: never);
+ * remap_out (B, max_tracks) int32 or NULL.  The rule, per scene, with n = count:
+ *  0. The slot is valid when the conditions of note hold and known == n, so that every update has been noted.  An invalid slot is
+ *     left untouched and its row of remap_out is all -1.
+ *  1. age[t] = (step - 1) - last[t] (computed without overflow): 0 for a track seen in the latest update.  A track is CONFIRMED
+ *     when hits[t] >= min_hits.
+ *  2. Track t is dropped when it is confirmed, max_age >= 0 and age[t] > max_age, or when it is not confirmed, tentative_age >= 0
+ *     and age[t] > tentative_age.
+ *  3. The m kept tracks move, in their order, to positions 0 .. m-1: label, score and the 24 corner floats in the store, uid, hits,
+ *     first and last in the life.  Then count = m, known = m and retired = min(retired + (n - m), INT32_MAX).  dropped, step and
+ *     next_uid are not touched.  Rows from m on are NOT written: they keep what they held before the call.
+ *  4. remap_out[t] = the new position of track t, -1 for a dropped track and for t >= n.
+ * A track's id (parq_tracks_update's track_id) is its position in its slot and so changes at a retire; its uid does not.
+ * Both: one wavefront per scene, no atomics, nothing allocated, the call only enqueues.  B = 0 is valid and launches nothing.
+ * PARQ_ERR_ARG, with nothing launched: Q or max_tracks outside [1, 2048], a negative count, min_hits < 1, a NULL store, life,
+ * slots_host or track_id, a slot outside [0, S_cap) or listed twice.
+ * (Parenthesised names, as above; the three entries are typed in _lib.LIFE_SYMBOLS.) */
+size_t (parq_tracks_life_bytes)(int32_t S_cap, int32_t max_tracks);
+int (parq_tracks_note)(const void *store, void *life, int32_t S_cap, int32_t max_tracks, const int32_t *slots_host, int32_t B,
+                     const int32_t *track_id, int32_t Q, int32_t *uid_out /*or NULL*/, int32_t *hits_out /*or NULL*/,
+                     parq_stream stream);
+int (parq_tracks_retire)(void *store, void *life, int32_t S_cap, int32_t max_tracks, const int32_t *slots_host, int32_t B,
+                       int32_t min_hits, int32_t max_age, int32_t tentative_age, int32_t *remap_out /*or NULL*/, parq_stream stream);
 
 /* ---- boxes drawn into the normalised input views (utils/parq_utils.py:141-211 draw_detections), three launches ------------------
  * images (B,T,3,H,W) float32; camera (B,T,6) = [w, h, fx, fy, cx, cy]; T_camera_pseudoCam, T_world_pseudoCam (B,T,12) = [R row-major |

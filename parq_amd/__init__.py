@@ -8,7 +8,8 @@ Public surface mirrors the reference (ymingxie/PARQ):
     ViewWindow   (no counterpart: the reference re-projects every view of every snippet)  a streaming window of view slots
     draw_boxes, box_colors (utils/parq_utils.py:134,141 get_colors / draw_detections)  boxes drawn into the views on the device
     SceneTracks  (utils/f1_eval.py:293 matching_pred, there on the host and inside the evaluator only)  detections followed across
-                 snippets in a device-resident track store: one enqueue per snippet batch returns a track id per query
+                 snippets in a device-resident track store: one enqueue per snippet batch returns a track id per query;
+                 lifecycle=True (no counterpart) adds hits, age, stable uids and retire() for streams that never end
     f1_counts    (utils/f1_eval.py:36 count_matches over all scenes)  the evaluator's per-class counts from a prediction and a
                  ground-truth SceneTracks, on the device
     FramePrep, resize_frames, resized_intrinsics, gravity_aligned, snippet_local (datasets/transforms.py:211 ScanNetBaseTransform)

@@ -184,6 +184,13 @@ EVAL_SYMBOLS = {
     "parq_f1_counts": (C.c_int, [_vp, _i32, _vp, _i32, _i32, C.POINTER(C.c_double), _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
 
+# the life record beside a track store (include/parq_hip.h parq_tracks_note, parq_tracks_retire): a table of its own for the same reason
+LIFE_SYMBOLS = {
+    "parq_tracks_life_bytes": (_sz, [_i32, _i32]),
+    "parq_tracks_note": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_i32), _i32, _vp, _i32, _vp, _vp, _vp]),
+    "parq_tracks_retire": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -210,7 +217,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in [kv for table in ALL_TABLES + (EVAL_SYMBOLS,) for kv in table.items()]:
+    for name, (res, args) in [kv for table in ALL_TABLES + (EVAL_SYMBOLS, LIFE_SYMBOLS) for kv in table.items()]:
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

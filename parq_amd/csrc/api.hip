@@ -2989,6 +2989,51 @@ int parq_f1_counts(const void* pred_store, int32_t pred_max_tracks, const void* 
     return PARQ_OK;
 }
 
+size_t parq_tracks_life_bytes(int32_t S_cap, int32_t max_tracks) {
+    if (S_cap < 0 || max_tracks < 1 || max_tracks > 2048) return 0;
+    return (size_t)S_cap * (4 + 4 * (size_t)max_tracks) * 4;
+}
+
+// the slots of a life call: each inside [0, S_cap) and listed once
+static int check_life_slots(const char* who, const int32_t* slots_host, int32_t B, int32_t S_cap) {
+    std::vector<char> seen((size_t)S_cap, 0);
+    for (int b = 0; b < B; ++b) {
+        const int32_t sl = slots_host[b];
+        if (sl < 0 || sl >= S_cap) return fail(PARQ_ERR_ARG, "%s: slot %d of scene %d outside [0, %d)", who, sl, b, S_cap);
+        if (seen[(size_t)sl]) return fail(PARQ_ERR_ARG, "%s: slot %d listed twice in one call", who, sl);
+        seen[(size_t)sl] = 1;
+    }
+    return PARQ_OK;
+}
+
+int parq_tracks_note(const void* store, void* life, int32_t S_cap, int32_t max_tracks, const int32_t* slots_host, int32_t B,
+                     const int32_t* track_id, int32_t Q, int32_t* uid_out, int32_t* hits_out, parq_stream stream) {
+    if (B < 0 || S_cap < 0) return fail(PARQ_ERR_ARG, "parq_tracks_note: negative count");
+    if (Q < 1 || Q > 2048 || max_tracks < 1 || max_tracks > 2048)
+        return fail(PARQ_ERR_ARG, "parq_tracks_note: Q = %d, max_tracks = %d; 1 <= Q, max_tracks <= 2048", Q, max_tracks);
+    if (B == 0) return PARQ_OK;                                         // no scene: no launch
+    if (!store || !life || !slots_host || !track_id) return fail(PARQ_ERR_ARG, "parq_tracks_note: NULL argument");
+    if (int rc = check_life_slots("parq_tracks_note", slots_host, B, S_cap)) return rc;
+    for (int b0 = 0; b0 < B; b0 += kTrackChunk)
+        HIPCHK(launch_tracks_note(static_cast<const int32_t*>(store), static_cast<int32_t*>(life), max_tracks, slots_host, b0,
+                                  std::min(B - b0, (int)kTrackChunk), track_id, Q, uid_out, hits_out, (hipStream_t)stream));
+    return PARQ_OK;
+}
+
+int parq_tracks_retire(void* store, void* life, int32_t S_cap, int32_t max_tracks, const int32_t* slots_host, int32_t B, int32_t min_hits,
+                       int32_t max_age, int32_t tentative_age, int32_t* remap_out, parq_stream stream) {
+    if (B < 0 || S_cap < 0) return fail(PARQ_ERR_ARG, "parq_tracks_retire: negative count");
+    if (max_tracks < 1 || max_tracks > 2048) return fail(PARQ_ERR_ARG, "parq_tracks_retire: max_tracks = %d; 1 <= max_tracks <= 2048", max_tracks);
+    if (min_hits < 1) return fail(PARQ_ERR_ARG, "parq_tracks_retire: min_hits = %d; a confirmed track has at least one hit", min_hits);
+    if (B == 0) return PARQ_OK;                                         // no scene: no launch
+    if (!store || !life || !slots_host) return fail(PARQ_ERR_ARG, "parq_tracks_retire: NULL argument");
+    if (int rc = check_life_slots("parq_tracks_retire", slots_host, B, S_cap)) return rc;
+    for (int b0 = 0; b0 < B; b0 += kTrackChunk)
+        HIPCHK(launch_tracks_retire(static_cast<int32_t*>(store), static_cast<int32_t*>(life), max_tracks, slots_host, b0,
+                                    std::min(B - b0, (int)kTrackChunk), min_hits, max_age, tentative_age, remap_out, (hipStream_t)stream));
+    return PARQ_OK;
+}
+
 size_t parq_set_match_workspace_bytes(int32_t I, int32_t B, int32_t Q, int32_t nmax) {
     if (I < 0 || B < 0 || Q < 1 || Q > 2048 || nmax < 1 || nmax > 2048 || (int64_t)I * B * Q > (int64_t)(1 << 28)) return 0;
     return set_match_workspace_bytes(I, B, Q, nmax);

@@ -793,6 +793,12 @@ size_t gt_tracks_update_workspace_bytes(int B, int P, int max_tracks);
 hipError_t launch_gt_tracks_update(int32_t* store, int max_tracks, const int32_t* slots_host, const int32_t* visits_host, int b0, int nb, int B,
                                    const float* corners_world, const int32_t* labels, const unsigned char* valid, int P, float iou_thresh,
                                    uint32_t seed_lo, uint32_t seed_hi, void* ws, float* iou_out, hipStream_t s);
+// track_life.hip: the life record beside the track store (uid, hits, first, last per track) for scenes [b0, b0 + nb) of a call
+// (nb <= kTrackChunk): one update noted, and the tracks unseen for too long removed in place; one launch each
+hipError_t launch_tracks_note(const int32_t* store, int32_t* life, int max_tracks, const int32_t* slots_host, int b0, int nb,
+                              const int32_t* track_id, int Q, int32_t* uid_out, int32_t* hits_out, hipStream_t s);
+hipError_t launch_tracks_retire(int32_t* store, int32_t* life, int max_tracks, const int32_t* slots_host, int b0, int nb, int min_hits,
+                                int max_age, int tentative_age, int32_t* remap_out, hipStream_t s);
 // f1_counts.hip: per-class ground-truth / prediction / true-positive counts of S scenes from a prediction and a ground-truth track
 // store (two launches); ws: f1_counts_workspace_bytes
 constexpr int kF1MaxThresholds = 8, kF1MaxClasses = 32;

@@ -1723,14 +1723,23 @@ class PARQDecoder(_Tracked, nn.Module):
         """Follow this snippet batch's detections in ``tracks`` (a ``parq_amd.SceneTracks``): ``parse_pred``, the box corners in
         world coordinates exactly as ``update_metrics`` builds them, then ``tracks.update``.  Adds ``pred_corners_world`` and
         ``track_id`` ((B,Q) int32 on the device: the object id of each kept detection, -1 for the other queries, -2 where the store
-        was full) next to ``pred_mask`` in the last iteration's dict and returns it.  Needs no ground truth, copies nothing to the
+        was full) next to ``pred_mask`` in the last iteration's dict and returns it; with ``SceneTracks(lifecycle=True)`` also
+        ``track_uid`` (the id that survives ``tracks.retire``) and ``track_hits``.  Needs no ground truth, copies nothing to the
         host and does not synchronise; under ``InFlight`` a deferred range check is settled first, as before the loss."""
         from .wrappers import Pose, raw
         self.settle_deferred()
         out = self.parse_pred(out_dict)
         obbs = out["obbs_pred"]
         out["pred_corners_world"] = Pose(raw(T_world_local)).transform(obbs.T_world_object.transform(obbs.bb3corners_object))
-        out["track_id"] = tracks.update(scene_name, out["pred_corners_world"], out["sem_cls_prob"], out["pred_mask"])
+        if not getattr(tracks, "lifecycle", False):
+            out["track_id"] = tracks.update(scene_name, out["pred_corners_world"], out["sem_cls_prob"], out["pred_mask"])
+            return out
+        # a store with a life: the stable id and the hit count of each detection's track beside its position
+        shape, dev = out["pred_mask"].shape, out["pred_corners_world"].device
+        out["track_uid"] = torch.empty(shape, dtype=torch.int32, device=dev)
+        out["track_hits"] = torch.empty(shape, dtype=torch.int32, device=dev)
+        out["track_id"] = tracks.update(scene_name, out["pred_corners_world"], out["sem_cls_prob"], out["pred_mask"],
+                                        uid_out=out["track_uid"], hits_out=out["track_hits"])
         return out
 
     def log_images(self, out_dict, obbs_padded, Ts_world_pseudoCam, Ts_world_local, T_camera_pseudoCam, rgb_img=None, calib_rgb=None,

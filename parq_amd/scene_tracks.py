@@ -13,6 +13,11 @@ set of tracks, and every metric, is the same.
 The evaluator's ground truth can live in a second store: ``update_labelled`` (parq_gt_tracks_update) follows labelled boxes under
 the same rule, and ``f1_counts`` (parq_f1_counts, csrc/f1_counts.hip) turns a prediction and a ground-truth store into the
 per-class counts of the F1 metrics; their NumPy statements are tests/f1_device_cases.py.
+
+A stream needs more than the evaluator's rule: ``SceneTracks(lifecycle=True)`` keeps a second device record per scene, the life
+(include/parq_hip.h parq_tracks_note, parq_tracks_retire, csrc/track_life.hip): a stable ``uid``, the hit count and the first / last
+sighting of every track, noted behind each update, and ``retire`` removes the tracks nobody has seen for too long, so that the
+store does not fill up.  Its NumPy statement is tests/track_life_cases.py.  Off (the default) nothing of it exists.
 """
 from __future__ import annotations
 
@@ -62,13 +67,36 @@ def check_labelled_args(corners_world, labels, valid, n_names):
     return B, P
 
 
+def check_life_out(t, what, rows, cols):
+    """An output of a life launch (uid_out, hits_out, remap_out): a contiguous int32 (rows, cols) tensor (ValueError otherwise)."""
+    if not (torch.is_tensor(t) and t.dtype == torch.int32 and tuple(t.shape) == (rows, cols) and t.is_contiguous()):
+        raise ValueError("%s must be a contiguous int32 (%d, %d) tensor, got %s %s"
+                         % (what, rows, cols, getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ()))))
+
+
+def check_retire_args(names, min_hits, max_age, tentative_age):
+    """The arguments of one retire (ValueError before anything touches the GPU); returns the names as a list."""
+    names = list(names)
+    if len(set(names)) != len(names):
+        twice = sorted({n for n in names if names.count(n) > 1}, key=str)
+        raise ValueError("retire: scene %r is listed twice; a scene is retired once per call" % (twice[0],))
+    for what, v in (("min_hits", min_hits), ("max_age", max_age), ("tentative_age", tentative_age)):
+        if isinstance(v, bool) or not isinstance(v, int) or not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError("retire: %s must be a 32-bit integer, got %r" % (what, v))
+    if min_hits < 1:
+        raise ValueError("retire: min_hits = %d; a confirmed track has at least one hit (min_hits >= 1)" % min_hits)
+    return names
+
+
 class SceneTracks:
     """A device-resident track store: ``update`` follows the detections of a snippet batch, ``boxes`` / ``to_host`` read the scenes'
     objects.  ``max_tracks`` is the capacity per scene (at most 2048): a detection that would open a track beyond it gets id -2 and
     is counted in ``dropped()`` — the store never overflows silently.  ``num_classes`` counts the background class, which is the
-    last one.  Nothing here synchronises except ``to_host`` and ``dropped``."""
+    last one.  ``lifecycle=True`` adds the tracks' life (``retire``, ``life``, ``confirmed``, ``life_to_host``, ``update``'s
+    ``uid_out`` / ``hits_out``); without it none of that exists and an update enqueues exactly what it always did.  Nothing here
+    synchronises except ``to_host``, ``life_to_host`` and ``dropped``."""
 
-    def __init__(self, max_tracks=512, conf_thresh=0.1, iou_thresh=0.1, num_classes=10, device="cuda"):
+    def __init__(self, max_tracks=512, conf_thresh=0.1, iou_thresh=0.1, num_classes=10, device="cuda", lifecycle=False):
         if isinstance(max_tracks, bool) or not isinstance(max_tracks, int) or not 1 <= max_tracks <= MAX_SIDE:
             raise ValueError("max_tracks must be an integer in [1, %d], got %r" % (MAX_SIDE, max_tracks))
         if isinstance(num_classes, bool) or not isinstance(num_classes, int) or num_classes < 2:
@@ -86,6 +114,11 @@ class SceneTracks:
         self._ws = None
         self._visits = {}                      # slot -> update_labelled visits so far (a word of the jitter's key)
         self.enqueues = 0                      # parq_tracks_update / parq_gt_tracks_update calls so far
+        self.lifecycle = bool(lifecycle)
+        self._life_words = 4 + 4 * max_tracks
+        self._life = None                      # (S_cap, life words) int32, with lifecycle only
+        self._arange = None
+        self.life_enqueues = 0                 # parq_tracks_note / parq_tracks_retire calls so far
 
     # ---- the store -----------------------------------------------------------------------------------------------------
     def _grow(self, need):
@@ -99,6 +132,26 @@ class SceneTracks:
         if cap:
             store[:cap].copy_(self._store)      # device to device, ordered on the stream: no synchronisation
         self._store = store
+        if self.lifecycle:
+            assert lib.parq_tracks_life_bytes(new_cap, self.max_tracks) == new_cap * self._life_words * 4
+            life = torch.zeros(new_cap, self._life_words, dtype=torch.int32, device=self.device)
+            if cap:
+                life[:cap].copy_(self._life)
+            self._life = life
+
+    def _need_life(self, what):
+        if not self.lifecycle:
+            raise ValueError("%s needs the tracks' life record: construct SceneTracks with lifecycle=True" % what)
+
+    def _life_out(self, t, what, rows, cols):
+        """An optional int32 (rows, cols) device tensor that a life launch fills."""
+        if t is None:
+            return None
+        self._need_life(what)
+        check_life_out(t, what, rows, cols)
+        if t.device != self.device:
+            raise RuntimeError("parq_amd.SceneTracks: %s must be on %s, got %s (no CPU fallback)" % (what, self.device, t.device))
+        return t
 
     def _slot(self, name):
         if name not in self._slots:
@@ -113,18 +166,23 @@ class SceneTracks:
 
     # ---- one snippet batch -----------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def update(self, scene_names, corners_world, sem_cls_prob, pred_mask, iou_out=None):
+    def update(self, scene_names, corners_world, sem_cls_prob, pred_mask, iou_out=None, uid_out=None, hits_out=None):
         """scene_names [B]; corners_world (B,Q,8,3); sem_cls_prob (B,Q,num_classes); pred_mask (B,Q) bool / uint8 -> track_id (B,Q)
         int32 on the device: the track of each detection, -1 for a query that is no detection, -2 for a detection the full store
         could not take.  A name listed k times is processed in k enqueues, each seeing what the previous one left.  ``iou_out``
-        (tests): a float32 (B, Q, max_tracks) device tensor that receives the IoU matrices."""
+        (tests): a float32 (B, Q, max_tracks) device tensor that receives the IoU matrices.  With ``lifecycle`` every enqueue is
+        followed by parq_tracks_note, and ``uid_out`` / ``hits_out``, int32 (B,Q) device tensors, receive each detection's stable
+        id (-1 / -2 as in track_id) and the hits of its track, this one included."""
         names = list(scene_names)
         B, Q = check_tracks_args(corners_world, sem_cls_prob, pred_mask, len(names), self.num_classes)
+        if uid_out is not None or hits_out is not None:
+            self._need_life("update(uid_out= / hits_out=)")
         if self.device.index is None and corners_world.is_cuda:
             self.device = corners_world.device                    # "cuda": the device of the first batch
         for t in (corners_world, sem_cls_prob, pred_mask):
             if t.device != self.device:
                 raise RuntimeError("parq_amd.SceneTracks: tensors must be on %s, got %s (no CPU fallback)" % (self.device, t.device))
+        uid_out, hits_out = self._life_out(uid_out, "uid_out", B, Q), self._life_out(hits_out, "hits_out", B, Q)
         corners = corners_world.detach().to(torch.float32).contiguous()
         prob = sem_cls_prob.detach().to(torch.float32).contiguous()
         mask = (pred_mask.view(torch.uint8) if pred_mask.dtype == torch.bool else pred_mask).contiguous()
@@ -163,6 +221,21 @@ class SceneTracks:
                                                   C.c_void_p(t_w.data_ptr()), None if i_w is None else _lib.ptr(i_w), stream),
                            "parq_tracks_update")
                 self.enqueues += 1
+                if self.lifecycle:
+                    u_w, h_w = uid_out, hits_out
+                    if not whole:
+                        u_w = None if uid_out is None else torch.empty(len(wave), Q, dtype=torch.int32, device=self.device)
+                        h_w = None if hits_out is None else torch.empty(len(wave), Q, dtype=torch.int32, device=self.device)
+                    dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+                    _lib.check(lib.parq_tracks_note(C.c_void_p(self._store.data_ptr()), C.c_void_p(self._life.data_ptr()),
+                                                    self._store.shape[0], self.max_tracks, arr, len(wave), C.c_void_p(t_w.data_ptr()), Q,
+                                                    dp(u_w), dp(h_w), stream), "parq_tracks_note")
+                    self.life_enqueues += 1
+                    if not whole:
+                        if uid_out is not None:
+                            uid_out.index_copy_(0, idx, u_w)
+                        if hits_out is not None:
+                            hits_out.index_copy_(0, idx, h_w)
                 if not whole:
                     track_id.index_copy_(0, idx, t_w)
                     if iou_out is not None:
@@ -176,6 +249,8 @@ class SceneTracks:
         moved by the hashed jitter of (seed, slot, visit, rank among the valid rows); the rest is ``update``'s rule.  A name listed
         k times is processed in k enqueues, and each counts as a visit of its scene.  Returns nothing and does not synchronise.
         ``iou_out`` (tests): a float32 (B, P, max_tracks) device tensor that receives the IoU matrices."""
+        if self.lifecycle:
+            raise ValueError("update_labelled: ground truth has no life; feed a SceneTracks built without lifecycle=True")
         names = list(scene_names)
         B, P = check_labelled_args(corners_world, labels, valid, len(names))
         if self.device.index is None and corners_world.is_cuda:
@@ -263,15 +338,79 @@ class SceneTracks:
         return list(self._slots)
 
     def reset(self, name=None):
-        """Forget every scene, or empty one scene's slot (its name keeps the slot)."""
+        """Forget every scene, or empty one scene's slot (its name keeps the slot).  A slot's life goes with its count: its clock and
+        its uids start from 0 again."""
         if name is None:
             self._slots = {}
             self._visits = {}
             if self._store is not None:
                 self._store.zero_()
+            if self._life is not None:
+                self._life.zero_()
         elif name in self._slots:
             self._visits.pop(self._slots[name], None)
             self._store[self._slots[name], :2].zero_()
+            if self._life is not None:
+                self._life[self._slots[name], :4].zero_()
+
+    # ---- the tracks' life (lifecycle=True) -------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def retire(self, names=None, min_hits=3, max_age=30, tentative_age=1, remap_out=None):
+        """Remove the tracks nobody has seen for too long (include/parq_hip.h parq_tracks_retire) from the scenes ``names`` (None:
+        every scene, in ``names()`` order).  A track's age is the number of its scene's updates since it was last matched; a track
+        with at least ``min_hits`` hits is confirmed and goes when its age exceeds ``max_age``, any other when it exceeds
+        ``tentative_age`` (negative: never).  The kept tracks move up in their order, so ``track_id``, a position, changes here and
+        ``track_uid`` does not; ``remap_out``, an int32 (len(names), max_tracks) device tensor, receives each old position's new one
+        (-1: removed or unused).  One enqueue; does not synchronise."""
+        self._need_life("retire")
+        names = check_retire_args(self.names() if names is None else names, min_hits, max_age, tentative_age)
+        for n in names:
+            if n not in self._slots:
+                raise KeyError(n)
+        if remap_out is not None:
+            self._life_out(remap_out, "remap_out", len(names), self.max_tracks)
+        if not names:
+            return
+        lib = _lib.load()
+        arr = (C.c_int32 * len(names))(*[self._slots[n] for n in names])
+        with torch.cuda.device(self.device):
+            _lib.check(lib.parq_tracks_retire(C.c_void_p(self._store.data_ptr()), C.c_void_p(self._life.data_ptr()), self._store.shape[0],
+                                              self.max_tracks, arr, len(names), min_hits, max_age, tentative_age,
+                                              None if remap_out is None else C.c_void_p(remap_out.data_ptr()), _lib.stream_ptr()),
+                       "parq_tracks_retire")
+        self.life_enqueues += 1
+
+    def life(self, name):
+        """Device views of one scene's life, nothing copied: {"step" (0-dim int32: the scene's updates so far), "uid", "hits",
+        "first", "last" (max_tracks) int32}; rows from the scene's ``count`` on are unused."""
+        self._need_life("life")
+        mt = self.max_tracks
+        row = self._life[self._slots[name]]
+        return {"step": row[0], "uid": row[4:4 + mt], "hits": row[4 + mt:4 + 2 * mt], "first": row[4 + 2 * mt:4 + 3 * mt],
+                "last": row[4 + 3 * mt:4 + 4 * mt]}
+
+    def confirmed(self, name, min_hits=3):
+        """(max_tracks,) bool on the device: the scene's tracks with at least ``min_hits`` hits; rows from ``count`` on are false.
+        It is ``parq_amd.draw_boxes``'s ``keep=`` for ``boxes(name)`` (after an ``[None]``).  Does not synchronise."""
+        self._need_life("confirmed")
+        if self._arange is None or self._arange.device != self.device:
+            self._arange = torch.arange(self.max_tracks, dtype=torch.int32, device=self.device)
+        return (self.life(name)["hits"] >= min_hits) & (self._arange < self._views(self._slots[name])["count"])
+
+    def life_to_host(self, name=None):
+        """``to_host`` with each track's life: entries ``[class, corners (8,3) float32, score (np.float32), id, uid, hits, first,
+        last]``, a list for one scene, {name: list} for all.  Synchronises (one copy of the store and one of the life)."""
+        self._need_life("life_to_host")
+        tracks = self.to_host(name)
+        if self._life is None:
+            return tracks
+        host = self._life[:len(self._slots)].cpu().numpy()
+        mt = self.max_tracks
+        for n, entries in ([(name, tracks)] if name is not None else tracks.items()):
+            row = host[self._slots[n]]
+            for e in entries:
+                e.extend(int(row[4 + f * mt + e[3]]) for f in range(4))
+        return tracks
 
 
 F1_MAX_THRESHOLDS = 8
