@@ -673,6 +673,59 @@ int (parq_f1_counts)(const void *pred_store, int32_t pred_max_tracks, const void
                    const double *thresholds_host, int32_t T, int32_t K, void *workspace, size_t workspace_bytes, int64_t *counts,
                    int64_t *invalid, double *best_iou /*NULL in normal use*/, parq_stream stream);
 
+/* ---- average precision per class on the device from the two track stores (csrc/avg_precision.hip) -------------------------------
+ * mAP@0.25 / mAP@0.5 and the precision-recall curve behind them.  This is NOT a number of the reference: its evaluator computes
+ * F1 at one confidence threshold and no AP, so there is no reference vector to pin against.  The oracle is the rule below, its
+ * NumPy statement (tests/average_precision_cases.py ap_statement; parq_amd/f1_eval.py average_precision_host is the host
+ * calculator's copy) and an independent sequential formulation (same file, ap_sequential).  The stores hold the tracks selected
+ * at CONF_THRESH, so a curve ends at that score; evaluate with a low threshold for the full curve.
+ * Inputs: pred_store / gt_store and their capacities, S, thresholds_host (T float64 on the HOST, 1 <= T <= 8) and K (1..32), all
+ * exactly as for parq_f1_counts: slot s < S of both stores is the same scene, a slot whose count is outside [0, capacity] counts as
+ * empty.  N = S * pred_max_tracks positions; N above 1 << 20 is refused.
+ * Population.  A prediction track is RANKED when its label is in [0, K) and its score is not NaN; any other is counted in
+ *   invalid[1] and nowhere else.  A ground-truth track with a label outside [0, K) goes to invalid[0].
+ * Target.  For a ranked prediction p of class c in scene s, walk the scene's ground-truth tracks i with label c in index order, with
+ *   v_i = iou3d(canon(gt i), canon(pred p)) (float64 from the stores' float32 corners, the ground truth as the first box: the
+ *   routine and orientation of parq_f1_counts, so the two entries see one IoU matrix):
+ *     m = "nothing seen", target = -1;  for i: if nothing seen yet and v_i is no NaN, or v_i > m:  m = v_i, target = i.
+ *   best_p = m, or 0 when target_p = -1.  So target_p is the FIRST index that reaches the maximum, with every IoU equal to 0 the
+ *   target is the first same-class box, a NaN never raises the maximum, and without a same-class ground truth (or with nothing but
+ *   NaN) target_p = -1 and best_p = 0.  An unranked prediction below the slot's count has target -1 and best 0.
+ * Order.  Within a class, predictions are ordered by a 32-bit key of the float32 score, DESCENDING, then slot ascending, then
+ *   position ascending:  b = bits(score);  key = b ^ ((b >> 31) ? 0xffffffff : 0x80000000).  The key is the rule, so -0.0 ranks
+ *   after +0.0.  Classes are laid out one after another, class 0 first: class c occupies ranks [class_start[c], class_start[c+1]).
+ * True positive.  At threshold t, prediction p is a true positive iff  target_p >= 0,  best_p > thresholds[t] (float64, strict),
+ *   and no prediction q of the same scene with target_q == target_p and best_q > thresholds[t] precedes p in the order.  Everything
+ *   else is a false positive.  This is the PASCAL-VOC / VoteNet sequential rule (walk the predictions by falling score; a
+ *   prediction claims its arg-max box; a box can be claimed once; there is no second choice) in its order-free form: the two are
+ *   equal (the first passing claimant of a box in the order is the one the walk lets claim it), which the CPU tier checks.
+ * Curve and AP.  Per (t, c): n ranked predictions, npos ground-truth tracks, tp_r the cumulative true positives at rank r = 1..n;
+ *   prec_r = (double) tp_r / (double) r;   pmax_r = max over r' >= r of prec_r';
+ *   ap[t][c] = (sum over the ranks r that are true positives, of pmax_r) / (double) npos      (all-point interpolation with each
+ *   recall step 1 / npos taken out of the sum);  ap = 0 when npos == 0 or n == 0.
+ *   The order of the float64 sum is part of the rule: acc = 0.0, then the true-positive ranks in DESCENDING rank (r = n down to 1),
+ *   acc = acc + pmax_r, one lane, each add rounded once, nothing contracted; then ONE division.
+ * Outputs, all on the device: ap (T, K) float64; counts (2, K) int64: ground-truth and ranked prediction tracks per class;
+ * invalid (2) int64.  Optionally, together or all NULL, for tests and for users who plot curves: order (N) int32:
+ * slot * pred_max_tracks + position of every rank, class-major, the tail from class_start[K] on filled with -1; class_start
+ * (K + 1) int32; cum_tp (T, N) int32: tp_r at each filled entry (the tail 0); pred_best (S, pred_max_tracks) float64 and
+ * pred_target (S, pred_max_tracks) int32: rows from a slot's count onwards are not written.
+ * Launches: the target pass (one wavefront per prediction track, the sort keys class | ~key | position beside it), the label
+ * counts, the true-positive flags (one workgroup per scene), a bitonic sort of the N keys padded to a power of two (strides below
+ * 2048 inside LDS tiles), the curves (one workgroup per (t, c)).  No atomics, nothing allocated, the call only enqueues; the number
+ * and geometry of the launches depend on the arguments, never on device data; every number read from device memory is checked
+ * before it indexes anything; two calls give the same bits.  workspace: parq_average_precision_workspace_bytes(S, pred_max_tracks,
+ * gt_max_tracks, T, K) bytes (0 for arguments the entry refuses), 16-byte aligned.  S = 0 is valid and zeroes ap, counts and invalid
+ * (and class_start).  PARQ_ERR_ARG, with nothing launched: S negative or above 65535, a capacity outside [1, 2048], N above
+ * 1 << 20, T outside [1, 8], K outside [1, 32], a NULL that is needed, optional outputs given only in part, a workspace too small
+ * or misaligned.  (Parenthesised names, as above; both entries are typed in _lib.AP_SYMBOLS.) */
+size_t (parq_average_precision_workspace_bytes)(int32_t S, int32_t pred_max_tracks, int32_t gt_max_tracks, int32_t T, int32_t K);
+int (parq_average_precision)(const void *pred_store, int32_t pred_max_tracks, const void *gt_store, int32_t gt_max_tracks, int32_t S,
+                           const double *thresholds_host, int32_t T, int32_t K, void *workspace, size_t workspace_bytes, double *ap,
+                           int64_t *counts, int64_t *invalid, int32_t *order /*or NULL*/, int32_t *class_start /*or NULL*/,
+                           int32_t *cum_tp /*or NULL*/, double *pred_best /*or NULL*/, int32_t *pred_target /*or NULL*/,
+                           parq_stream stream);
+
 /* ---- a life for the tracks of a store: hits, age, stable ids and retirement (csrc/track_life.hip), one launch each ---------------
  * The track store above never removes a track and keeps no history.  A stream needs both, so a store may have a second, parallel
  * record, the LIFE: parq_tracks_life_bytes(S_cap, max_tracks) = S_cap * (4 + 4 * max_tracks) * 4 bytes of DEVICE memory (0 for

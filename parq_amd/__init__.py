@@ -12,6 +12,8 @@ Public surface mirrors the reference (ymingxie/PARQ):
                  lifecycle=True (no counterpart) adds hits, age, stable uids and retire() for streams that never end
     f1_counts    (utils/f1_eval.py:36 count_matches over all scenes)  the evaluator's per-class counts from a prediction and a
                  ground-truth SceneTracks, on the device
+    average_precision (no counterpart: the reference's evaluator has no AP)  AP per IoU threshold and class, and the curve behind
+                 it, from the same two stores, on the device
     FramePrep, resize_frames, resized_intrinsics, gravity_aligned, snippet_local (datasets/transforms.py:211 ScanNetBaseTransform)
                  raw uint8 frames, intrinsics and T_world_camera prepared on the device into the batch PARQ.forward reads
     SnippetTargets, select_views (scripts/scannet_preprocessing/generate_scannet_anno_snippet.py, the offline annotation pass)
@@ -45,7 +47,7 @@ def __getattr__(name):
     if name in ("draw_boxes", "box_colors"):
         from . import draw
         return getattr(draw, name)
-    if name in ("SceneTracks", "f1_counts"):
+    if name in ("SceneTracks", "f1_counts", "average_precision"):
         from . import scene_tracks
         return getattr(scene_tracks, name)
     if name in ("FramePrep", "resize_frames", "resized_intrinsics", "gravity_aligned", "snippet_local"):

@@ -191,6 +191,13 @@ LIFE_SYMBOLS = {
     "parq_tracks_retire": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp, _vp]),
 }
 
+# average precision from the two track stores (include/parq_hip.h parq_average_precision): a table of its own for the same reason
+AP_SYMBOLS = {
+    "parq_average_precision_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "parq_average_precision": (C.c_int, [_vp, _i32, _vp, _i32, _i32, C.POINTER(C.c_double), _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -217,7 +224,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc, --offload-arch=gfx950). "
             "There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in [kv for table in ALL_TABLES + (EVAL_SYMBOLS, LIFE_SYMBOLS) for kv in table.items()]:
+    for name, (res, args) in [kv for table in ALL_TABLES + (EVAL_SYMBOLS, LIFE_SYMBOLS, AP_SYMBOLS) for kv in table.items()]:
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -2989,6 +2989,48 @@ int parq_f1_counts(const void* pred_store, int32_t pred_max_tracks, const void* 
     return PARQ_OK;
 }
 
+size_t parq_average_precision_workspace_bytes(int32_t S, int32_t pred_max_tracks, int32_t gt_max_tracks, int32_t T, int32_t K) {
+    if (S < 0 || S > 65535 || pred_max_tracks < 1 || pred_max_tracks > 2048 || gt_max_tracks < 1 || gt_max_tracks > 2048 || T < 1 ||
+        T > kF1MaxThresholds || K < 1 || K > kF1MaxClasses || (int64_t)S * pred_max_tracks > kApMaxPositions)
+        return 0;
+    return average_precision_workspace_bytes(S, pred_max_tracks, T, K);
+}
+
+int parq_average_precision(const void* pred_store, int32_t pred_max_tracks, const void* gt_store, int32_t gt_max_tracks, int32_t S,
+                           const double* thresholds_host, int32_t T, int32_t K, void* workspace, size_t workspace_bytes, double* ap,
+                           int64_t* counts, int64_t* invalid, int32_t* order, int32_t* class_start, int32_t* cum_tp, double* pred_best,
+                           int32_t* pred_target, parq_stream stream) {
+    if (S < 0) return fail(PARQ_ERR_ARG, "parq_average_precision: negative count");
+    if (S > 65535 || pred_max_tracks < 1 || pred_max_tracks > 2048 || gt_max_tracks < 1 || gt_max_tracks > 2048 || T < 1 || T > kF1MaxThresholds ||
+        K < 1 || K > kF1MaxClasses)
+        return fail(PARQ_ERR_ARG, "parq_average_precision: S = %d, capacities %d / %d, T = %d, K = %d; S <= 65535, 1 <= capacity <= 2048, "
+                    "1 <= T <= %d, 1 <= K <= %d", S, pred_max_tracks, gt_max_tracks, T, K, kF1MaxThresholds, kF1MaxClasses);
+    if ((int64_t)S * pred_max_tracks > kApMaxPositions)
+        return fail(PARQ_ERR_ARG, "parq_average_precision: S * pred_max_tracks = %lld; at most %d positions are ranked",
+                    (long long)S * pred_max_tracks, kApMaxPositions);
+    if (!thresholds_host || !ap || !counts || !invalid) return fail(PARQ_ERR_ARG, "parq_average_precision: NULL argument");
+    const int given = (order != nullptr) + (class_start != nullptr) + (cum_tp != nullptr) + (pred_best != nullptr) + (pred_target != nullptr);
+    if (given != 0 && given != 5)
+        return fail(PARQ_ERR_ARG, "parq_average_precision: order, class_start, cum_tp, pred_best and pred_target are given together or all NULL");
+    if (S == 0) {                                                       // no scene: everything is zero
+        HIPCHK(hipMemsetAsync(ap, 0, (size_t)T * K * 8, (hipStream_t)stream));
+        HIPCHK(hipMemsetAsync(counts, 0, (size_t)2 * K * 8, (hipStream_t)stream));
+        HIPCHK(hipMemsetAsync(invalid, 0, 16, (hipStream_t)stream));
+        if (class_start) HIPCHK(hipMemsetAsync(class_start, 0, (size_t)(K + 1) * 4, (hipStream_t)stream));
+        return PARQ_OK;
+    }
+    if (!pred_store || !gt_store || !workspace) return fail(PARQ_ERR_ARG, "parq_average_precision: NULL argument");
+    const size_t need = parq_average_precision_workspace_bytes(S, pred_max_tracks, gt_max_tracks, T, K);
+    if (workspace_bytes < need) return fail(PARQ_ERR_ARG, "parq_average_precision: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 15) return fail(PARQ_ERR_ARG, "parq_average_precision: the workspace must be 16-byte aligned");
+    F1Thresholds thr;
+    for (int t = 0; t < kF1MaxThresholds; ++t) thr.thr[t] = t < T ? thresholds_host[t] : 0.0;
+    HIPCHK(launch_average_precision(static_cast<const int32_t*>(pred_store), pred_max_tracks, static_cast<const int32_t*>(gt_store),
+                                    gt_max_tracks, S, thr, T, K, workspace, ap, counts, invalid, order, class_start, cum_tp, pred_best,
+                                    pred_target, (hipStream_t)stream));
+    return PARQ_OK;
+}
+
 size_t parq_tracks_life_bytes(int32_t S_cap, int32_t max_tracks) {
     if (S_cap < 0 || max_tracks < 1 || max_tracks > 2048) return 0;
     return (size_t)S_cap * (4 + 4 * (size_t)max_tracks) * 4;

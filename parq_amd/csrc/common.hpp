@@ -809,6 +809,15 @@ struct F1Thresholds {
 hipError_t launch_f1_counts(const int32_t* pred_store, int pred_max_tracks, const int32_t* gt_store, int gt_max_tracks, int S,
                             const F1Thresholds& thr, int T, int K, void* ws, int64_t* counts, int64_t* invalid, double* best_iou,
                             hipStream_t s);
+// avg_precision.hip: average precision per (threshold, class) of S scenes from the same two stores (target pass, counts, true-positive
+// flags, a bitonic sort of S * pred_max_tracks keys padded to a power of two, the curves); ws: average_precision_workspace_bytes.
+// The five optional outputs are all given or all NULL.
+constexpr int kApMaxPositions = 1 << 20;
+size_t average_precision_workspace_bytes(int S, int pred_max_tracks, int T, int K);
+hipError_t launch_average_precision(const int32_t* pred_store, int pred_max_tracks, const int32_t* gt_store, int gt_max_tracks, int S,
+                                    const F1Thresholds& thr, int T, int K, void* ws, double* ap, int64_t* counts, int64_t* invalid,
+                                    int32_t* order, int32_t* class_start, int32_t* cum_tp, double* pred_best, int32_t* pred_target,
+                                    hipStream_t s);
 // setmatch.hip: the set loss's matcher for all I * B (iteration, scene) problems (cost, launch_assign_max, pairs, finish: four
 // launches; I * B >= 1, Q and nmax in [1, 2048]); ws: set_match_workspace_bytes, 16-byte aligned
 size_t set_match_workspace_bytes(int I, int B, int Q, int nmax);

@@ -322,6 +322,11 @@ class PARQDecoder(_Tracked, nn.Module):
     # is then the hashed one (F1Calculator gt_jitter="hash"), not NumPy's draw: the metrics are those of the host calculator in
     # that mode.  Switch it between reset_metrics() and the first update_metrics(), as tracks_on_device.
     gt_tracks_on_device = False
+    # True (on the class or on one module): compute_metrics adds "<thr>_mAP" and "<thr>_AP_<class name>" per IoU threshold
+    # (F1Calculator average_precision; include/parq_hip.h parq_average_precision states the rule).  With the three flags above on, the
+    # values come from the device and ride in the counts' one copy; else from the host statement.  Not a number of the reference,
+    # whose evaluator has no AP.  False: compute_metrics returns exactly the keys it always did.
+    average_precision = False
     # True (on the class or on one module): log_images draws the predicted / ground-truth boxes of scene 0 into the RGB views on the
     # device (parq_amd/draw.py).  False: log_images returns {} and costs nothing, as before the drawing existed.
     draw_images = False
@@ -1788,6 +1793,7 @@ class PARQDecoder(_Tracked, nn.Module):
                 calc.iou_device = next(self.parameters()).device
             calc.track_store = "device" if (self.metrics_on_device and self.tracks_on_device) else "host"
             calc.gt_store = "device" if self._gt_tracks_on_device() else "host"
+            calc.average_precision = bool(self.average_precision)
             metrics.update(calc.compute_metrics())
         return metrics
 

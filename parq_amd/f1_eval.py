@@ -21,6 +21,10 @@ stated in include/parq_hip.h (``gt_jitter="hash"`` is the same rule on the host,
 enqueues, and ``compute_metrics`` reads the per-class counts of ``parq_f1_counts`` with one small copy.  The device side
 of the rest of the evaluation path (box building, validity window, NMS) is ``PARQDecoder.parse_pred``.
 
+``F1Calculator(average_precision=True)`` adds mAP and the per-class AP at every IoU threshold.  The reference's evaluator has no
+AP: the rule is this project's, stated in include/parq_hip.h (``parq_average_precision``), ``average_precision_host`` below is its
+copy for the host paths, and with ``gt_store="device"`` the values come from the device in the counts' one copy.
+
 The oriented IoU follows the reference's convention (utils/f1_eval.py:46-48,77-107): corners are re-ordered with
 [4,0,1,5,7,3,2,6] and rotated by +90 deg about x, the first four re-ordered corners (taken in reverse) are the footprint
 polygon in the rotated (x, z) plane, the overlap height is min(y of corner 0) - max(y of corner 4), and the volume is the
@@ -191,6 +195,100 @@ def f1_from_counts(gts, preds, tps, verbose=False):
     return acc, rec, f1
 
 
+# ---- average precision (include/parq_hip.h parq_average_precision: the rule in full; the reference's evaluator has no AP) ------------
+def score_key(score) -> int:
+    """The 32-bit order key of a float32 score: larger key = ranks earlier; -0.0 ranks after +0.0."""
+    b = int(np.asarray(score, np.float32).reshape(()).view(np.uint32))
+    return b ^ (0xFFFFFFFF if b >> 31 else 0x80000000)
+
+
+def _host_pair_iou(gt_corners, pred_corners):
+    return iou3d(canonical(gt_corners), canonical(pred_corners))[0]
+
+
+def average_precision_host(preds, gts, thresholds, num_classes=len(CARE_CLASSES), ious=None, pair_iou=None):
+    """parq_average_precision's rule on the host: the statement's copy (tests/average_precision_cases.py ap_statement) for the
+    calculator's host paths, and the oracle of its device path.  preds / gts: per-scene lists of entries [class, corners (8,3),
+    score, ...] / (class, corners, ...), scene s of both the same scene.  ``ious``: per scene the float64 (ground truth,
+    predictions) matrix when it has been computed already, else ``pair_iou(gt corners, pred corners)`` (default: the host iou3d)
+    fills in the same-class pairs.  Returns {"ap" (T, K) float64, "counts" (2, K) int64, "invalid" (2,) int64, "order"
+    [(scene, position)] class-major, "class_start" (K + 1,), "cum_tp" (T, ranked) int32, "best" / "target" per scene}."""
+    K, T = int(num_classes), len(thresholds)
+    pair_iou = pair_iou or _host_pair_iou
+    counts, invalid = np.zeros((2, K), np.int64), np.zeros(2, np.int64)
+    ranked, best, target = [], [], []
+    for s, (ps, gs) in enumerate(zip(preds, gts)):
+        for g in gs:
+            if 0 <= g[0] < K:
+                counts[0, g[0]] += 1
+            else:
+                invalid[0] += 1
+        b, tg = np.zeros(len(ps), np.float64), -np.ones(len(ps), np.int64)
+        for j, p in enumerate(ps):
+            c = p[0]
+            if not (0 <= c < K) or np.isnan(np.float32(p[2])):
+                invalid[1] += 1
+                continue
+            counts[1, c] += 1
+            ranked.append((int(c), 0xFFFFFFFF - score_key(p[2]), s, j))
+            m = None                                                    # nothing seen
+            for i, g in enumerate(gs):
+                if g[0] != c:
+                    continue
+                v = float(ious[s][i, j]) if ious is not None else float(pair_iou(g[1], p[1]))
+                if (m is None and v == v) or (m is not None and v > m):
+                    m, tg[j] = v, i
+            b[j] = m if tg[j] >= 0 else 0.0
+        best.append(b)
+        target.append(tg)
+    ranked.sort()
+    n = len(ranked)
+    class_start = np.zeros(K + 1, np.int64)
+    for c, _, _, _ in ranked:
+        class_start[c + 1:] += 1
+    # true positives: per (scene, box) the first claimant in the order whose IoU passes
+    flags = np.zeros((T, n), bool)
+    for t, thr in enumerate(thresholds):
+        claimed = set()
+        for r, (_, _, s, j) in enumerate(ranked):
+            if target[s][j] >= 0 and best[s][j] > thr and (s, int(target[s][j])) not in claimed:
+                claimed.add((s, int(target[s][j])))
+                flags[t, r] = True
+    ap, cum_tp = np.zeros((T, K), np.float64), np.zeros((T, n), np.int32)
+    for t in range(T):
+        for c in range(K):
+            lo, hi = int(class_start[c]), int(class_start[c + 1])
+            if hi == lo:
+                continue
+            tp = np.cumsum(flags[t, lo:hi]).astype(np.int32)
+            cum_tp[t, lo:hi] = tp
+            prec = tp.astype(np.float64) / np.arange(1, hi - lo + 1, dtype=np.float64)
+            pmax = np.maximum.accumulate(prec[::-1])[::-1]
+            acc = np.float64(0.0)
+            for r in range(hi - lo - 1, -1, -1):                        # descending rank: the order is part of the rule
+                if flags[t, lo + r]:
+                    acc = acc + pmax[r]
+            if counts[0, c] > 0:
+                ap[t, c] = acc / np.float64(counts[0, c])
+    return dict(ap=ap, counts=counts, invalid=invalid, order=[(s, j) for _, _, s, j in ranked], class_start=class_start, cum_tp=cum_tp,
+                best=best, target=target)
+
+
+def ap_metrics(ap, gt_counts, thresholds):
+    """{"<thr>_mAP", "<thr>_AP_<class name>"}: mAP is the mean, in class order, over the care classes with at least one
+    ground-truth track (0 if there is none)."""
+    metrics = {}
+    have = [c for c in CARE_CLASSES if gt_counts[c] > 0]
+    for t, thr in enumerate(thresholds):
+        total = 0.0
+        for c in have:
+            total = total + float(ap[t][c])
+        metrics["{}_mAP".format(thr)] = total / len(have) if have else 0.0
+        for c, name in CARE_CLASSES.items():
+            metrics["{}_AP_{}".format(thr, name)] = float(ap[t][c])
+    return metrics
+
+
 def canonical_stack(entries) -> np.ndarray:
     """(n, 8, 3) float64 canonical() corners of a list of entries [class, corners, ...]."""
     if not len(entries):
@@ -321,12 +419,17 @@ class F1Calculator:
     ``gt_store``: "host" (default), or "device" (needs ``track_store="device"``; the jitter is then the hash): the ground truth
     lives in a second ``SceneTracks`` fed by ``update_labelled``, ``step`` waits for nothing, and ``compute_metrics`` takes the
     per-class counts from ``parq_f1_counts`` with one small copy.  ``step`` then takes the ground truth as the list of per-scene
-    dicts or as one padded dict {"labels" (B,P), "gt_corners_world" (B,P,8,3), "valid" (B,P)}."""
+    dicts or as one padded dict {"labels" (B,P), "gt_corners_world" (B,P,8,3), "valid" (B,P)}.
+    ``average_precision``: False (default) returns exactly the F1 keys.  True adds "<thr>_mAP" and "<thr>_AP_<class name>" per
+    threshold (``ap_metrics``; the rule is parq_average_precision's in include/parq_hip.h, and it is not a number of the
+    reference, whose evaluator has no AP): with ``gt_store="device"`` from ``parq_average_precision``, its values riding in the
+    counts' one copy, else from ``average_precision_host`` over ``preds`` / ``gts``.  The tracks are those selected at
+    ``conf_thresh``, so the curve ends at that score."""
 
     track_capacity = 2048
 
     def __init__(self, conf_thresh, f1_iou_thresh=(0.25, 0.5, 0.7), verbose=False, iou_device=None, iou_backend=None,
-                 track_store="host", gt_jitter="numpy", gt_seed=0, gt_store="host"):
+                 track_store="host", gt_jitter="numpy", gt_seed=0, gt_store="host", average_precision=False):
         if track_store not in ("host", "device"):
             raise ValueError("track_store must be 'host' or 'device', got %r" % (track_store,))
         if track_store == "device" and iou_device is None:
@@ -345,6 +448,8 @@ class F1Calculator:
         self._gt_tracks = None
         self.count_launches = 0                # parq_f1_counts calls so far
         self.count_copies = 0                  # device-to-host copies compute_metrics made on the gt_store="device" path
+        self.average_precision = bool(average_precision)
+        self.ap_launches = 0                   # parq_average_precision calls so far
         self.f1_iou_thresh = list(f1_iou_thresh)
         self.conf_thresh = conf_thresh
         self.iou_thresh = 0.1
@@ -580,18 +685,30 @@ class F1Calculator:
         import torch
         from .scene_tracks import f1_counts
         K, T = len(CARE_CLASSES), len(self.f1_iou_thresh)
+        self._ap_host = None                   # with average_precision: (ap (T, K) float64, ground-truth tracks per class) of this call
         if self._tracks is None or self._gt_tracks is None or not self._tracks._slots:
+            if self.average_precision:
+                self._ap_host = (np.zeros((T, K), np.float64), np.zeros(K, np.int64))
             return [0] * K, [0] * K, [[0] * K for _ in range(T)]
         assert self._gt_tracks._slots == self._tracks._slots, "the two device stores must number the scenes alike"
         S, n = len(self._tracks._slots), (2 + T) * K + 2
+        n_ap = (T + 2) * K + 2 if self.average_precision else 0       # ap (its float64 bits), counts, invalid behind the rest
         with torch.cuda.device(self._tracks.device):
-            buf = torch.empty(n + 2 * S, dtype=torch.int64, device=self._tracks.device)
+            buf = torch.empty(n + 2 * S + n_ap, dtype=torch.int64, device=self._tracks.device)
             f1_counts(self._tracks, self._gt_tracks, self.f1_iou_thresh, K, out=buf)
             self.count_launches += 1
             buf[n:n + S] = self._tracks._store[:S, 1]
-            buf[n + S:] = self._gt_tracks._store[:S, 1]
+            buf[n + S:n + 2 * S] = self._gt_tracks._store[:S, 1]
+            if n_ap:
+                from .scene_tracks import average_precision
+                average_precision(self._tracks, self._gt_tracks, self.f1_iou_thresh, K, out=buf[n + 2 * S:])
+                self.ap_launches += 1
             host = buf.cpu().numpy()
             self.count_copies += 1
+        if n_ap:
+            tail = host[n + 2 * S:]
+            self._ap_host = (tail[:T * K].view(np.float64).reshape(T, K).copy(), tail[T * K:(T + 1) * K].copy())
+            host = host[:n + 2 * S]
         names = list(self._tracks._slots)
         for what, col in (("detections", host[n:n + S]), ("ground-truth boxes", host[n + S:])):
             lost = {names[s]: int(k) for s, k in enumerate(col) if k}
@@ -613,6 +730,8 @@ class F1Calculator:
                 metrics["{}_accuracy".format(thr)] = acc
                 metrics["{}_recall".format(thr)] = rec
                 metrics["{}_f1".format(thr)] = f1
+            if self.average_precision:
+                metrics.update(ap_metrics(self._ap_host[0], self._ap_host[1], self.f1_iou_thresh))
             return metrics
         if self.on_device_tracks:
             self.pull_tracks()
@@ -623,6 +742,11 @@ class F1Calculator:
             metrics["{}_accuracy".format(thr)] = acc
             metrics["{}_recall".format(thr)] = rec
             metrics["{}_f1".format(thr)] = f1
+        if self.average_precision:
+            names = list(self.preds)
+            res = average_precision_host([self.preds[s] for s in names], [self.gts[s] for s in names], self.f1_iou_thresh, len(CARE_CLASSES),
+                                         ious=None if ious is None else [ious[s] for s in names])
+            metrics.update(ap_metrics(res["ap"], res["counts"][0], self.f1_iou_thresh))
         return metrics
 
 

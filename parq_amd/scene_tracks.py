@@ -12,7 +12,9 @@ set of tracks, and every metric, is the same.
 
 The evaluator's ground truth can live in a second store: ``update_labelled`` (parq_gt_tracks_update) follows labelled boxes under
 the same rule, and ``f1_counts`` (parq_f1_counts, csrc/f1_counts.hip) turns a prediction and a ground-truth store into the
-per-class counts of the F1 metrics; their NumPy statements are tests/f1_device_cases.py.
+per-class counts of the F1 metrics; their NumPy statements are tests/f1_device_cases.py.  ``average_precision``
+(parq_average_precision, csrc/avg_precision.hip) gives AP per IoU threshold and class from the same two stores, a metric the
+reference's evaluator does not have; its NumPy statement is tests/average_precision_cases.py.
 
 A stream needs more than the evaluator's rule: ``SceneTracks(lifecycle=True)`` keeps a second device record per scene, the life
 (include/parq_hip.h parq_tracks_note, parq_tracks_retire, csrc/track_life.hip): a stable ``uid``, the hit count and the first / last
@@ -460,3 +462,70 @@ def f1_counts(pred_tracks, gt_tracks, thresholds, num_classes=9, best_iou_out=No
                                       None if best_iou_out is None else C.c_void_p(best_iou_out.data_ptr()), _lib.stream_ptr()),
                    "parq_f1_counts")
     return counts, invalid
+
+
+AP_MAX_POSITIONS = 1 << 20  # scenes x prediction capacity that parq_average_precision ranks in one call
+
+
+def check_average_precision_args(pred_tracks, gt_tracks, thresholds, num_classes):
+    """The arguments of ``average_precision`` (an error before anything touches the GPU); returns (thresholds as floats, scenes)."""
+    thr = [float(t) for t in thresholds]
+    if not 1 <= len(thr) <= F1_MAX_THRESHOLDS:
+        raise ValueError("average_precision takes 1 to %d thresholds, got %d" % (F1_MAX_THRESHOLDS, len(thr)))
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 1 <= num_classes <= 32:
+        raise ValueError("num_classes must be an integer in [1, 32], got %r" % (num_classes,))
+    if not (isinstance(pred_tracks, SceneTracks) and isinstance(gt_tracks, SceneTracks)):
+        raise TypeError("average_precision takes two SceneTracks")
+    if pred_tracks._slots != gt_tracks._slots:
+        raise ValueError("average_precision: the two stores do not hold the same scenes in the same slots (feed both with the same names)")
+    if pred_tracks.device != gt_tracks.device:
+        raise RuntimeError("average_precision: the stores are on %s and %s" % (pred_tracks.device, gt_tracks.device))
+    S = len(pred_tracks._slots)
+    if S * pred_tracks.max_tracks > AP_MAX_POSITIONS:
+        raise ValueError("average_precision: %d scenes x %d tracks; at most %d positions are ranked" % (S, pred_tracks.max_tracks, AP_MAX_POSITIONS))
+    return thr, S
+
+
+def average_precision(pred_tracks, gt_tracks, thresholds, num_classes=9, curves=False, out=None):
+    """Average precision per (IoU threshold, class) from two ``SceneTracks`` with the same scenes in the same slots (include/parq_hip.h
+    parq_average_precision, where the rule is stated in full): (ap (T, num_classes) float64, counts (2, num_classes) int64, invalid
+    (2) int64), all on the device.  counts[0] / counts[1]: the ground-truth / ranked prediction tracks per class; invalid: tracks
+    that are not ranked (a label outside [0, num_classes), or a NaN score on the prediction side).  Only enqueues.  The reference's
+    evaluator has no AP: this is not one of its numbers.  The stores hold the tracks selected at the tracker's confidence threshold,
+    so a curve ends there.  ``curves=True`` appends a dict of the curve's parts: "order" (N) int32, "class_start" (num_classes + 1)
+    int32, "cum_tp" (T, N) int32, "pred_best" (scenes, pred max_tracks) float64, "pred_target" (the same shape) int32, with
+    N = scenes * pred max_tracks.  ``out``: an int64 device tensor of at least (T + 2) * num_classes + 2 elements to place the
+    three results in (ap first, its float64 bits), for callers that copy them back with more."""
+    thr, S = check_average_precision_args(pred_tracks, gt_tracks, thresholds, num_classes)
+    T, K = len(thr), num_classes
+    dev = pred_tracks.device
+    n = (T + 2) * K
+    if out is None:
+        out = torch.empty(n + 2, dtype=torch.int64, device=dev)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() >= n + 2
+    ap, counts, invalid = out[:T * K].view(torch.float64).view(T, K), out[T * K:n].view(2, K), out[n:n + 2]
+    N = S * pred_tracks.max_tracks
+    extra = None
+    if curves:
+        extra = {"order": torch.empty(N, dtype=torch.int32, device=dev), "class_start": torch.empty(K + 1, dtype=torch.int32, device=dev),
+                 "cum_tp": torch.empty(T, N, dtype=torch.int32, device=dev),
+                 "pred_best": torch.zeros(S, pred_tracks.max_tracks, dtype=torch.float64, device=dev),
+                 "pred_target": torch.full((S, pred_tracks.max_tracks), -1, dtype=torch.int32, device=dev)}
+    if S == 0:
+        out[:n + 2].zero_()
+        if curves:
+            extra["class_start"].zero_()
+        return (ap, counts, invalid, extra) if curves else (ap, counts, invalid)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        need = lib.parq_average_precision_workspace_bytes(S, pred_tracks.max_tracks, gt_tracks.max_tracks, T, K)
+        if gt_tracks._ws is None or gt_tracks._ws.numel() < need:
+            gt_tracks._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = gt_tracks._ws
+        opt = [C.c_void_p(extra[k].data_ptr()) if curves else None for k in ("order", "class_start", "cum_tp", "pred_best", "pred_target")]
+        _lib.check(lib.parq_average_precision(C.c_void_p(pred_tracks._store.data_ptr()), pred_tracks.max_tracks,
+                                              C.c_void_p(gt_tracks._store.data_ptr()), gt_tracks.max_tracks, S, (C.c_double * T)(*thr), T, K,
+                                              C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(ap.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                              C.c_void_p(invalid.data_ptr()), *opt, _lib.stream_ptr()),
+                   "parq_average_precision")
+    return (ap, counts, invalid, extra) if curves else (ap, counts, invalid)
